@@ -11,10 +11,15 @@ driver's 20 timed steps last seconds, not a third of a second).  value = pairs a
 Workload = BASELINE.json configs[2], the configuration the metric "extract+match+introspect" names: the introspection FCN
 runs on every left image inside the timed step and its cost map gates the left extractor.  --no-introspect measures
 configs[1] (extract + match only); the default run also reports that figure in `extract_match_only`, measured after the
-timed region.  Prints ONE JSON line on rank 0, carrying `roofline` for the dominant kernel (HIP events on its stream inside
-the timed region), `cpu_baseline` (ports of the reference CPU path timed on this box's host cores), and after the timed
-region: `latency_ms_batch1` (the per-call drop-in API on host buffers, the mode the reference runs at 10 fps) and
-`h2d_included` (the same stream fed from pinned host memory over PCIe, copies overlapped with compute).
+timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps, writes the outputs of the last timed launch sequence (--dump-outputs DIR)
+and prints the line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload description.
+--full adds everything else after the timed region: `roofline` for the dominant kernel (HIP events on its stream inside
+the timed region), the oracle spot check of the last timed launch sequence, the tracker report, `cpu_baseline` (ports of
+the reference CPU path timed on this box's host cores), `latency_ms_batch1` (the per-call drop-in API on host buffers, the
+mode the reference runs at 10 fps) and `h2d_included` (the same stream fed from pinned host memory over PCIe, copies
+overlapped with compute).  The timed steps are the same work in both modes.
 """
 import argparse
 import json
@@ -519,6 +524,60 @@ def h2d_included(torch, iv, fe, fcn, dev, P, n_batches, left, right, bgr, cost, 
                     "image crosses once, as colour (grey conversion on the device: ivf_frontend_run_color)"}
 
 
+DUMP_BYTES = 60 * 10 ** 6         # --dump-outputs: at most this much in all (under 64 MB however counted)
+DUMP_SEED = 0x1F5A                # the fixed sample of pairs / cost-map pixels when everything would not fit
+DUMP_COST_PIXELS = 1 << 19
+
+
+def dump_outputs(torch, outdir, fe, P, s_last, cost_u8, track_out):
+    """--dump-outputs: what the LAST timed launch sequence returned to its caller, read back right after the timed region, as
+    float32 .npy files (float64 where a float32 would not hold the value exactly).  Per pair and side (StereoFrontend.fetch,
+    padded with zeros to nfeatures; n_keypoints says how many are real): keypoints (x, y, size, angle, response, octave),
+    descriptors (32 bytes as 32 values), mvKeyQualScore; per pair: mvuRight, mvDepth.  All pairs when they fit, else a fixed,
+    seeded sample of pairs.  The FCN's u8 cost maps at a fixed, seeded sample of pixels (flat index into [P, H, W] beside them).
+    The tracker step's matches (per frame pair: the matched keypoint of the last frame for every keypoint of the current frame,
+    -1 for none) and match counts.  The inputs are seeded, so the same arguments give the same files from run to run."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    F = np.float32
+    out = {}
+    if track_out is not None:
+        tp_h, assign, nm = track_out
+        out["track_pairs"] = np.asarray(tp_h, F).reshape(-1, 2)
+        out["track_assign"] = assign.astype(F)
+        out["track_nmatches"] = nm[:len(out["track_pairs"])].astype(F)
+    if cost_u8 is not None:
+        flat = cost_u8.contiguous().reshape(-1)
+        k = min(flat.numel(), DUMP_COST_PIXELS)
+        idx = np.sort(rng.choice(flat.numel(), k, replace=False))
+        out["fcn_cost_u8_sample_index"] = idx.astype(np.float64)
+        out["fcn_cost_u8_sample"] = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().astype(F)
+    N = NFEAT
+    per_pair = 4 * (2 * N * (6 + 32 + 1) + 2 * N + 2 + 1)
+    room = (DUMP_BYTES - sum(a.nbytes for a in out.values()) - (1 << 16)) // per_pair
+    pairs = np.arange(P) if room >= P else np.sort(rng.choice(P, max(int(room), 1), replace=False))
+    n = len(pairs)
+    kps = np.zeros((n, 2, N, 6), F); desc = np.zeros((n, 2, N, 32), F); qual = np.zeros((n, 2, N), F)
+    nk = np.zeros((n, 2), F); ur = np.zeros((n, N), F); dp = np.zeros((n, N), F)
+    for i, p in enumerate(pairs):
+        for side in (0, 1):
+            r = fe.fetch(int(p), side)
+            m = len(r["kps"])
+            nk[i, side] = m
+            for j, f in enumerate(("x", "y", "size", "angle", "response", "octave")):
+                kps[i, side, :m, j] = r["kps"][f]
+            desc[i, side, :m] = r["desc"]; qual[i, side, :m] = r["quality"]
+            if side == 0:
+                ur[i, :m] = r["uright"]; dp[i, :m] = r["depth"]
+    out.update(pair_index=(s_last + pairs).astype(F), n_keypoints=nk, keypoints=kps, descriptors=desc, quality=qual, uright=ur, depth=dp)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BYTES, total
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {"dir": outdir, "files": sorted(out), "bytes": int(total), "pairs": n, "pairs_in_launch_sequence": P}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -531,9 +590,15 @@ def main():
     ap.add_argument("--stream", type=int, default=0, help="distinct pairs resident per GPU (default: 512; 128 for --config 4)")
     ap.add_argument("--introspect", action="store_true", help="(default) configs[2]: run the introspection FCN on every left image and gate keypoints with it")
     ap.add_argument("--no-introspect", action="store_true", help="configs[1]: extract + match only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything beyond the headline figure: "
+                    "rooflines, the oracle spot check of the last timed launch sequence, the tracker report, the isolated / configs[1] / "
+                    "PCIe-fed / batch-1 legs and the CPU baseline (off by default: a plain run prints only the headline line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed launch sequence "
+                    "returned (keypoints, descriptors, stereo matches, quality scores, a fixed sample of the FCN cost maps, the tracker's "
+                    "matches) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (rank 0's outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-extras", action="store_true", help="skip the post-run latency / PCIe-inclusive / configs[1] measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the post-run latency / PCIe-inclusive / configs[1] measurements")
     ap.add_argument("--force-gather", action="store_true", help="test aid: run the multi-GPU exchange step (RCCL all-gather of "
                     "the descriptor records) even with one rank")
     ap.add_argument("--track", action="store_true", help=argparse.SUPPRESS)      # r03 flag, now the default
@@ -737,13 +802,14 @@ def main():
     n_timed = min(args.steps * BPS, 64)
     if fcn is not None:
         fcn.status(sptr)                 # raises if any forward of the timed region drove an un-clamped activation out of the f16 range
-    fast_sum_ms, fast_n = fe.fast_ms_stats(n_timed)
-    if fcn is not None:
-        probe_sets = {}
-        for which in (0, 1):
-            fcn.probe_select(which); probe_sets[which] = fcn.probe_stats(n_timed)
-        fcn.probe_select(0)
-        probe_sum_ms, probe_n, probe_batch = probe_sets[0]
+    if args.full:
+        fast_sum_ms, fast_n = fe.fast_ms_stats(n_timed)
+        if fcn is not None:
+            probe_sets = {}
+            for which in (0, 1):
+                fcn.probe_select(which); probe_sets[which] = fcn.probe_stats(n_timed)
+            fcn.probe_select(0)
+            probe_sum_ms, probe_n, probe_batch = probe_sets[0]
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev if backend != "gloo" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -754,9 +820,44 @@ def main():
     # sanity on the last batch: keypoints were really produced and matched
     r0 = fe.fetch(0, 0)
     assert len(r0["kps"]) > NFEAT // 4 and (r0["uright"] >= 0).sum() > 20, "degenerate output"
+    line = {
+        "metric": METRIC, "value": round(value, 2), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "host_enqueue_ms_per_step_incl_backpressure": round(host_enqueue_bp_ms, 4),
+        "launches_per_step": round(launches / max(args.steps, 1), 1), "launches_per_launch_sequence": round(launches / max(args.steps * BPS, 1), 1),
+        "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "u8 (ORB) + f32 via split-f16 MFMA (FCN)" if args.introspect else "u8",
+        "data": "synthetic",
+        "config": {"workload": (WORKLOAD if args.introspect == CONFIGS[args.config]["introspect"] else
+                                CONFIGS[1]["name"] if args.config == 2 else WORKLOAD + " -- run with --no-introspect"),
+                   "baseline_config_index": args.config if (args.introspect or args.config != 2) else 1, "width": W, "height": H,
+                   "pairs_per_step_per_gpu": P * BPS, "pairs_per_launch_sequence": P, "launch_sequences_per_step": BPS,
+                   "distinct_pairs_per_gpu": n_stream, "nfeatures": NFEAT,
+                   "nlevels": 8, "scale_factor": 1.2, "fast_thresholds": [INI_TH, MIN_TH],
+                   "parallelism": "frames sharded %d-way, RCCL all-gather of descriptor blocks" % world if world > 1 else "1 GPU"},
+        "timed_region_s": round(dt, 3),
+        "track_in_timed_region": bool(track and len(tpairs_h)),
+        "cost_maps": ("written by the FCN into the front end's level-0 cost plane (ivf_frontend_cost_plane): no ingest copy" if cost_plane_mode else
+                      "FCN -> caller's buffer -> ingest copy" if fcn is not None else None),
+        "build": {"libivfront": iv.load().ivf_build_id().decode(), "sources": iv._lib.source_build_id()},
+        "full": bool(args.full),
+    }
+    s_last = ((nsub[0] - 1) % nslices) * P
+    if args.dump_outputs and rank == 0:
+        # read back before anything else runs on the front end: fetch(age 0) and the cost plane still hold the last timed launch sequence
+        last = (nsub[0] - 1) % 3
+        line["outputs"] = dump_outputs(torch, args.dump_outputs, fe, P, s_last,
+                                       (last_plane[0] if cost_plane_mode else cost) if fcn is not None else None,
+                                       (tpairs_h, assign3[last].cpu().numpy(), nm3[last].cpu().numpy()) if track and len(tpairs_h) else None)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if exchange:
+            dist.destroy_process_group()
+        return
+
     # parity spot check: 4 pairs of the LAST timed sub-batch -- results, inputs and (configs[2]) the cost maps that gated them
     # are copied out now, before anything else runs, and compared with the oracle below (never inside the timed region)
-    s_last = ((nsub[0] - 1) % nslices) * P
     spot_pairs = sorted({0, 1, P // 2, P - 1})
     if last_plane[0] is not None:
         cost.copy_(last_plane[0])                  # the maps that gated the last sub-batch, out of the context's plane (after the timed region)
@@ -1009,29 +1110,7 @@ def main():
                                     "note": "f16 MFMA flops issued by this launch (hi*hi + hi*lo + lo*hi); sustained clock under this kernel ~1.95 GHz"}
         else:
             roofline = fast_roof
-        out = {
-            "metric": METRIC, "value": round(value, 2), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "host_enqueue_ms_per_step": round(host_enqueue_ms, 4),
-            "host_enqueue_ms_per_step_incl_backpressure": round(host_enqueue_bp_ms, 4),
-            "launches_per_step": round(launches / max(args.steps, 1), 1), "launches_per_launch_sequence": round(launches / max(args.steps * BPS, 1), 1),
-            "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u8 (ORB) + f32 via split-f16 MFMA (FCN)" if args.introspect else "u8",
-            "data": "synthetic",
-            "config": {"workload": (WORKLOAD if args.introspect == CONFIGS[args.config]["introspect"] else
-                                    CONFIGS[1]["name"] if args.config == 2 else WORKLOAD + " -- run with --no-introspect"),
-                       "baseline_config_index": args.config if (args.introspect or args.config != 2) else 1, "width": W, "height": H,
-                       "pairs_per_step_per_gpu": P * BPS, "pairs_per_launch_sequence": P, "launch_sequences_per_step": BPS,
-                       "distinct_pairs_per_gpu": n_stream, "nfeatures": NFEAT,
-                       "nlevels": 8, "scale_factor": 1.2, "fast_thresholds": [INI_TH, MIN_TH],
-                       "parallelism": "frames sharded %d-way, RCCL all-gather of descriptor blocks" % world if world > 1 else "1 GPU"},
-            "timed_region_s": round(dt, 3),
-            "track_in_timed_region": bool(track and len(tpairs_h)),
-            "cost_maps": ("written by the FCN into the front end's level-0 cost plane (ivf_frontend_cost_plane): no ingest copy" if cost_plane_mode else
-                          "FCN -> caller's buffer -> ingest copy" if fcn is not None else None),
-            "build": {"libivfront": iv.load().ivf_build_id().decode(), "sources": iv._lib.source_build_id()},
-            "roofline": roofline,
-            "parity_spot_check": parity,
-        }
+        out = dict(line, host_enqueue_ms_per_step=round(host_enqueue_ms, 4), roofline=roofline, parity_spot_check=parity)
         if exch is not None:
             out["exchange"] = exch
         if trk is not None:

@@ -1,7 +1,9 @@
 """tools/export_fcn_weights.py on the artefact formats the reference ships / produces: a TorchScript archive traced and saved the way
 IF/training/export_model_light.py:114-121 does (what stereo_kitti.cc:236 `torch::jit::load`s), a whole-module state_dict, and
-separate encoder / decoder checkpoints (models_light.py:57-60, 81-84).  The reference model is IMPORTED here (build container
-only; nothing of it is committed) -- the test is skipped where /root/reference is absent."""
+separate encoder / decoder checkpoints (models_light.py:57-60, 81-84).  The module is rebuilt from the reference IntrospectionModule's
+state_dict layout recorded in tests/golden/fcn_state_dict_layout.json (names, shapes, dtypes, parameter or buffer, in the reference's
+order, num_batches_tracked included; tests/golden/make_fcn_layout.py), so every file below carries the reference's own keys."""
+import json
 import os
 import sys
 
@@ -9,27 +11,45 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/introspection_function"
+LAYOUT = os.path.join(ROOT, "tests", "golden", "fcn_state_dict_layout.json")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference's Python model is only present in the build container")
+
+def layout_module(W):
+    """an nn.Module whose state_dict has the recorded layout, floats from W; forward only has to be traceable"""
+    import torch
+
+    class Node(torch.nn.Module):
+        def forward(self, x):
+            return x
+
+    class Root(torch.nn.Module):
+        def forward(self, x):
+            return x * self.decoder.conv_last.weight.mean() + self.decoder.conv_last.bias
+
+    root = Root()
+    for name, shape, dtype, kind in json.load(open(LAYOUT)):
+        *path, leaf = name.split(".")
+        mod = root
+        for p in path:
+            if not hasattr(mod, p):
+                mod.add_module(p, Node())
+            mod = getattr(mod, p)
+        t = torch.zeros(shape, dtype=getattr(torch, dtype)) if name.endswith("num_batches_tracked") else torch.from_numpy(W[name].copy())
+        assert tuple(t.shape) == tuple(shape) and str(t.dtype) == "torch." + dtype, name
+        if kind == "parameter":
+            mod.register_parameter(leaf, torch.nn.Parameter(t, requires_grad=False))
+        else:
+            mod.register_buffer(leaf, t)
+    return root.eval()
 
 
 @pytest.fixture(scope="module")
 def model_and_weights():
-    import torch
-    sys.path.insert(0, REF)
-    from networks.models_light import models_light as ML, mobilenet
     from iv_slam_amd import fcn_weights
     W = fcn_weights.make_seeded_weights(11)
-    enc = ML.MobileNetV2Dilated(mobilenet.mobilenetv2(pretrained=False), 8)
-    dec = ML.C1DeepSup(num_class=1, fc_dim=320, regression_mode=True, inference_mode=True, out_size=(96, 128))
-    m = ML.IntrospectionModule(enc, dec, (512, 512), logistic_func=True).eval()
-    sd = m.state_dict()
-    for k in sd:
-        if not k.endswith("num_batches_tracked"):
-            sd[k] = torch.from_numpy(W[k].copy())
-    m.load_state_dict(sd)
+    m = layout_module(W)
+    assert [k for k in m.state_dict()] == [e[0] for e in json.load(open(LAYOUT))]
     return m, W
 
 

@@ -1,5 +1,6 @@
-"""bench.py's contract on a real GPU: one JSON line with the roofline and (optionally) cpu_baseline objects, and the
-multi-GPU exchange step (RCCL all-gather of descriptor records on a side stream) exercised with a single rank."""
+"""bench.py's contract on a real GPU: one JSON line; with --full the roofline and (optionally) cpu_baseline objects, and the
+multi-GPU exchange step (RCCL all-gather of descriptor records on a side stream) exercised with a single rank; without it the
+headline line alone, and --dump-outputs."""
 import json
 import os
 import subprocess
@@ -11,9 +12,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*extra):
+def _run(*extra, full=True):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *extra],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                        *(["--full"] if full else []), *extra],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -64,6 +66,32 @@ def test_tracker_step_is_timed_at_every_rank_count():
     assert j["track_in_timed_region"] is False and j["track"]["in_timed_region"] is False and j["track"]["parity_ok"] is True
 
 
+def test_plain_line_is_lean_and_dumps_are_reproducible(tmp_path):
+    """Without --full the line carries the headline figure only; --dump-outputs writes the outputs of the last timed launch sequence,
+    float32 / float64 and at most 64 MB, and a second run with the same workload (here with --full, whose oracle spot check covers
+    that same launch sequence) writes the same arrays."""
+    import numpy as np
+    da, db = str(tmp_path / "a"), str(tmp_path / "b")
+    j = _run("--pairs", "16", "--stream", "32", "--dump-outputs", da, full=False)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config", "build"):
+        assert k in j, k
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0 and j["full"] is False
+    for k in ("roofline", "roofline_fast_nms", "parity_spot_check", "track", "fcn_forward", "extract_match_only", "latency_ms_batch1",
+              "h2d_included", "cpu_baseline", "host_enqueue_ms_per_step"):
+        assert k not in j, k
+    jf = _run("--pairs", "16", "--stream", "32", "--dump-outputs", db)
+    assert jf["full"] is True and jf["parity_spot_check"]["ok"] is True and jf["track"]["parity_ok"] is True
+    files = sorted(f for f in os.listdir(da) if f.endswith(".npy"))
+    assert files == sorted(f + ".npy" for f in j["outputs"]["files"]) == sorted(os.listdir(db))
+    assert sum(os.path.getsize(os.path.join(da, f)) for f in files) <= 64 * 10 ** 6
+    for f in files:
+        a, b = np.load(os.path.join(da, f)), np.load(os.path.join(db, f))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    nk = np.load(os.path.join(da, "n_keypoints.npy"))
+    assert nk.shape == (16, 2) and (nk > 1000 // 4).all() and (np.load(os.path.join(da, "uright.npy")) > 0).sum(1).min() > 20
+    assert np.load(os.path.join(da, "track_assign.npy")).shape == (16, 1000) and np.load(os.path.join(da, "fcn_cost_u8_sample.npy")).max() > 0
+
+
 @pytest.mark.parametrize("cfg,pairs,w,h,n", [(3, 8, 1242, 375, 2000), (4, 4, 1920, 1200, 4000)])
 def test_other_baseline_configs_have_bench_lines(cfg, pairs, w, h, n):
     """bench.py --config 3 / --config 4 (BASELINE.json configs[3] / configs[4]): one contract line each, oracle spot check of the last
@@ -85,7 +113,7 @@ def test_ranks_on_one_gpu_through_gloo(ranks):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", IVF_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--pairs", "16", "--stream", "32"],
+                        "--full", "--no-cpu-baseline", "--pairs", "16", "--stream", "32"],
                        env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -115,7 +143,7 @@ def test_bench_gpus_flag_spawns_ranks_nccl():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--pairs", "16", "--stream", "32"],
+                        "--full", "--no-cpu-baseline", "--pairs", "16", "--stream", "32"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]

@@ -145,10 +145,8 @@ def test_settings_keys(tmp_path):
 
 
 def test_reference_settings_files_parse():
-    """The reference's own FileStorage files, where the reference tree is mounted (not on the GPU box)."""
-    d = "/root/reference/introspective_ORB_SLAM/Examples/Stereo"
-    if not os.path.isdir(d):
-        pytest.skip("reference tree not mounted")
+    """The reference's own FileStorage files (introspective_ORB_SLAM/Examples/Stereo), kept verbatim under tests/golden/settings/."""
+    d = os.path.join(ROOT, "tests", "golden", "settings")
     S = kitti.Settings.load(os.path.join(d, "KITTI00-02.yaml"))
     assert S.extractor_params()[:5] == (2000, 1.2, 8, 20, 7) or S.extractor_params()[2:5] == (8, 20, 7)
     assert abs(S.stereo()[0] - 386.1448) < 1e-6

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; tag=$1; shift
 for kv in "$@"; do export "$kv"; done
 O=$R/gpurun_out/feprof_$tag; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o p -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --serial --no-introspect > $O/log.txt 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o p -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --serial --no-introspect > $O/log.txt 2>&1
 python3 - $O/p_kernel_stats.csv $tag <<'P'
 import csv, sys
 rows = [r for r in csv.DictReader(open(sys.argv[1])) if r["Name"].startswith("ivf::") or r["Name"].startswith("void ivf::")]

@@ -6,7 +6,7 @@ O=$R/gpurun_out/quick
 mkdir -p $O; rm -f $O/*
 cd /tmp; export TMPDIR=/tmp
 export IVF_NO_SIDE_BLUR=1      # as tools/profile_round.sh's *_serial runs: comparable with profiles/*_kernel_stats_config*_serial.csv
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o q -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --serial "$@" > $O/q.log 2>&1 < /dev/null
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o q -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --serial "$@" > $O/q.log 2>&1 < /dev/null
 echo "rc=$?"
 grep -h '^{"metric"' $O/q.log | cut -c1-400
 rm -f $O/*_kernel_trace.csv $O/*agent_info.csv

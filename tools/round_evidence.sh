@@ -9,7 +9,7 @@ mkdir -p $E; rm -f $E/*
 cd $R
 timeout 900 python3 -m pytest tests -m gpu -q 2>&1 | tail -3 > $E/pytest_gpu.txt; cat $E/pytest_gpu.txt
 for c in 2 1 3 4; do
-  timeout 900 python3 bench.py --config $c > $E/bench_config$c.log 2>&1; echo "bench config $c rc=$?"
+  timeout 900 python3 bench.py --full --config $c > $E/bench_config$c.log 2>&1; echo "bench config $c rc=$?"
   grep -h '^{"metric"' $E/bench_config$c.log | tail -1 > $E/bench_config$c.json
   python3 -c "import json,sys; d=json.load(open('$E/bench_config$c.json')); print('config $c', d['value'], d['ms_per_step'], (d.get('fcn_forward') or {}).get('us_per_image'), d.get('latency_ms_batch1'))" 2>&1 | cut -c1-300
 done

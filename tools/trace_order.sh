@@ -6,7 +6,7 @@ O=$R/gpurun_out/trace2
 K=$1; N=$2; shift; shift
 mkdir -p $O; rm -f $O/*
 cd /tmp; export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O -o t -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras --serial "$@" > $O/t.log 2>&1 < /dev/null
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O -o t -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras --serial "$@" > $O/t.log 2>&1 < /dev/null
 echo "rc=$?"
 python3 - "$O/t_kernel_trace.csv" "$K" "$N" <<'PY'
 import csv, sys
