@@ -406,6 +406,23 @@ int  ivf_fcn_forward_device_strided(ivf_fcn* f, const uint8_t* d_bgr, size_t ima
  * the handle that raised it: callers that overlap forwards of several handles on one device must treat IVF_E_STATE from ANY of them as
  * invalidating the forwards of ALL of them since their last checks (bench.py and the reference's one-network-per-process use a single handle). */
 int  ivf_fcn_status(ivf_fcn* f, void* hip_stream);
+/* The other stereo driver's call contract (Examples/Stereo/stereo_airsim.cc:386-411), which resizes in u8 around the network:
+ * bgr (src_width x src_height) -> cv::resize INTER_LINEAR to the handle's in size (:389-390) -> forward (the module's interpolation to
+ * 512x512 is the identity when in = 512x512) -> u8 map (cost*255 truncated, :409) at the handle's out size -> cv::resize INTER_LINEAR to
+ * dst_width x dst_height (:410-411).  The rounding to u8 between the resizes and the network is the driver's: no combination of the calls
+ * above reproduces it.  The handle owns the scratch (max_batch u8 inputs at the in size, max_batch u8 maps at the out size, allocated by the
+ * first such call) and keeps the resize tables of the last (src, dst) geometry.  Input = BGR as for ivf_fcn_forward: the R/B swap of the
+ * network's input happens inside (a resize treats the channels alike, so swap-then-resize equals resize-then-swap).  The driver's swap is
+ * IN PLACE on imLeft (:386-387), which TrackStereo receives afterwards: that side effect is the caller's.
+ * Host buffers: rows of `stride` / `cost_stride` bytes; checks the f16-range flag like ivf_fcn_forward (IVF_E_STATE, output not written). */
+int  ivf_fcn_forward_resized(ivf_fcn* f, const uint8_t* bgr, int src_width, int src_height, int stride,
+                             uint8_t* cost_u8, int dst_width, int dst_height, int cost_stride);
+/* stereo_airsim.cc:386-411 for n <= max_batch device images (image i at d_bgr + i * image_stride, rows of row_stride bytes); map i at
+ * d_cost_u8 + i * cost_image_stride, rows of cost_row_stride bytes -- e.g. ivf_frontend_cost_plane's plane.  Asynchronous on hip_stream;
+ * check ivf_fcn_status afterwards like after ivf_fcn_forward_device. */
+int  ivf_fcn_forward_device_resized(ivf_fcn* f, const uint8_t* d_bgr, int src_width, int src_height, size_t image_stride, int row_stride, int n,
+                                    uint8_t* d_cost_u8, int dst_width, int dst_height, size_t cost_image_stride, int cost_row_stride,
+                                    void* hip_stream);
 
 /* ---- next rows of SURVEY section 8(f) ----
  * ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (ORB/src/ORBmatcher.cc:410-519):
@@ -571,6 +588,26 @@ int  ivf_remap_apply_device(ivf_remap* r, const uint8_t* d_src, int src_stride, 
                       int dst_stride, size_t dst_image_stride, int n_images, void* hip_stream);
 /* test aid: the fixed-point maps as cv::convertMaps would give them: xy [height][width][2] int16, alpha [height][width] (fy<<5|fx) */
 int  ivf_remap_get_fixed_maps(const ivf_remap* r, int16_t* xy, uint16_t* alpha);
+
+/* cv::resize(src, dst, cv::Size(dst_width, dst_height)) with the default INTER_LINEAR, 8-bit images of 1 or 3 interleaved channels
+ * (Examples/Stereo/stereo_airsim.cc:389-390: the RGB image to the network's 512x512 input; :410-411: the u8 cost map back to the image
+ * size).  OpenCV's fixed-point arithmetic, bit-exact: 11-bit coefficients, any down- or up-scale per axis.  The
+ * coefficient tables are built once per handle and stay on the device.  channels 1 or 3; sources of at most 65536 pixels per axis. */
+typedef struct ivf_resize ivf_resize;
+int  ivf_resize_create(int src_width, int src_height, int dst_width, int dst_height, int channels, int device_id, ivf_resize** out);
+void ivf_resize_destroy(ivf_resize* r);
+/* host buffers (drop-in for one cv::resize call, stereo_airsim.cc:389-390 / :410-411; synchronous) */
+int  ivf_resize_apply(ivf_resize* r, const uint8_t* src, int src_stride, uint8_t* dst, int dst_stride);
+/* device buffers (stereo_airsim.cc:389-390 / :410-411 for n_images images): image i at d_src + i * src_image_stride, rows of src_stride
+ * bytes, likewise the destination; on `hip_stream` (hipStream_t, NULL = default stream); asynchronous */
+int  ivf_resize_apply_device(ivf_resize* r, const uint8_t* d_src, int src_stride, size_t src_image_stride,
+                             uint8_t* d_dst, int dst_stride, size_t dst_image_stride, int n_images, void* hip_stream);
+/* test aid, host only, needs no device: one axis of ssize -> dsize as cv::resize builds it (stereo_airsim.cc:389-390 / :410-411), the
+ * table behind both the handles above and the extractor's pyramid: per destination index d the two source indices the pass reads,
+ * idx0 = clip(s) and idx1 = clip(s + 1) with s = cvFloor(f), f = (float)((d + 0.5) * (1. / ((double)dsize / ssize)) - 0.5), and the
+ * 11-bit coefficients w0 = saturate_cast<short>((1 - (f - s)) * 2048), w1 = saturate_cast<short>((f - s) * 2048).  That is the row
+ * rule; the column rule is the same table with w0 = 2048, w1 = 0 where idx0 == idx1 (cv::resize clamps the column and sets fx = 0). */
+int  ivf_resize_axis_table(int ssize, int dsize, int32_t* idx0, int32_t* idx1, int16_t* w0, int16_t* w1);
 
 /* measurement aid (bench.py): HIP events bracket the network's most expensive launch (fused depthwise 3x3 + 1x1
  * projection 960 -> 160 of block 15, k_fcn_dwpw<5,4>) on the stream each forward runs on.  probe_stats returns the summed

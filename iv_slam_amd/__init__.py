@@ -8,5 +8,5 @@ from .orb import (ORBextractor, ORBmatcher, ORBVocabulary, ComputeStereoMatches,
                   ComputeDistinctiveDescriptors, DeviceFrame)
 from .frontend import StereoFrontend  # noqa: F401
 from .fcn import IntrospectionFCN  # noqa: F401
-from .rectify import initUndistortRectifyMap, Remap  # noqa: F401
+from .rectify import initUndistortRectifyMap, Remap, Resize, resize_linear  # noqa: F401
 from .track import BatchTracker  # noqa: F401

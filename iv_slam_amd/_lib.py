@@ -121,6 +121,11 @@ _SIGS = {
     "ivf_remap_apply": (C.c_int, [vp, vp, C.c_int, vp, C.c_int]),
     "ivf_remap_apply_device": (C.c_int, [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_size_t, C.c_int, vp]),
     "ivf_remap_get_fixed_maps": (C.c_int, [vp, vp, vp]),
+    "ivf_resize_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "ivf_resize_destroy": (None, [vp]),
+    "ivf_resize_apply": (C.c_int, [vp, vp, C.c_int, vp, C.c_int]),
+    "ivf_resize_apply_device": (C.c_int, [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_size_t, C.c_int, vp]),
+    "ivf_resize_axis_table": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp]),
     "ivf_test_retain_best": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int]),
     "ivf_frontend_create": (C.c_int, [C.POINTER(FrontendConfig), C.POINTER(vp)]),
     "ivf_frontend_destroy": (None, [vp]),
@@ -149,6 +154,9 @@ _SIGS = {
     "ivf_fcn_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "ivf_fcn_forward_device": (C.c_int, [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]),
     "ivf_fcn_status": (C.c_int, [vp, vp]),
+    "ivf_fcn_forward_resized": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
+    "ivf_fcn_forward_device_resized": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_size_t,
+                                                 C.c_int, vp]),
     "ivf_fcn_probe_enable": (C.c_int, [vp]),
     "ivf_fcn_probe_select": (C.c_int, [vp, C.c_int]),
     "ivf_fcn_probe_info": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_double)]),

@@ -213,34 +213,17 @@ int Context::build(const Tables& t, int w, int h, int maxImages, int sides, int 
         c.btileBases[l] = l < c.nlevels ? c.lv[l].btileBase : INT_MAX;
     }
 
-    // cv::resize coefficient table (OpenCV resize.cpp, INTER_LINEAR 8U): per output column
-    // {clamped sx, a0, a1}, per output row {clipped sy, b0, b1}; x clamps f to 0 at the right edge, y does not.
+    // cv::resize coefficient table (OpenCV resize.cpp, INTER_LINEAR 8U), from the axis rule shared with
+    // ivf_resize (resize_axis_table): per output column {clamped sx, a0, a1}, per output row {clipped sy, b0, b1}.
+    // pyr_tile reads rows y0 and min(y0 + 1, h - 1): the second row of the table for every level pair, which only down-scales
+    // (tests/test_resize_cpu.py checks that on the pyramids of the benchmark sizes).
     std::vector<ResizeCoef> tab;
-    auto sat = [](float v) { int i = cvRoundF(v); return (unsigned)(unsigned short)std::min(32767, std::max(-32768, i)); };
     for (int l = 1; l < c.nlevels; l++) {
         LevelGeom& D = c.lv[l]; const LevelGeom& S = c.lv[l - 1];
-        // cv::resize: inv_scale = (double)dsize / ssize, scale = 1. / inv_scale (not the direct quotient: the doubles can differ in the last bit)
-        const double sx_ = 1. / ((double)D.w / S.w), sy_ = 1. / ((double)D.h / S.h);
         D.rtX = (int)tab.size();
-        for (int dx = 0; dx < D.w; dx++) {
-            float fx = (float)((dx + 0.5) * sx_ - 0.5);
-            int sx = cvFloorF(fx);
-            fx -= sx;
-            if (sx < 0) { fx = 0; sx = 0; }
-            if (sx >= S.w - 1) { fx = 0; sx = S.w - 1; }
-            tab.push_back((ResizeCoef)sx | ((ResizeCoef)sat((1.f - fx) * 2048.f) << 16) | ((ResizeCoef)sat(fx * 2048.f) << 32));
-        }
+        resize_axis_pack(S.w, D.w, true, false, tab);
         D.rtY = (int)tab.size();
-        for (int dy = 0; dy < D.h; dy++) {
-            float fy = (float)((dy + 0.5) * sy_ - 0.5);
-            int sy = cvFloorF(fy);
-            fy -= sy;
-            // rows are clipped, coefficients are not (VResize reads clip(sy), clip(sy+1)); sy >= 0 for down-scaling
-            const int y0 = std::min(std::max(sy, 0), S.h - 1);
-            ResizeCoef b0 = sat((1.f - fy) * 2048.f), b1 = sat(fy * 2048.f);
-            if (sy < 0) { /* both taps clip to row 0 */ }
-            tab.push_back((ResizeCoef)y0 | (b0 << 16) | (b1 << 32));
-        }
+        resize_axis_pack(S.h, D.h, false, false, tab);
     }
     if (tab.empty()) tab.push_back(0);
 

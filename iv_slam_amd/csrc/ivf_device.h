@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>      // getenv behind IVF_EXP_ENV (experiment builds)
+#include <vector>
 #include "../../include/ivfront.h"
 
 namespace ivf {
@@ -52,8 +53,18 @@ struct Config {
     LevelGeom lv[kMaxLevels];
 };
 
-// cv::resize coefficient table entry: src index | coef0 << 16 | coef1 << 32 (11-bit fixed point, A-3)
+// cv::resize coefficient table entry: src index | coef0 << 16 | coef1 << 32 (11-bit fixed point, A-3); k_resize's entries also carry
+// the second source index in bits 48-63 (the pyramid's are zero there)
 typedef unsigned long long ResizeCoef;
+
+// The one restatement of cv::resize's INTER_LINEAR axis rule (ivf_rectify.hip).  For every destination index d:
+// s = cvFloor(f), f = (float)((d + 0.5) * scale - 0.5) with scale = 1. / ((double)dsize / ssize); idx0 = clip(s), idx1 = clip(s + 1),
+// w0 = saturate_cast<short>((1 - (f - s)) * 2048), w1 = saturate_cast<short>((f - s) * 2048): the rows the vertical pass reads and their
+// coefficients, which are not clipped.  Columns additionally set f - s to 0 where s < 0 or s >= ssize - 1, i.e. exactly where
+// idx0 == idx1: there w0 = 2048, w1 = 0.
+void resize_axis_table(int ssize, int dsize, int32_t* idx0, int32_t* idx1, int16_t* w0, int16_t* w1);
+// appends the dsize entries of one axis to `tab`: idx0 | w0 << 16 | w1 << 32 (| idx1 << 48 when withIdx1); columns get the edge rule
+void resize_axis_pack(int ssize, int dsize, bool columns, bool withIdx1, std::vector<ResizeCoef>& tab);
 
 #ifndef IVF_FAST_TH
 #define IVF_FAST_TH 32        // 64 measured slower: 405 vs 348 us per 128 images (occupancy: 32 KB of LDS per workgroup, ragged level edges)

@@ -4516,6 +4516,14 @@ struct ivf_fcn {
     char probeBName[96] = "";
     double probeBAlgoBytes = 0;
     int probeSel = 0;
+    // ivf_fcn_forward_resized / _device_resized (stereo_airsim.cc:386-411), all allocated by the first such call: the resize tables of the
+    // last geometry (src -> in size, 3 channels; out size -> dst, 1 channel), the u8 scratch [maxBatch] inputs at the in size and
+    // [maxBatch] maps at the out size, and the host path's pinned / device staging (source rows, then destination rows)
+    ivf_resize *rsIn = nullptr, *rsOut = nullptr;
+    int rsSrcW = 0, rsSrcH = 0, rsDstW = 0, rsDstH = 0;
+    uint8_t *dRsIn = nullptr, *dRsOut = nullptr, *dRsSrc = nullptr;
+    void* hRsPin = nullptr;
+    size_t rsPinCap = 0;
 };
 
 namespace {
@@ -5397,6 +5405,12 @@ void ivf_fcn_destroy(ivf_fcn* f)
     if (f->dStageU8) (void)hipFree(f->dStageU8);
     if (f->dStageF) (void)hipFree(f->dStageF);
     if (f->hPin) (void)hipHostFree(f->hPin);
+    ivf_resize_destroy(f->rsIn);
+    ivf_resize_destroy(f->rsOut);
+    if (f->dRsIn) (void)hipFree(f->dRsIn);
+    if (f->dRsOut) (void)hipFree(f->dRsOut);
+    if (f->dRsSrc) (void)hipFree(f->dRsSrc);
+    if (f->hRsPin) (void)hipHostFree(f->hRsPin);
     delete f;
 }
 
@@ -5538,6 +5552,96 @@ int ivf_fcn_forward(ivf_fcn* f, const uint8_t* bgr, int width, int height, int s
     }
     if (cost_u8) for (int y = 0; y < f->outH; y++) memcpy(cost_u8 + (size_t)y * cost_stride, hU8 + (size_t)y * f->outW, (size_t)f->outW);
     if (cost_f32) memcpy(cost_f32, hF, outPx * sizeof(float));
+    return IVF_OK;
+}
+
+// ---- stereo_airsim.cc:386-411: u8 resize -> forward -> u8 resize ----
+
+// the resize handles of the (src, dst) geometry of this call, built when it differs from the last call's; the scratch on first use
+static int resized_prepare(ivf_fcn* f, int sw, int sh, int dw, int dh)
+{
+    if (!f->dRsIn) {
+        FHIP(hipMalloc(&f->dRsIn, (size_t)f->maxBatch * f->inW * f->inH * 3));
+        FHIP(hipMalloc(&f->dRsOut, (size_t)f->maxBatch * f->outW * f->outH));
+    }
+    if (!f->rsIn || f->rsSrcW != sw || f->rsSrcH != sh) {
+        if (f->rsIn) { FHIP(hipDeviceSynchronize()); ivf_resize_destroy(f->rsIn); f->rsIn = nullptr; }      // its table may be in use
+        if (int rc = ivf_resize_create(sw, sh, f->inW, f->inH, 3, f->device, &f->rsIn)) return rc;
+        f->rsSrcW = sw; f->rsSrcH = sh;
+    }
+    if (!f->rsOut || f->rsDstW != dw || f->rsDstH != dh) {
+        if (f->rsOut) { FHIP(hipDeviceSynchronize()); ivf_resize_destroy(f->rsOut); f->rsOut = nullptr; }
+        if (int rc = ivf_resize_create(f->outW, f->outH, dw, dh, 1, f->device, &f->rsOut)) return rc;
+        f->rsDstW = dw; f->rsDstH = dh;
+    }
+    return IVF_OK;
+}
+
+static int resized_device(ivf_fcn* f, const uint8_t* dBgr, size_t imageStride, int rowStride, int n, uint8_t* dCost,
+                          size_t costImageStride, int costRowStride, hipStream_t st)
+{
+    const int inRow = f->inW * 3;
+    const size_t inImage = (size_t)inRow * f->inH, outImage = (size_t)f->outW * f->outH;
+    int rc;
+    if ((rc = ivf_resize_apply_device(f->rsIn, dBgr, rowStride, imageStride, f->dRsIn, inRow, inImage, n, st))) return rc;
+    if ((rc = ivf_fcn_forward_device(f, f->dRsIn, inImage, inRow, n, f->dRsOut, nullptr, st))) return rc;
+    return ivf_resize_apply_device(f->rsOut, f->dRsOut, f->outW, outImage, dCost, costRowStride, costImageStride, n, st);
+}
+
+int ivf_fcn_forward_device_resized(ivf_fcn* f, const uint8_t* d_bgr, int src_width, int src_height, size_t image_stride, int row_stride, int n,
+                                   uint8_t* d_cost_u8, int dst_width, int dst_height, size_t cost_image_stride, int cost_row_stride,
+                                   void* hip_stream)
+{
+    if (!f || !d_bgr || !d_cost_u8) return ffail(IVF_E_INVALID, "null argument");
+    if (n < 1 || n > f->maxBatch) return ffail(IVF_E_INVALID, "batch %d outside [1,%d]", n, f->maxBatch);
+    if (src_width < 1 || src_height < 1 || dst_width < 1 || dst_height < 1)
+        return ffail(IVF_E_INVALID, "bad sizes (source %dx%d, destination %dx%d)", src_width, src_height, dst_width, dst_height);
+    if (row_stride < 3 * src_width || (n > 1 && image_stride < (size_t)row_stride * (src_height - 1) + 3 * (size_t)src_width))
+        return ffail(IVF_E_INVALID, "input strides too small for %dx%d", src_width, src_height);
+    if (cost_row_stride < dst_width || (n > 1 && cost_image_stride < (size_t)cost_row_stride * (dst_height - 1) + dst_width))
+        return ffail(IVF_E_INVALID, "cost strides too small for %dx%d", dst_width, dst_height);
+    FHIP(hipSetDevice(f->device));
+    if (int rc = resized_prepare(f, src_width, src_height, dst_width, dst_height)) return rc;
+    return resized_device(f, d_bgr, image_stride, row_stride, n, d_cost_u8, cost_image_stride, cost_row_stride, (hipStream_t)hip_stream);
+}
+
+int ivf_fcn_forward_resized(ivf_fcn* f, const uint8_t* bgr, int src_width, int src_height, int stride,
+                            uint8_t* cost_u8, int dst_width, int dst_height, int cost_stride)
+{
+    if (!f || !bgr || !cost_u8) return ffail(IVF_E_INVALID, "null argument");
+    if (src_width < 1 || src_height < 1 || dst_width < 1 || dst_height < 1)
+        return ffail(IVF_E_INVALID, "bad sizes (source %dx%d, destination %dx%d)", src_width, src_height, dst_width, dst_height);
+    if (stride < 3 * src_width || cost_stride < dst_width) return ffail(IVF_E_INVALID, "stride too small");
+    FHIP(hipSetDevice(f->device));
+    if (int rc = resized_prepare(f, src_width, src_height, dst_width, dst_height)) return rc;
+    // pageable caller buffers: rows go through a pinned staging buffer of the handle (see ivf_fcn_forward), grown to the largest geometry seen
+    const size_t inBytes = (size_t)src_width * 3 * src_height, outBytes = (size_t)dst_width * dst_height;
+    const size_t pinBytes = inBytes + outBytes + 16;
+    if (pinBytes > f->rsPinCap) {
+        FHIP(hipDeviceSynchronize());
+        if (f->hRsPin) { FHIP(hipHostFree(f->hRsPin)); f->hRsPin = nullptr; }
+        if (f->dRsSrc) { FHIP(hipFree(f->dRsSrc)); f->dRsSrc = nullptr; }
+        f->rsPinCap = 0;
+        FHIP(hipHostMalloc(&f->hRsPin, pinBytes, hipHostMallocDefault));
+        FHIP(hipMalloc(&f->dRsSrc, pinBytes));
+        f->rsPinCap = pinBytes;
+    }
+    uint8_t* hIn = (uint8_t*)f->hRsPin; uint8_t* hOut = hIn + inBytes;
+    int* hSt = (int*)(hIn + ((inBytes + outBytes + 3) & ~(size_t)3));
+    uint8_t* dIn = f->dRsSrc; uint8_t* dOut = dIn + inBytes;
+    for (int y = 0; y < src_height; y++) memcpy(hIn + (size_t)y * src_width * 3, bgr + (size_t)y * stride, (size_t)src_width * 3);
+    FHIP(hipMemcpyAsync(dIn, hIn, inBytes, hipMemcpyHostToDevice, nullptr));
+    int rc = resized_device(f, dIn, inBytes, src_width * 3, 1, dOut, outBytes, dst_width, nullptr);
+    if (rc) return rc;
+    FHIP(hipMemcpyAsync(hOut, dOut, outBytes, hipMemcpyDeviceToHost, nullptr));
+    FHIP(hipMemcpyAsync(hSt, f->dStatus, sizeof(int), hipMemcpyDeviceToHost, nullptr));
+    FHIP(hipStreamSynchronize(nullptr));
+    if (*hSt) {                                 // as ivf_fcn_forward: no plausible-looking cost map leaves the call
+        FHIP(hipMemset(f->dStatus, 0, sizeof(int)));
+        return ffail(IVF_E_STATE, "ivf_fcn_forward_resized: an un-clamped activation left the f16 range (|x| >= 65504, flags 0x%x): the split-f16 "
+                                  "products of the next layer would be wrong; these weights need activations re-scaled", *hSt);
+    }
+    for (int y = 0; y < dst_height; y++) memcpy(cost_u8 + (size_t)y * cost_stride, hOut + (size_t)y * dst_width, (size_t)dst_width);
     return IVF_OK;
 }
 

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
+#include <climits>
 #include <cstring>
 #include <vector>
 #include "ivf_device.h"
@@ -33,7 +34,18 @@ struct ivf_remap {
     hipStream_t stream = nullptr;
 };
 
+struct ivf_resize {
+    int device = 0;
+    int sw = 0, sh = 0, dw = 0, dh = 0, cn = 1;     // source size, destination size, channels
+    ivf::ResizeCoef* dTab = nullptr;                 // [dw] column entries, then [dh] row entries (k_resize)
+    uint8_t *dSrc = nullptr, *dDst = nullptr;        // staging of the host-buffer entry point, allocated by its first call
+    uint8_t* hPin = nullptr;                         // ... and its pinned host twin (source rows, then destination rows)
+    hipStream_t stream = nullptr;
+};
+
 namespace {
+
+using ivf::ResizeCoef;
 
 // fixed-point bilinear weights of OpenCV's BilinearTab_i in closed form: the float products (1-fy)(1-fx) ... of
 // multiples of 1/32 are exact, so entry k = 32 * (5-bit factors); alpha 0 is the one table OpenCV's sum repair
@@ -98,7 +110,108 @@ int launch_remap(const ivf_remap* r, const uint8_t* dsrc, int sstride, size_t sr
     return IVF_OK;
 }
 
+// ---- cv::resize(src, dst, dsize, 0, 0, INTER_LINEAR), 8-bit, 1 or 3 interleaved channels (stereo_airsim.cc:389-390, :410-411) ----
+// OpenCV's fixed-point path: HResizeLinear with 11-bit coefficients into int, VResizeLinear's
+// ((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2.  The exact 2x downscale that OpenCV routes to INTER_AREA gives the same
+// bytes there (tests/test_gpu_resize.py).  Table entry (ResizeCoef): idx0 | w0 << 16 | w1 << 32 | idx1 << 48, columns then rows.
+//
+// Workgroup = 256 x 16 destination pixels: a wave owns 256 consecutive pixels of kResizeRows consecutive rows; lane i takes pixels
+// i, i+64, i+128, i+192 (k_remap's layout: every gather and every store of the wave touches consecutive addresses).  The column taps
+// and coefficients of a lane stay in registers for all its rows; the row index, hence both source rows and both row coefficients, is
+// wave-uniform.  Sources go through L1 / L2 straight from HBM (no LDS window): a source row serves the two or three destination rows
+// that read it from L2.
+constexpr int kResizeRows = 4;
+
+template <int CN>
+__global__ __launch_bounds__(256) void k_resize(const ResizeCoef* __restrict__ tx, const ResizeCoef* __restrict__ ty,
+                                                const uint8_t* __restrict__ src, size_t srcImage, int sstride,
+                                                uint8_t* __restrict__ dst, size_t dstImage, int dstride, int w, int h)
+{
+    const int xb = blockIdx.x * 256 + (threadIdx.x & 63);
+    const int dy0 = (blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * kResizeRows;
+    if (dy0 >= h) return;
+    const uint8_t* S = src + (size_t)blockIdx.z * srcImage;
+    uint8_t* D = dst + (size_t)blockIdx.z * dstImage;
+    int c0[4], c1[4];
+    unsigned a0[4], a1[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const ResizeCoef c = tx[min(xb + 64 * k, w - 1)];       // lanes past the row read the last column's taps, store nothing
+        c0[k] = (int)(c & 0xffff) * CN; c1[k] = (int)(c >> 48) * CN;
+        a0[k] = (unsigned)(c >> 16) & 0xffffu; a1[k] = (unsigned)(c >> 32) & 0xffffu;
+    }
+#pragma unroll
+    for (int r = 0; r < kResizeRows; r++) {
+        const int dy = dy0 + r;
+        if (dy >= h) break;
+        const ResizeCoef cy = ty[dy];
+        const uint8_t* r0 = S + (size_t)(cy & 0xffff) * sstride;
+        const uint8_t* r1 = S + (size_t)(cy >> 48) * sstride;
+        const unsigned b0 = (unsigned)(cy >> 16) & 0xffffu, b1 = (unsigned)(cy >> 32) & 0xffffu;
+        uint8_t* Dr = D + (size_t)dy * dstride;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = xb + 64 * k;
+#pragma unroll
+            for (int c = 0; c < CN; c++) {
+                // every coefficient is in [0, 2048]: the horizontal sums stay below 2^20, the vertical products below 2^27
+                const unsigned h0 = r0[c0[k] + c] * a0[k] + r0[c1[k] + c] * a1[k];
+                const unsigned h1 = r1[c0[k] + c] * a0[k] + r1[c1[k] + c] * a1[k];
+                const unsigned v = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2u) >> 2;
+                if (x < w) Dr[x * CN + c] = (uint8_t)v;
+            }
+        }
+    }
+}
+
+int launch_resize(const ivf_resize* r, const uint8_t* dsrc, int sstride, size_t srcImage, uint8_t* ddst, int dstride,
+                  size_t dstImage, int nImg, hipStream_t st)
+{
+    const int rowsPerGroup = 4 * kResizeRows;
+    const dim3 grid((r->dw + 255) / 256, (r->dh + rowsPerGroup - 1) / rowsPerGroup, nImg);
+    const ResizeCoef* tx = r->dTab;
+    const ResizeCoef* ty = r->dTab + r->dw;
+    if (r->cn == 1) k_resize<1><<<grid, 256, 0, st>>>(tx, ty, dsrc, srcImage, sstride, ddst, dstImage, dstride, r->dw, r->dh);
+    else k_resize<3><<<grid, 256, 0, st>>>(tx, ty, dsrc, srcImage, sstride, ddst, dstImage, dstride, r->dw, r->dh);
+    RHIPCHK(hipGetLastError());
+    return IVF_OK;
+}
+
 }  // namespace
+
+namespace ivf {
+
+void resize_axis_table(int ssize, int dsize, int32_t* idx0, int32_t* idx1, int16_t* w0, int16_t* w1)
+{
+    // cv::resize: inv_scale = (double)dsize / ssize, scale = 1. / inv_scale (not the direct quotient: the doubles can differ in the last bit)
+    const double scale = 1. / ((double)dsize / ssize);
+    auto sat = [](float v) { const int i = (int)lrintf(v); return (int16_t)(i < -32768 ? -32768 : i > 32767 ? 32767 : i); };
+    for (int d = 0; d < dsize; d++) {
+        float f = (float)((d + 0.5) * scale - 0.5);
+        int s = (int)f;
+        s -= s > f;                                             // cvFloor
+        f -= s;
+        idx0[d] = std::min(std::max(s, 0), ssize - 1);
+        idx1[d] = std::min(std::max(s + 1, 0), ssize - 1);
+        w0[d] = sat((1.f - f) * 2048.f);
+        w1[d] = sat(f * 2048.f);
+    }
+}
+
+void resize_axis_pack(int ssize, int dsize, bool columns, bool withIdx1, std::vector<ResizeCoef>& tab)
+{
+    std::vector<int32_t> i0(dsize), i1(dsize);
+    std::vector<int16_t> a0(dsize), a1(dsize);
+    resize_axis_table(ssize, dsize, i0.data(), i1.data(), a0.data(), a1.data());
+    for (int d = 0; d < dsize; d++) {
+        // columns: cv::resize clamps the column and sets fx = 0 where s < 0 or s >= ssize - 1, i.e. where both taps are one column
+        const bool edge = columns && i0[d] == i1[d];
+        const ResizeCoef c0 = edge ? 2048 : (uint16_t)a0[d], c1 = edge ? 0 : (uint16_t)a1[d];
+        tab.push_back((ResizeCoef)i0[d] | (c0 << 16) | (c1 << 32) | (withIdx1 ? (ResizeCoef)i1[d] << 48 : 0));
+    }
+}
+
+}  // namespace ivf
 
 extern "C" {
 
@@ -250,6 +363,98 @@ int ivf_remap_get_fixed_maps(const ivf_remap* r, int16_t* xy, uint16_t* alpha)
             alpha[(size_t)y * r->w + x] = ha[(size_t)y * r->wp + x];
         }
     return IVF_OK;
+}
+
+// ---- cv::resize INTER_LINEAR, 8UC1 / 8UC3 (stereo_airsim.cc:389-390 input image, :410-411 cost map) ----
+
+int ivf_resize_axis_table(int ssize, int dsize, int32_t* idx0, int32_t* idx1, int16_t* w0, int16_t* w1)
+{
+    if (!idx0 || !idx1 || !w0 || !w1) return rfail(IVF_E_INVALID, "null argument");
+    if (ssize < 1 || dsize < 1 || ssize > 65536) return rfail(IVF_E_INVALID, "axis %d -> %d: sizes must be >= 1, the source at most 65536", ssize, dsize);
+    ivf::resize_axis_table(ssize, dsize, idx0, idx1, w0, w1);
+    return IVF_OK;
+}
+
+void ivf_resize_destroy(ivf_resize* r)
+{
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    if (r->stream) (void)hipStreamDestroy(r->stream);
+    if (r->dTab) (void)hipFree(r->dTab);
+    if (r->dSrc) (void)hipFree(r->dSrc);
+    if (r->dDst) (void)hipFree(r->dDst);
+    if (r->hPin) (void)hipHostFree(r->hPin);
+    delete r;
+}
+
+int ivf_resize_create(int src_width, int src_height, int dst_width, int dst_height, int channels, int device_id, ivf_resize** out)
+{
+    if (!out) return rfail(IVF_E_INVALID, "null argument");
+    *out = nullptr;
+    if (src_width < 1 || src_height < 1 || dst_width < 1 || dst_height < 1)
+        return rfail(IVF_E_INVALID, "bad sizes (source %dx%d, destination %dx%d)", src_width, src_height, dst_width, dst_height);
+    if (src_width > 65536 || src_height > 65536)           // the table holds source indices in 16 bits
+        return rfail(IVF_E_INVALID, "source %dx%d: at most 65536 pixels per axis", src_width, src_height);
+    if ((size_t)dst_width * channels > INT_MAX || (size_t)src_width * channels > INT_MAX)
+        return rfail(IVF_E_INVALID, "rows too long");
+    if (channels != 1 && channels != 3) return rfail(IVF_E_INVALID, "channels must be 1 or 3 (got %d)", channels);
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n <= 0) return rfail(IVF_E_NO_DEVICE, "no HIP device available (%s); libivfront has no CPU path",
+                                                e == hipSuccess ? "count 0" : hipGetErrorString(e));
+    if (device_id < 0 || device_id >= n) return rfail(IVF_E_INVALID, "device_id %d outside [0,%d)", device_id, n);
+    RHIPCHK(hipSetDevice(device_id));
+    ivf_resize* r = new ivf_resize();
+    r->device = device_id; r->sw = src_width; r->sh = src_height; r->dw = dst_width; r->dh = dst_height; r->cn = channels;
+    std::vector<ResizeCoef> tab;
+    tab.reserve((size_t)dst_width + dst_height);
+    ivf::resize_axis_pack(src_width, dst_width, true, true, tab);
+    ivf::resize_axis_pack(src_height, dst_height, false, true, tab);
+    if (hipMalloc(&r->dTab, tab.size() * sizeof(ResizeCoef)) != hipSuccess) {
+        ivf_resize_destroy(r);
+        return rfail(IVF_E_NO_DEVICE, "device allocation failed for a %dx%d -> %dx%d resize", src_width, src_height, dst_width, dst_height);
+    }
+    if (hipMemcpy(r->dTab, tab.data(), tab.size() * sizeof(ResizeCoef), hipMemcpyHostToDevice) != hipSuccess) {
+        ivf_resize_destroy(r);
+        return rfail(IVF_E_NO_DEVICE, "table upload failed");
+    }
+    *out = r;
+    return IVF_OK;
+}
+
+int ivf_resize_apply(ivf_resize* r, const uint8_t* src, int src_stride, uint8_t* dst, int dst_stride)
+{
+    if (!r || !src || !dst) return rfail(IVF_E_INVALID, "null argument");
+    if (src_stride < r->sw * r->cn || dst_stride < r->dw * r->cn) return rfail(IVF_E_INVALID, "stride smaller than a row");
+    RHIPCHK(hipSetDevice(r->device));
+    const size_t srow = (size_t)r->sw * r->cn, drow = (size_t)r->dw * r->cn;
+    const size_t sBytes = srow * r->sh, dBytes = drow * r->dh;
+    // the staging of this entry point exists only once it is used (the network's resizes run on device buffers only)
+    if (!r->stream) RHIPCHK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+    if (!r->dSrc) RHIPCHK(hipMalloc(&r->dSrc, sBytes));
+    if (!r->dDst) RHIPCHK(hipMalloc(&r->dDst, dBytes));
+    if (!r->hPin) RHIPCHK(hipHostMalloc((void**)&r->hPin, sBytes + dBytes, hipHostMallocDefault));
+    for (int y = 0; y < r->sh; y++) memcpy(r->hPin + (size_t)y * srow, src + (size_t)y * src_stride, srow);
+    RHIPCHK(hipMemcpyAsync(r->dSrc, r->hPin, sBytes, hipMemcpyHostToDevice, r->stream));
+    int rc = launch_resize(r, r->dSrc, (int)srow, 0, r->dDst, (int)drow, 0, 1, r->stream);
+    if (rc) return rc;
+    RHIPCHK(hipMemcpyAsync(r->hPin + sBytes, r->dDst, dBytes, hipMemcpyDeviceToHost, r->stream));
+    RHIPCHK(hipStreamSynchronize(r->stream));
+    for (int y = 0; y < r->dh; y++) memcpy(dst + (size_t)y * dst_stride, r->hPin + sBytes + (size_t)y * drow, drow);
+    return IVF_OK;
+}
+
+int ivf_resize_apply_device(ivf_resize* r, const uint8_t* d_src, int src_stride, size_t src_image_stride,
+                            uint8_t* d_dst, int dst_stride, size_t dst_image_stride, int n_images, void* hip_stream)
+{
+    if (!r || !d_src || !d_dst) return rfail(IVF_E_INVALID, "null argument");
+    if (n_images < 1 || n_images > 65535) return rfail(IVF_E_INVALID, "n_images %d outside [1,65535]", n_images);
+    if (src_stride < r->sw * r->cn || dst_stride < r->dw * r->cn) return rfail(IVF_E_INVALID, "stride smaller than a row");
+    if (n_images > 1 && (src_image_stride < (size_t)src_stride * (r->sh - 1) + (size_t)r->sw * r->cn ||
+                         dst_image_stride < (size_t)dst_stride * (r->dh - 1) + (size_t)r->dw * r->cn))
+        return rfail(IVF_E_INVALID, "image stride smaller than an image");
+    RHIPCHK(hipSetDevice(r->device));
+    return launch_resize(r, d_src, src_stride, src_image_stride, d_dst, dst_stride, dst_image_stride, n_images, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"

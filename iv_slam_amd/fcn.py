@@ -52,6 +52,33 @@ class IntrospectionFCN:
                                                None if cost_u8 is None else cost_u8.data_ptr(),
                                                None if cost_f32 is None else cost_f32.data_ptr(), stream_ptr))
 
+    def forward_resized(self, bgr_u8, dst_size):
+        """The AirSim driver's contract (Examples/Stereo/stereo_airsim.cc:386-411): bgr_u8 HxWx3 u8 host array of any size (rows may be
+        padded) -> cv::resize INTER_LINEAR to the handle's in size -> forward -> u8 map at the out size -> cv::resize INTER_LINEAR to
+        dst_size = (width, height).  Returns the u8 map [dst_h][dst_w]."""
+        img = np.asarray(bgr_u8)
+        assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3
+        if img.strides[1:] != (3, 1):
+            img = np.ascontiguousarray(img)
+        dw, dh = int(dst_size[0]), int(dst_size[1])
+        u8 = np.empty((dh, dw), np.uint8)
+        check(self._lib.ivf_fcn_forward_resized(self._h, img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0], img.strides[0],
+                                                ptr(u8), dw, dh, dw))
+        return u8
+
+    def forward_device_resized(self, bgr, cost_u8, dst_size, stream_ptr=None):
+        """stereo_airsim.cc:386-411 for a batch: bgr torch.uint8 [n,H,W,3] on the device (any H x W; rows / images may be padded),
+        cost_u8 torch.uint8 [n,dst_h,dst_w] (rows / images may be padded: e.g. StereoFrontend.cost_plane).  Asynchronous on
+        stream_ptr; check status() afterwards."""
+        n, h, w = bgr.shape[0], bgr.shape[1], bgr.shape[2]
+        st = bgr.stride()
+        assert bgr.shape[3] == 3 and st[3] == 1 and st[2] == 3, "interleaved BGR pixels; rows and images may be padded (a view of a larger tensor)"
+        dw, dh = int(dst_size[0]), int(dst_size[1])
+        cs = cost_u8.stride()
+        assert tuple(cost_u8.shape) == (n, dh, dw) and cs[2] == 1, "cost_u8 must be [n][%d][%d] with contiguous rows" % (dh, dw)
+        check(self._lib.ivf_fcn_forward_device_resized(self._h, bgr.data_ptr(), w, h, st[0], st[1], n, cost_u8.data_ptr(), dw, dh, cs[0], cs[1],
+                                                       stream_ptr))
+
     def status(self, stream_ptr=None):
         """waits for the stream and raises IvfError(IVF_E_STATE) if a forward of this handle since the last check drove an un-clamped
         activation out of the f16 range (|x| >= 65504: the split-f16 products of the next layer would be wrong); clears the flag."""

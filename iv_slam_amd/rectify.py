@@ -77,3 +77,81 @@ class Remap:
         xy = np.empty(self.shape + (2,), np.int16); al = np.empty(self.shape, np.uint16)
         check(self._lib.ivf_remap_get_fixed_maps(self._h, ptr(xy), ptr(al)))
         return xy, al
+
+
+class Resize:
+    """cv::resize(src, dst, dsize) with the default INTER_LINEAR for 8-bit images of 1 or 3 interleaved channels, bit-exact with OpenCV's
+    fixed-point path; the coefficient tables stay on the device.  One object per (source size, destination size, channel count), the way
+    the AirSim driver resizes its input image and its cost map (Examples/Stereo/stereo_airsim.cc:389-390, :410-411).
+    Sizes are (width, height) like cv::Size."""
+
+    def __init__(self, src_size, dst_size, channels=1, device_id=0):
+        self._lib = _lib.load()
+        self.src_size = (int(src_size[0]), int(src_size[1])); self.dst_size = (int(dst_size[0]), int(dst_size[1]))
+        self.channels = int(channels); self.device_id = device_id
+        h = C.c_void_p()
+        check(self._lib.ivf_resize_create(self.src_size[0], self.src_size[1], self.dst_size[0], self.dst_size[1], self.channels,
+                                          device_id, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.ivf_resize_destroy(self._h)
+            self._h = None
+
+    def _tail(self):
+        return (3,) if self.channels == 3 else ()
+
+    def __call__(self, image, out=None):
+        """host numpy [H][W] or [H][W][3] uint8 (rows may be padded: a view of a larger array) -> the resized image"""
+        img = np.asarray(image)
+        want = (self.src_size[1], self.src_size[0]) + self._tail()
+        if img.dtype != np.uint8 or img.shape != want:
+            raise AssertionError("image %s %s, resize built for %s uint8" % (img.shape, img.dtype, want))
+        if img.strides[1:] != ((3, 1) if self.channels == 3 else (1,)):
+            img = np.ascontiguousarray(img)          # only rows may be padded
+        if out is None:
+            out = np.empty((self.dst_size[1], self.dst_size[0]) + self._tail(), np.uint8)
+        elif out.shape != (self.dst_size[1], self.dst_size[0]) + self._tail() or out.dtype != np.uint8 or \
+                out.strides[1:] != ((3, 1) if self.channels == 3 else (1,)):
+            raise AssertionError("output must be a uint8 %s array whose rows may be padded" % ((self.dst_size[1], self.dst_size[0]) + self._tail(),))
+        check(self._lib.ivf_resize_apply(self._h, img.ctypes.data_as(C.c_void_p), img.strides[0], out.ctypes.data_as(C.c_void_p), out.strides[0]))
+        return out
+
+    def apply_device(self, src, out=None, stream_ptr=None):
+        """torch uint8 CUDA tensors [N][H][W] (1 channel) or [N][H][W][3]; rows and images may be padded (views of larger tensors).
+        Runs on `stream_ptr` (default: torch's current stream); returns `out` (allocated contiguous when None)."""
+        import torch
+        tail = self._tail()
+        pix = (3, 1) if self.channels == 3 else (1,)
+        if not (src.is_cuda and src.dtype == torch.uint8) or src.dim() != 3 + len(tail):
+            raise AssertionError("uint8 CUDA tensor [N][H][W]%s expected" % ("[3]" if tail else ""))
+        if tuple(src.shape[1:]) != (self.src_size[1], self.src_size[0]) + tail or src.stride()[2:] != pix:
+            raise AssertionError("source %s (strides %s), resize built for %s with interleaved pixels"
+                                 % (tuple(src.shape[1:]), src.stride(), (self.src_size[1], self.src_size[0]) + tail))
+        n = src.shape[0]
+        if out is None:
+            out = torch.empty((n, self.dst_size[1], self.dst_size[0]) + tail, dtype=torch.uint8, device=src.device)
+        if tuple(out.shape) != (n, self.dst_size[1], self.dst_size[0]) + tail or out.dtype != torch.uint8 or out.stride()[2:] != pix:
+            raise AssertionError("output must be uint8 %s with interleaved pixels" % ((n, self.dst_size[1], self.dst_size[0]) + tail,))
+        if stream_ptr is None:
+            stream_ptr = torch.cuda.current_stream(src.device).cuda_stream
+        ss, ds = src.stride(), out.stride()
+        check(self._lib.ivf_resize_apply_device(self._h, C.c_void_p(src.data_ptr()), ss[1], ss[0], C.c_void_p(out.data_ptr()), ds[1], ds[0],
+                                                n, C.c_void_p(stream_ptr)))
+        return out
+
+
+def resize_linear(img, dsize):
+    """cv::resize(img, dsize) (INTER_LINEAR) of one host uint8 image [H][W] or [H][W][3]; dsize = (width, height).  Builds the tables per
+    call: for a stream of same-size frames keep a Resize object instead."""
+    img = np.asarray(img)
+    return Resize((img.shape[1], img.shape[0]), dsize, 3 if img.ndim == 3 else 1)(img)
+
+
+def resize_axis_table(ssize, dsize):
+    """(idx0, idx1, w0, w1) of one ssize -> dsize axis as cv::resize builds it (ivf_resize_axis_table; no device needed)"""
+    lib = _lib.load()
+    i0 = np.empty(dsize, np.int32); i1 = np.empty(dsize, np.int32); w0 = np.empty(dsize, np.int16); w1 = np.empty(dsize, np.int16)
+    check(lib.ivf_resize_axis_table(int(ssize), int(dsize), ptr(i0), ptr(i1), ptr(w0), ptr(w1)))
+    return i0, i1, w0, w1

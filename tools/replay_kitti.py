@@ -4,7 +4,7 @@ reference's stereo driver (introspective_ORB_SLAM/Examples/Stereo/stereo_kitti.c
 System::TrackStereo would take over -- load pair, optional undistort/rectify remap, optional cost image (predicted
 heat maps from disk, remapped like the left image, :470-521), extract L/R, stereo match.
 
-  python tools/replay_kitti.py SEQUENCE_DIR SETTINGS.yaml [--rectify] [--undistort] [--qual DIR | --fcn WEIGHTS.bin] [--batch 16] [--track]
+  python tools/replay_kitti.py SEQUENCE_DIR SETTINGS.yaml [--rectify] [--undistort] [--qual DIR | --fcn WEIGHTS.bin [--fcn-input WxH]] [--batch 16] [--track]
   python tools/replay_kitti.py --make-synthetic DIR --frames 12        # writes a small synthetic sequence + settings
 
 Prints one line per frame (keypoints L/R, stereo matches, median depth) and the pairs/s of the device part.
@@ -107,7 +107,8 @@ def make_synthetic(root, frames, with_qual=True):
 class Replay:
     """The per-frame device work of the driver, batched: remap (optional) -> StereoFrontend."""
 
-    def __init__(self, settings, rectify=False, undistort=False, introspect=False, batch=16, device_id=0, fcn_blob=None, track=False):
+    def __init__(self, settings, rectify=False, undistort=False, introspect=False, batch=16, device_id=0, fcn_blob=None, track=False,
+                 fcn_input=None):
         import torch
         import iv_slam_amd as iv
         self.torch = torch; self.iv = iv
@@ -138,10 +139,14 @@ class Replay:
         self.scale_factors = iv.ORBextractor(nf, sf, nl, ini, mn).GetScaleFactors()
         # online inference of the introspection network (stereo_kitti.cc:493-514): the UN-remapped left image goes in,
         # the cost map comes out at the same size and is then remapped like the left image (:519-521)
+        # fcn_input = (w, h): the AirSim driver's contract instead (Examples/Stereo/stereo_airsim.cc:386-411): u8 resize of the left image
+        # to w x h, the network at w x h, u8 resize of its map back to the image size
         self.fcn = None
+        self.fcn_input = fcn_input
         if fcn_blob is not None:
             src = (int(settings["Camera.height"]), int(settings["Camera.width"]))
-            self.fcn = iv.IntrospectionFCN(fcn_blob, src, src, max_batch=batch, device_id=device_id)
+            net = src if fcn_input is None else (fcn_input[1], fcn_input[0])
+            self.fcn = iv.IntrospectionFCN(fcn_blob, net, net, max_batch=batch, device_id=device_id)
 
     def run(self, lefts, rights, costs=None, raw_lefts=None):
         """lists of host grey images (cost entries may be None; raw_lefts = the left frames as loaded, B,G,R or grey, for the
@@ -156,7 +161,11 @@ class Replay:
             Lraw = torch.from_numpy(np.stack(raw_lefts if raw_lefts is not None else lefts)).to(self.dev)
             bgr = Lraw if Lraw.dim() == 4 else Lraw.unsqueeze(-1).expand(-1, -1, -1, 3)      # grey frames: the same plane three times
             C = torch.empty(Lraw.shape[:3], dtype=torch.uint8, device=self.dev)
-            self.fcn.forward_device(bgr.contiguous(), cost_u8=C, stream_ptr=torch.cuda.current_stream().cuda_stream)
+            st = torch.cuda.current_stream().cuda_stream
+            if self.fcn_input is None:
+                self.fcn.forward_device(bgr.contiguous(), cost_u8=C, stream_ptr=st)
+            else:
+                self.fcn.forward_device_resized(bgr.contiguous(), C, (C.shape[2], C.shape[1]), st)
             if self.remapL is not None:
                 C = self.remapL.apply_device(C)
         elif costs is not None and any(c is not None for c in costs):
@@ -209,6 +218,8 @@ def main():
     ap.add_argument("--rectify", action="store_true"); ap.add_argument("--undistort", action="store_true")
     ap.add_argument("--qual", help="directory of predicted cost images (%%06d.*): enables the introspection-weighted extractor")
     ap.add_argument("--fcn", help="weights blob (tools/export_fcn_weights.py) or 'seeded': run the introspection network on every left image")
+    ap.add_argument("--fcn-input", help="WxH, e.g. 512x512: run the network through the AirSim driver's contract (stereo_airsim.cc:386-411: "
+                                        "u8 resize to WxH, forward at WxH, u8 resize of the map back to the image size)")
     ap.add_argument("--batch", type=int, default=16); ap.add_argument("--max-frames", type=int, default=0)
     ap.add_argument("--track", action="store_true", help="also replay the tracker's cross-frame matcher call (zero-motion prior) on resident frames")
     ap.add_argument("--make-synthetic"); ap.add_argument("--frames", type=int, default=12)
@@ -231,7 +242,14 @@ def main():
     if a.fcn:
         from iv_slam_amd import fcn_weights
         blob = fcn_weights.pack_blob(fcn_weights.make_seeded_weights(7)) if a.fcn == "seeded" else np.fromfile(a.fcn, np.float32)
-    rp = Replay(S, a.rectify, a.undistort, introspect=bool(a.qual), batch=batch, fcn_blob=blob, track=a.track)
+    fcn_input = None
+    if a.fcn_input:
+        if not a.fcn:
+            ap.error("--fcn-input needs --fcn")
+        fcn_input = tuple(int(v) for v in a.fcn_input.lower().split("x"))
+        if len(fcn_input) != 2 or min(fcn_input) < 1:
+            ap.error("--fcn-input takes WxH, e.g. 512x512")
+    rp = Replay(S, a.rectify, a.undistort, introspect=bool(a.qual), batch=batch, fcn_blob=blob, track=a.track, fcn_input=fcn_input)
     t_dev = 0.0; done = 0
     for i0 in range(0, n, batch):
         idx = [i for i in range(i0, min(i0 + batch, n)) if left[i]]
