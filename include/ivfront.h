@@ -135,6 +135,26 @@ typedef struct ivf_bounds { float min_x, min_y, max_x, max_y; } ivf_bounds;   /*
 int  ivf_features_in_area(const ivf_keypoint* kps, int n, const ivf_bounds* bounds,
                           float x, float y, float r, int min_level, int max_level,
                           int32_t* out, int cap, int* n_out);
+/* ---- Frame::UndistortKeyPoints / Frame::ComputeImageBounds (ORB/src/Frame.cc:696-726, :728-756) ----
+ * Both are cv::undistortPoints(src, dst, mK, mDistCoef, cv::Mat(), mK) (:714, :740) as OpenCV 4.x's plain C++ path computes it
+ * (DESIGN.md A-14): IEEE double throughout, EXACTLY five fixed-point iterations (TermCriteria(MAX_ITER, 5, 0.01): the count only,
+ * converged or not), float result.  mK and mDistCoef are CV_32F (ORB/src/Tracking.cc:106-123), hence float here.
+ * dist = k1,k2,p1,p2[,k3[,k4,k5,k6[,s1,s2,s3,s4]]]; n_dist 0, 4, 5, 8 or 12 as ivf_init_undistort_rectify_map accepts (tilt terms
+ * unsupported), anything else IVF_E_INVALID.  Like the reference, only k1 switches the undistortion on: with n_dist == 0 or
+ * dist[0] == 0 the keypoints are copied and the bounds are (0, 0, width, height), whatever the other coefficients say (:698-702, :730). */
+typedef struct ivf_camera { float fx, fy, cx, cy; float dist[12]; int32_t n_dist; } ivf_camera;
+/* Frame::ComputeImageBounds (Frame.cc:728-756): the four image corners (0,0), (width,0), (0,height), (width,height) undistorted;
+ * min_x = min(p0.x, p2.x), max_x = max(p1.x, p3.x), min_y = min(p0.y, p1.y), max_y = max(p2.y, p3.y).  Host only: needs no device. */
+int  ivf_image_bounds(const ivf_camera* cam, int width, int height, ivf_bounds* out);
+/* Frame::UndistortKeyPoints (Frame.cc:696-726) for one frame, host buffers, computed on the device: out[i] = kps[i] with pt
+ * undistorted; size, angle, response, octave are copied (:721-724).  out may alias kps; n == 0 is fine. */
+int  ivf_undistort_keypoints(const ivf_camera* cam, const ivf_keypoint* kps, int n, ivf_keypoint* out, int device_id);
+/* Frame::UndistortKeyPoints (Frame.cc:696-726) for n_frames frames in device memory: d_kps / d_out [n_frames][cap], d_count
+ * [n_frames] as the front end lays them out; slots at or past a frame's count are not written; d_out may be d_kps.  One kernel
+ * launch on hip_stream (hipStream_t, NULL = default stream), asynchronous; a camera that does not undistort copies the keypoints below each count. */
+int  ivf_undistort_keypoints_device(const ivf_camera* cam, const ivf_keypoint* d_kps, const int32_t* d_count, int n_frames, int cap,
+                                    ivf_keypoint* d_out, void* hip_stream);
+
 /* ORBmatcher::SearchByProjection(Frame& Current, const Frame& Last, th, bMono) (ORB/src/ORBmatcher.cc:1372-1518)
  * on flat, already-projected queries (one per last-frame map point that passed :1399-1421):
  *   q_u,q_v  projection (:1416-1417); q_ur = u - mbf*invzc (:1453); q_radius = th*mvScaleFactors[oct] (:1427);
@@ -260,6 +280,23 @@ int  ivf_frontend_fetch(ivf_frontend* fe, int pair, int side, ivf_keypoint* kps,
  * two further runs have been enqueued, so a caller that keeps three batches in flight reads each of them this way. */
 int  ivf_frontend_fetch_of(ivf_frontend* fe, int age, int pair, int side, ivf_keypoint* kps, uint8_t* desc, int cap, int* n_out,
                            float* uright, float* depth, float* quality);
+/* Frame::UndistortKeyPoints inside the batch (the stereo constructor's call, ORB/src/Frame.cc:145, :696-726).  With a camera set,
+ * every run from the next one on also produces mvKeysUn of the LEFT frames in its batch context, by one more kernel launch behind the
+ * batch (no host synchronisation, no allocation per run; three contexts in flight like every other result).  Only the left keypoints
+ * are undistorted: ComputeStereoMatches, the quality lookup and the descriptors keep using the distorted mvKeys (Frame.cc:130-146,
+ * :758-932), so ivf_frontend_device_results / _fetch / _fetch_of return exactly what they return without a camera.  What changes:
+ * ivf_frontend_undistorted / _fetch_undistorted below, the keypoint field of the gather records (ivf_frontend_pack_gather_block[_of])
+ * and the grid of ivf_frame_create_from_frontend (side 0).  cam == NULL, or a camera that does not undistort (n_dist == 0 or
+ * dist[0] == 0, Frame.cc:698-702), restores the behaviour of a handle that never had a camera.  The buffers are allocated by the
+ * first call that sets an undistorting camera. */
+int  ivf_frontend_set_camera(ivf_frontend* fe, const ivf_camera* cam);
+/* mvKeysUn of the run `age` runs back (Frame.cc:696-726), device-resident and addressed like d_kps of ivf_frontend_device_results(side 0):
+ * the LEFT frame of pair p at *d_kps_un + 2 * p * cap (the slots of the right frames in between are never written), counts = the left
+ * counts d_count[2 * p].  Valid like the other results of that run.  IVF_E_STATE when that run had no undistorting camera: mvKeysUn == mvKeys then (ivf_frontend_device_results). */
+int  ivf_frontend_undistorted(const ivf_frontend* fe, int age, const ivf_keypoint** d_kps_un);
+/* mvKeysUn of one pair's left frame to the host (synchronises), Frame.cc:696-726; a run without an undistorting camera returns
+ * mvKeys, as the reference does (:698-702). */
+int  ivf_frontend_fetch_undistorted(ivf_frontend* fe, int age, int pair, ivf_keypoint* kps_un, int cap, int* n_out);
 /* Elapsed milliseconds of the dominant kernel (FAST score + NMS) in the last run, from HIP events
  * recorded on the run's stream around that launch (bench.py's roofline leg); <0 if unavailable. */
 float ivf_frontend_last_fast_ms(ivf_frontend* fe);
@@ -270,7 +307,11 @@ int   ivf_frontend_fast_ms_stats(ivf_frontend* fe, int last_n, double* sum_ms, i
  * n_pairs fixed-size records {int32 n; int32 pad[3]; ivf_keypoint kps[cap]; uint8 desc[cap][32]; float uright[cap];
  * float depth[cap]} (the LEFT frame of each pair: mvKeys, mDescriptors, mvuRight, mvDepth -- what a rank needs to run the
  * tracker's cross-frame search against a frame extracted elsewhere, ivf_tracker_run below) and returns the record size in
- * *record_bytes (= ivf_track_record_bytes(cap)). */
+ * *record_bytes (= ivf_track_record_bytes(cap)).
+ * With a camera set for that run (ivf_frontend_set_camera) the keypoint field holds mvKeysUn instead of mvKeys (Frame.cc:696-726).
+ * The record layout and size do not change: the tracker step reads nothing but mvKeysUn, mvuRight, mvDepth and the descriptors from
+ * a record (ORB/src/ORBmatcher.cc:1372-1518, :45-135; Frame::UnprojectStereo, Frame.cc:958-972), and mvuRight / mvDepth are those
+ * of the distorted keypoints, as in the reference. */
 int  ivf_frontend_pack_gather_block(ivf_frontend* fe, uint8_t* d_block, size_t block_bytes, size_t* record_bytes,
                                     void* hip_stream);
 /* Same for the run `age` runs back (0 = the last one ... 2 = the oldest one still held).  Note that `hip_stream` waits
@@ -297,7 +338,10 @@ void* ivf_frontend_batch_stream(ivf_frontend* fe, int age);
  *      GetFeaturesInArea windows (ORB/src/Frame.cc:615-668), greedy assignment in last-keypoint order with the stereo check,
  *      rotation histogram + ComputeThreeMaxima (:1654-1695)
  *   -> the retry with th_retry when fewer than retry_below matches were found (Tracking.cc:1320-1330).
- * Keypoints are taken as undistorted (rectified stereo: mvKeysUn == mvKeys, Frame.cc:714 is a no-op there). */
+ * The keypoints of a record are mvKeysUn: for rectified stereo mvKeysUn == mvKeys (Frame.cc:698-702); for a lens-distorted camera
+ * set it on the front end (ivf_frontend_set_camera: the records then carry the undistorted keypoints, Frame.cc:696-726) or undistort
+ * hand-built records with ivf_undistort_keypoints_device, and take `bounds` from ivf_image_bounds (Frame.cc:728-756; min_x / min_y
+ * may be negative). */
 typedef struct ivf_track_config {
     int32_t nfeatures;                       /* capacity of a gather record (<= 4096) */
     int32_t nlevels;
@@ -548,7 +592,9 @@ int  ivf_frame_search_map_points(ivf_frame* f, int n_q, const float* q_u, const 
 
 /* A resident frame made straight from a batch of the front end (run `age` back, pair, side 0 = left / 1 = right): keypoints,
  * descriptors and uRight are copied device -> device and the grid is built on the device; only the keypoint count is read
- * back.  The greedy replays' host mirror (angle, octave, uRight: 28 B per keypoint) is fetched by the first search. */
+ * back.  The greedy replays' host mirror (angle, octave, uRight: 28 B per keypoint) is fetched by the first search.
+ * With a camera set for that run (ivf_frontend_set_camera) the left frame's keypoints and grid are those of mvKeysUn
+ * (Frame::AssignFeaturesToGrid reads mvKeysUn, ORB/src/Frame.cc:424); pass the bounds of ivf_image_bounds. */
 int  ivf_frame_create_from_frontend(ivf_frontend* fe, int age, int pair, int side, const ivf_bounds* bounds, ivf_frame** out);
 /* The remaining window searches against a resident frame: same semantics as ivf_search_keyframe_points, ivf_fuse_candidates
  * (the frame's own uRight is the keyframe's mvuRight), ivf_search_by_sim3 (two resident keyframes) and

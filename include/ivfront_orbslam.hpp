@@ -705,6 +705,41 @@ inline void ComputeStereoMatches(ORB_SLAM2::ORBextractor* left, ORB_SLAM2::ORBex
                                     mvuRight.data(), mvDepth.data());
     if (rc != IVF_OK) throw std::runtime_error(std::string("ivf_stereo_match: ") + ivf_last_error());
 }
+// mK (3x3 CV_32F) and mDistCoef (n x 1 or 1 x n CV_32F, n = 4, 5, 8 or 12; ORB/src/Tracking.cc:106-123) as an ivf_camera
+inline ivf_camera CameraOf(const cv::Mat& mK, const cv::Mat& mDistCoef)
+{
+    if (mK.rows != 3 || mK.cols != 3 || mK.type() != CV_32F) throw std::runtime_error("mK must be a 3x3 CV_32F matrix");
+    ivf_camera c{};
+    c.fx = mK.at<float>(0, 0); c.fy = mK.at<float>(1, 1); c.cx = mK.at<float>(0, 2); c.cy = mK.at<float>(1, 2);
+    const int n = mDistCoef.empty() ? 0 : mDistCoef.rows * mDistCoef.cols;
+    if (n > 0 && mDistCoef.type() != CV_32F) throw std::runtime_error("mDistCoef must be CV_32F");
+    if (n > 12) throw std::runtime_error("mDistCoef: at most 12 coefficients (tilt terms are not supported)");
+    for (int i = 0; i < n; i++) c.dist[i] = mDistCoef.at<float>(i / mDistCoef.cols, i % mDistCoef.cols);
+    c.n_dist = n;
+    return c;
+}
+// Body replacement for Frame::UndistortKeyPoints (ORB/src/Frame.cc:696-726): mvKeysUn from mvKeys, on the device.
+inline void UndistortKeyPoints(const std::vector<cv::KeyPoint>& mvKeys, const cv::Mat& mK, const cv::Mat& mDistCoef,
+                               std::vector<cv::KeyPoint>& mvKeysUn, int device_id = 0)
+{
+    const ivf_camera cam = CameraOf(mK, mDistCoef);
+    std::vector<ivf_keypoint> k(mvKeys.size());
+    for (size_t i = 0; i < mvKeys.size(); i++) k[i] = {mvKeys[i].pt.x, mvKeys[i].pt.y, mvKeys[i].size, mvKeys[i].angle, mvKeys[i].response, mvKeys[i].octave};
+    const int rc = ivf_undistort_keypoints(&cam, k.data(), (int)k.size(), k.data(), device_id);
+    if (rc != IVF_OK) throw std::runtime_error(std::string("ivf_undistort_keypoints: ") + ivf_last_error());
+    mvKeysUn = mvKeys;                                  // cv::KeyPoint kp = mvKeys[i]: every member but pt is kept (:721-724)
+    for (size_t i = 0; i < k.size(); i++) { mvKeysUn[i].pt.x = k[i].x; mvKeysUn[i].pt.y = k[i].y; }
+}
+// Body replacement for Frame::ComputeImageBounds (ORB/src/Frame.cc:728-756); cols, rows = imLeft.cols, imLeft.rows.  Host only.
+inline void ComputeImageBounds(int cols, int rows, const cv::Mat& mK, const cv::Mat& mDistCoef,
+                               float& mnMinX, float& mnMinY, float& mnMaxX, float& mnMaxY)
+{
+    const ivf_camera cam = CameraOf(mK, mDistCoef);
+    ivf_bounds b;
+    const int rc = ivf_image_bounds(&cam, cols, rows, &b);
+    if (rc != IVF_OK) throw std::runtime_error(std::string("ivf_image_bounds: ") + ivf_last_error());
+    mnMinX = b.min_x; mnMinY = b.min_y; mnMaxX = b.max_x; mnMaxY = b.max_y;
+}
 // Core of MapPoint::ComputeDistinctiveDescriptors (ORB/src/MapPoint.cc:247-312): index of the observed descriptor to keep.
 inline int DistinctiveDescriptorIndex(const std::vector<cv::Mat>& vDescriptors, int device_id = 0)
 {

@@ -24,6 +24,11 @@ class Bounds(C.Structure):
     _fields_ = [("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float)]
 
 
+class CameraC(C.Structure):
+    """ivf_camera (include/ivfront.h): mK and mDistCoef as the reference holds them, CV_32F (Tracking.cc:106-123)"""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("dist", C.c_float * 12), ("n_dist", C.c_int32)]
+
+
 class FrontendConfig(C.Structure):
     _fields_ = [("left", ExtractorParams), ("right", ExtractorParams), ("width", C.c_int32), ("height", C.c_int32),
                 ("max_pairs", C.c_int32), ("bf", C.c_float), ("b", C.c_float), ("device_id", C.c_int32)]
@@ -82,6 +87,12 @@ _SIGS = {
                                               vp, vp, C.c_int, vp, vp, C.POINTER(C.c_int), C.c_int]),
     "ivf_search_map_points": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(Bounds), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
                                         C.c_float, vp, C.POINTER(C.c_int), C.c_int]),
+    "ivf_image_bounds": (C.c_int, [C.POINTER(CameraC), C.c_int, C.c_int, C.POINTER(Bounds)]),
+    "ivf_undistort_keypoints": (C.c_int, [C.POINTER(CameraC), vp, C.c_int, vp, C.c_int]),
+    "ivf_undistort_keypoints_device": (C.c_int, [C.POINTER(CameraC), vp, vp, C.c_int, C.c_int, vp, vp]),
+    "ivf_frontend_set_camera": (C.c_int, [vp, C.POINTER(CameraC)]),
+    "ivf_frontend_undistorted": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+    "ivf_frontend_fetch_undistorted": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
     "ivf_update_quality_scores": (C.c_int, [vp, C.c_int, vp, vp, C.c_int]),
     "ivf_search_for_initialization": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(Bounds), vp, C.c_int, C.c_float, C.c_int,
                                                 vp, C.POINTER(C.c_int), C.c_int]),

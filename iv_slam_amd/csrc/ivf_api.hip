@@ -499,6 +499,12 @@ struct ivf_frontend {
     int lastPairs = 0;
     int pairsOf[kPipe] = {};            // batch size of the run each context holds
     long long runs = 0;
+    // Frame::UndistortKeyPoints inside the batch (ivf_frontend_set_camera): mvKeysUn of the left frames, one buffer per context
+    bool camOn = false;                 // an undistorting camera is set: runs from now on fill kpsUn of their context
+    ivf::UndistortCam cam{};
+    ivf_keypoint* kpsUn[kPipe] = {};    // addressed like Buffers::kps ([2 * max_pairs][nfeatures], the left frame of pair p at 2 * p: the odd frames are
+                                        // never written), so that every consumer of b.kps -- k_pack_gather -- runs unchanged; allocated by the first undistorting camera
+    bool unOf[kPipe] = {};              // the run each context holds was made with a camera
     int last() const { return (int)((runs + kPipe - 1) % kPipe); }      // context of the most recent run
 };
 
@@ -770,6 +776,74 @@ int ivf_stereo_match(const ivf_extractor* left, const ivf_extractor* right,
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(u_right, cl.b.uright, (size_t)n_left * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(depth, cl.b.depth, (size_t)n_left * sizeof(float), hipMemcpyDeviceToHost));
+    return IVF_OK;
+}
+
+// ---- Frame::UndistortKeyPoints / ComputeImageBounds (ORB/src/Frame.cc:696-756) ----
+static int check_camera(const ivf_camera* cam)
+{
+    if (!cam) return fail(IVF_E_INVALID, "null camera");
+    const int nd = cam->n_dist;
+    if (!(nd == 0 || nd == 4 || nd == 5 || nd == 8 || nd == 12))
+        return fail(IVF_E_INVALID, "distortion vector of %d coefficients (0, 4, 5, 8 or 12; tilt terms are not supported)", nd);
+    return IVF_OK;
+}
+// mDistCoef.at<float>(0) == 0.0 is the reference's only test (Frame.cc:698, :730)
+static bool camera_undistorts(const ivf_camera& cam) { return cam.n_dist > 0 && cam.dist[0] != 0.0f; }
+
+int ivf_image_bounds(const ivf_camera* cam, int width, int height, ivf_bounds* out)
+{
+    if (!out) return fail(IVF_E_INVALID, "null argument");
+    int rc = check_camera(cam);
+    if (rc) return rc;
+    if (width < 1 || height < 1) return fail(IVF_E_INVALID, "bad image size %dx%d", width, height);
+    if (!camera_undistorts(*cam)) { *out = ivf_bounds{0.0f, 0.0f, (float)width, (float)height}; return IVF_OK; }      // Frame.cc:749-755
+    const ivf::UndistortCam c = ivf::undistort_cam(*cam);
+    const float cx[4] = {0.0f, (float)width, 0.0f, (float)width}, cy[4] = {0.0f, 0.0f, (float)height, (float)height};   // :732-736
+    float x[4], y[4];
+    for (int i = 0; i < 4; i++) ivf::undistort_point(c, cx[i], cy[i], x[i], y[i]);
+    out->min_x = std::min(x[0], x[2]); out->max_x = std::max(x[1], x[3]);      // :743-746
+    out->min_y = std::min(y[0], y[1]); out->max_y = std::max(y[2], y[3]);
+    return IVF_OK;
+}
+
+int ivf_undistort_keypoints(const ivf_camera* cam, const ivf_keypoint* kps, int n, ivf_keypoint* out, int device_id)
+{
+    int rc = check_camera(cam);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!kps || !out))) return fail(IVF_E_INVALID, "bad argument");
+    if (n == 0) return IVF_OK;
+    if (!camera_undistorts(*cam)) { if (out != kps) memmove(out, kps, (size_t)n * sizeof(ivf_keypoint)); return IVF_OK; }   // Frame.cc:698-702
+    rc = have_device(device_id);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(device_id));
+    const size_t bytes = (size_t)n * sizeof(ivf_keypoint);
+    uint8_t* d = nullptr;
+    rc = thread_scratch(device_id, bytes + 16, &d);
+    if (rc) return rc;
+    int* dCount = (int*)d;
+    ivf_keypoint* dK = (ivf_keypoint*)(d + 16);
+    HIPCHK(hipMemcpy(dCount, &n, sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dK, kps, bytes, hipMemcpyHostToDevice));
+    launch_undistort_keys(ivf::undistort_cam(*cam), false, dK, 0, dCount, 0, 1, n, dK, 0, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, dK, bytes, hipMemcpyDeviceToHost));
+    return IVF_OK;
+}
+
+int ivf_undistort_keypoints_device(const ivf_camera* cam, const ivf_keypoint* d_kps, const int32_t* d_count, int n_frames, int cap,
+                                   ivf_keypoint* d_out, void* hip_stream)
+{
+    int rc = check_camera(cam);
+    if (rc) return rc;
+    if (n_frames < 0 || cap < 0 || n_frames > 65535) return fail(IVF_E_INVALID, "n_frames %d outside [0,65535] or negative cap %d", n_frames, cap);
+    if (n_frames == 0 || cap == 0) return IVF_OK;
+    if (!d_kps || !d_count || !d_out) return fail(IVF_E_INVALID, "null argument");
+    if ((((size_t)d_kps | (size_t)d_out) & 7) != 0) return fail(IVF_E_INVALID, "keypoint arrays must be 8-byte aligned");
+    const bool on = camera_undistorts(*cam);
+    if (!on && d_out == d_kps) return IVF_OK;
+    launch_undistort_keys(ivf::undistort_cam(*cam), !on, d_kps, (size_t)cap, d_count, 1, n_frames, cap, d_out, (size_t)cap, (hipStream_t)hip_stream);
+    HIPCHK(hipGetLastError());
     return IVF_OK;
 }
 
@@ -2120,6 +2194,7 @@ void ivf_frontend_destroy(ivf_frontend* fe)
         if (fe->evDone[k]) (void)hipEventSynchronize(fe->evDone[k]);      // never recorded = complete
     if (fe->dFlags) (void)hipFree(fe->dFlags);
     for (int k = 0; k < kPipe; k++) {
+        if (fe->kpsUn[k]) (void)hipFree(fe->kpsUn[k]);
         fe->ctx[k].release();
         // fe->stream[k] belongs to the process-wide pool: never destroyed
         if (fe->evIn[k]) (void)hipEventDestroy(fe->evIn[k]);
@@ -2204,6 +2279,11 @@ static int frontend_run_common(ivf_frontend* fe, const uint8_t* d_left, const ui
     if (rc) return rc;
     launch_stereo(c.hc, c.dc, c.b, n_pairs, fe->cfg.bf, fe->cfg.b, st);
     IVF_MARK(st, c.markOwn, 7, c.nRuns - 1);
+    // Frame::UndistortKeyPoints (Frame.cc:145, :696-726): the left frames only (images are interleaved L,R: every second frame of b.kps)
+    if (fe->camOn)
+        launch_undistort_keys(fe->cam, false, c.b.kps, (size_t)2 * c.hc.nfeatures, c.b.count, 2, n_pairs, c.hc.nfeatures, fe->kpsUn[k],
+                              (size_t)2 * c.hc.nfeatures, st);
+    fe->unOf[k] = fe->camOn;
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(fe->evDone[k], st));
     // the caller's stream may overwrite its input buffers once they have been ingested
@@ -2297,6 +2377,49 @@ int ivf_frontend_fetch(ivf_frontend* fe, int pair, int side, ivf_keypoint* kps, 
     return ivf_frontend_fetch_of(fe, 0, pair, side, kps, desc, cap, n_out, uright, depth, quality);
 }
 
+// Frame::UndistortKeyPoints inside the batch (Frame.cc:145, :696-726)
+int ivf_frontend_set_camera(ivf_frontend* fe, const ivf_camera* cam)
+{
+    if (!fe) return fail(IVF_E_INVALID, "null handle");
+    if (cam) { const int rc = check_camera(cam); if (rc) return rc; }
+    if (!cam || !camera_undistorts(*cam)) { fe->camOn = false; return IVF_OK; }     // Frame.cc:698-702: mvKeysUn = mvKeys
+    HIPCHK(hipSetDevice(fe->cfg.device_id));
+    const size_t bytes = (size_t)2 * fe->cfg.max_pairs * fe->ctx[0].hc.nfeatures * sizeof(ivf_keypoint);
+    for (int k = 0; k < kPipe; k++)
+        if (!fe->kpsUn[k]) HIPCHK(hipMalloc(&fe->kpsUn[k], bytes));
+    fe->cam = ivf::undistort_cam(*cam);       // passed to the kernel by value: batches already enqueued keep the camera they ran with
+    fe->camOn = true;
+    return IVF_OK;
+}
+
+int ivf_frontend_undistorted(const ivf_frontend* fe, int age, const ivf_keypoint** d_kps_un)
+{
+    if (!fe || !d_kps_un) return fail(IVF_E_INVALID, "null argument");
+    if (age < 0 || age >= kPipe || fe->runs <= age) return fail(IVF_E_STATE, "no batch of age %d is held", age);
+    const int k = (int)((fe->runs - 1 - age) % kPipe);
+    if (!fe->unOf[k]) return fail(IVF_E_STATE, "the batch of age %d ran without an undistorting camera: mvKeysUn == mvKeys", age);
+    *d_kps_un = fe->kpsUn[k];
+    return IVF_OK;
+}
+
+int ivf_frontend_fetch_undistorted(ivf_frontend* fe, int age, int pair, ivf_keypoint* kps_un, int cap, int* n_out)
+{
+    if (!fe || !n_out) return fail(IVF_E_INVALID, "bad argument");
+    if (age < 0 || age >= kPipe || fe->runs <= age) return fail(IVF_E_STATE, "no batch of age %d is held", age);
+    const int k = (int)((fe->runs - 1 - age) % kPipe);
+    if (!fe->unOf[k]) return ivf_frontend_fetch_of(fe, age, pair, 0, kps_un, nullptr, cap, n_out, nullptr, nullptr, nullptr);
+    if (pair < 0 || pair >= fe->pairsOf[k]) return fail(IVF_E_INVALID, "pair %d outside the batch of %d", pair, fe->pairsOf[k]);
+    int rc = ivf_frontend_sync(fe);
+    if (rc) return rc;
+    const size_t nf = fe->ctx[0].hc.nfeatures;
+    int n = 0;
+    HIPCHK(hipMemcpy(&n, fe->ctx[k].b.count + (size_t)pair * 2, sizeof(int), hipMemcpyDeviceToHost));
+    *n_out = n;
+    if (n > cap) return fail(IVF_E_CAPACITY, "%d keypoints exceed caller capacity %d", n, cap);
+    if (n > 0 && kps_un) HIPCHK(hipMemcpy(kps_un, fe->kpsUn[k] + (size_t)2 * pair * nf, (size_t)n * sizeof(ivf_keypoint), hipMemcpyDeviceToHost));
+    return IVF_OK;
+}
+
 float ivf_frontend_last_fast_ms(ivf_frontend* fe)
 {
     double sum = 0; int n = 0;
@@ -2342,7 +2465,7 @@ int ivf_frontend_pack_gather_block_of(ivf_frontend* fe, int age, uint8_t* d_bloc
     hipStream_t st = (hipStream_t)hip_stream;
     if (hip_stream == IVF_STREAM_OF_BATCH) st = fe->stream[k];        // in order behind the batch itself: nothing to wait for
     else HIPCHK(hipStreamWaitEvent(st, fe->evDone[k], 0));            // the batch ran on an internal stream
-    launch_pack_gather(fe->ctx[k].b, (int)nf, np, d_block, rec, st);
+    launch_pack_gather(fe->ctx[k].b, fe->unOf[k] ? fe->kpsUn[k] : nullptr, (int)nf, np, d_block, rec, st);
     HIPCHK(hipGetLastError());
     return IVF_OK;
 }
@@ -2381,7 +2504,9 @@ int ivf_frame_create_from_frontend(ivf_frontend* fe, int age, int pair, int side
         hipStreamSynchronize(f->stream) != hipSuccess) return bail("count read");
     f->n = n;
     if (n > 0) {
-        if (hipMemcpyAsync(f->dKps, b.kps + img * nf, (size_t)n * sizeof(ivf_keypoint), hipMemcpyDeviceToDevice, f->stream) != hipSuccess ||
+        // Frame::AssignFeaturesToGrid reads mvKeysUn (Frame.cc:424): the left frame of a run made with a camera
+        const ivf_keypoint* srcKps = (side == 0 && fe->unOf[k]) ? fe->kpsUn[k] + img * nf : b.kps + img * nf;
+        if (hipMemcpyAsync(f->dKps, srcKps, (size_t)n * sizeof(ivf_keypoint), hipMemcpyDeviceToDevice, f->stream) != hipSuccess ||
             hipMemcpyAsync(f->dDesc, b.desc + img * nf * 32, (size_t)n * 32, hipMemcpyDeviceToDevice, f->stream) != hipSuccess)
             return bail("device copy");
         if (side == 0) { if (hipMemcpyAsync(f->dUright, b.uright + (size_t)pair * nf, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, f->stream) != hipSuccess) return bail("device copy"); }

@@ -66,6 +66,38 @@ void resize_axis_table(int ssize, int dsize, int32_t* idx0, int32_t* idx1, int16
 // appends the dsize entries of one axis to `tab`: idx0 | w0 << 16 | w1 << 32 (| idx1 << 48 when withIdx1); columns get the edge rule
 void resize_axis_pack(int ssize, int dsize, bool columns, bool withIdx1, std::vector<ResizeCoef>& tab);
 
+// The one text of cv::undistortPoints(src, dst, K, D, cv::Mat(), K) for one point, shared by the host entry points and
+// k_undistort_keys (Frame::UndistortKeyPoints / ComputeImageBounds, ORB/src/Frame.cc:714, :740).  K and D are CV_32F in
+// the reference (ORB/src/Tracking.cc:106-123): widened here once, every intermediate is double, the result is narrowed once.
+// Five iterations whether converged or not (TermCriteria(MAX_ITER, 5, 0.01): the count only); RR = K * I is spelled out term by term.
+// The library is built with -ffp-contract=off: host and device round every operation alike.
+struct UndistortCam { double fx, fy, cx, cy, k[12]; };          // k = k1,k2,p1,p2,k3,k4,k5,k6,s1,s2,s3,s4 (missing ones 0)
+inline UndistortCam undistort_cam(const ivf_camera& c)
+{
+    UndistortCam u{};
+    u.fx = (double)c.fx; u.fy = (double)c.fy; u.cx = (double)c.cx; u.cy = (double)c.cy;
+    for (int i = 0; i < 12; i++) u.k[i] = i < c.n_dist ? (double)c.dist[i] : 0.;
+    return u;
+}
+__host__ __device__ inline void undistort_point(const UndistortCam& c, float px, float py, float& ox, float& oy)
+{
+    const double* k = c.k;
+    const double ifx = 1. / c.fx, ify = 1. / c.fy;
+    const double u = (double)px, v = (double)py;
+    double x = (u - c.cx) * ifx, y = (v - c.cy) * ify;
+    const double x0 = x, y0 = y;
+    for (int j = 0; j < 5; j++) {
+        const double r2 = x * x + y * y;
+        const double icdist = (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2) / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2);
+        if (icdist < 0) { x = (u - c.cx) * ifx; y = (v - c.cy) * ify; break; }
+        const double dX = 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x) + k[8] * r2 + k[9] * r2 * r2;
+        const double dY = k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y + k[10] * r2 + k[11] * r2 * r2;
+        x = (x0 - dX) * icdist; y = (y0 - dY) * icdist;
+    }
+    const double xx = c.fx * x + 0. * y + c.cx, yy = 0. * x + c.fy * y + c.cy, ww = 1. / (0. * x + 0. * y + 1.);
+    ox = (float)(xx * ww); oy = (float)(yy * ww);
+}
+
 #ifndef IVF_FAST_TH
 #define IVF_FAST_TH 32        // 64 measured slower: 405 vs 348 us per 128 images (occupancy: 32 KB of LDS per workgroup, ragged level edges)
 #endif
@@ -158,7 +190,11 @@ void launch_grid_build(const ivf_keypoint* kps, int n, float minX, float minY, f
 void launch_grid_window(const ivf_keypoint* kps, const uint8_t* desc, const int* start, const int* idx, float minX, float minY,
                         float invW, float invH, int nq, const float* qu, const float* qv, const float* qr, const int* qminL,
                         const int* qmaxL, const uint8_t* qdesc, const uint8_t* qvalid, int cap, int* count, int* cand, hipStream_t s);
-void launch_pack_gather(const Buffers& b, int nf, int nPairs, uint8_t* block, size_t recBytes, hipStream_t s);
+// kpsUn != nullptr: the records carry these keypoints (mvKeysUn of the left frames, addressed like b.kps: pair p at 2 * p * nf) instead of b.kps
+void launch_pack_gather(const Buffers& b, const ivf_keypoint* kpsUn, int nf, int nPairs, uint8_t* block, size_t recBytes, hipStream_t s);
+// k_undistort_keys (ivf_rectify.hip): frame f reads kps + f * kpStride and count[f * cntStride], writes out + f * outStride (elements)
+void launch_undistort_keys(const UndistortCam& cam, bool passThrough, const ivf_keypoint* kps, size_t kpStride, const int* count, int cntStride,
+                           int nFrames, int cap, ivf_keypoint* out, size_t outStride, hipStream_t s);
 void launch_hamming_pairs(const uint8_t* a, const uint8_t* b, const int* pairs, int n, int* dist, hipStream_t s);
 void launch_distinct_median(const uint8_t* desc, int n, int* median, hipStream_t s);
 void launch_bow_transform(const int* childStart, const int* child, const uint8_t* nodeDesc, const uint8_t* desc, int n, int nidLevel,

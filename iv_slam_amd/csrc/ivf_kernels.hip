@@ -2508,9 +2508,10 @@ __global__ __launch_bounds__(256) void k_pack_gather(const int* __restrict__ cou
     copy(out + 4 + nk + nd + nf, z, nf);
 }
 
-void launch_pack_gather(const Buffers& b, int nf, int nPairs, uint8_t* block, size_t recBytes, hipStream_t s)
+void launch_pack_gather(const Buffers& b, const ivf_keypoint* kpsUn, int nf, int nPairs, uint8_t* block, size_t recBytes, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_pack_gather, dim3(nPairs), dim3(256), 0, s, b.count, b.kps, b.desc, b.uright, b.depth, nf, (unsigned*)block, recBytes / 4);
+    // the kernel itself is the one a handle without a camera runs: mvKeysUn is laid out like b.kps (left frame of pair p at 2 * p * nf)
+    hipLaunchKernelGGL(k_pack_gather, dim3(nPairs), dim3(256), 0, s, b.count, kpsUn ? kpsUn : b.kps, b.desc, b.uright, b.depth, nf, (unsigned*)block, recBytes / 4);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -177,9 +177,38 @@ int launch_resize(const ivf_resize* r, const uint8_t* dsrc, int sstride, size_t 
     return IVF_OK;
 }
 
+// ---- Frame::UndistortKeyPoints (ORB/src/Frame.cc:696-726) for a batch of frames: cv::undistortPoints per keypoint ----
+// One lane per keypoint slot, blockIdx.y = frame; lanes at or past the frame's count write nothing.  ~150 f64 operations per
+// keypoint in registers (ivf::undistort_point, the text the host entry points run), no LDS.  A keypoint is 24 bytes at 8-byte
+// alignment: one lane moves it as three 8-byte accesses, and the lanes of a wave cover 1536 consecutive bytes.  Only pt changes;
+// size, angle, response and octave are copied (:721-724).  `out` may be `kps` (every lane reads its keypoint before it writes it).
+// passThrough: the camera's k1 is 0, mvKeysUn = mvKeys (:698-702).
+__global__ __launch_bounds__(256) void k_undistort_keys(ivf::UndistortCam cam, int passThrough, const ivf_keypoint* kps, size_t kpStride,
+                                                        const int* __restrict__ count, int cntStride, int cap,
+                                                        ivf_keypoint* out, size_t outStride)
+{
+    const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int n = min(count[(size_t)f * cntStride], cap);
+    if (i >= n) return;
+    const uint2* src = (const uint2*)(kps + (size_t)f * kpStride + i);
+    const uint2 a = src[0], b = src[1], c = src[2];
+    float ox = __uint_as_float(a.x), oy = __uint_as_float(a.y);
+    if (!passThrough) ivf::undistort_point(cam, __uint_as_float(a.x), __uint_as_float(a.y), ox, oy);
+    uint2* dst = (uint2*)(out + (size_t)f * outStride + i);
+    dst[0] = make_uint2(__float_as_uint(ox), __float_as_uint(oy)); dst[1] = b; dst[2] = c;
+}
+
 }  // namespace
 
 namespace ivf {
+
+void launch_undistort_keys(const UndistortCam& cam, bool passThrough, const ivf_keypoint* kps, size_t kpStride, const int* count, int cntStride,
+                           int nFrames, int cap, ivf_keypoint* out, size_t outStride, hipStream_t s)
+{
+    if (nFrames < 1 || cap < 1) return;
+    hipLaunchKernelGGL(k_undistort_keys, dim3((cap + 255) / 256, nFrames), dim3(256), 0, s, cam, passThrough ? 1 : 0, kps, kpStride, count,
+                       cntStride, cap, out, outStride);
+}
 
 void resize_axis_table(int ssize, int dsize, int32_t* idx0, int32_t* idx1, int16_t* w0, int16_t* w1)
 {

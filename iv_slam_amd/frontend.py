@@ -88,6 +88,19 @@ class StereoFrontend:
             self._plane_views[key] = device_view_u8(p.value, (n, self.height, self.width), (ist.value, rst.value, 1), self.device_id)
         return self._plane_views[key]
 
+    def set_camera(self, camera):
+        """Frame::UndistortKeyPoints inside the batch (Frame.cc:696-726): with a Camera (iv_slam_amd.camera) whose k1 != 0 every
+        later run also keeps mvKeysUn of the left frames -- fetch(..., undistorted=True), the gather records and
+        DeviceFrame.from_frontend then carry them.  None (or a camera with k1 == 0) restores the plain behaviour."""
+        check(self._lib.ivf_frontend_set_camera(self._h, None if camera is None else C.byref(camera.c_struct())))
+
+    def undistorted_device_ptr(self, age=0):
+        """device pointer of mvKeysUn of the run `age` runs back (ivf_frontend_undistorted): the left frame of pair p at 2 * p * nfeatures
+        keypoints, like the left keypoints of ivf_frontend_device_results"""
+        p = C.c_void_p()
+        check(self._lib.ivf_frontend_undistorted(self._h, int(age), C.byref(p)))
+        return p.value
+
     def set_opencv_variant(self, blur=0, retain_best=0, atan2=0):
         check(self._lib.ivf_frontend_set_opencv_variant(self._h, int(blur), int(retain_best), int(atan2)))
 
@@ -103,8 +116,9 @@ class StereoFrontend:
         check(self._lib.ivf_frontend_fast_ms_stats(self._h, last_n, C.byref(s), C.byref(n)))
         return s.value, n.value
 
-    def fetch(self, pair, side, age=0):
-        """Results of one image of the run `age` runs back (0 = last; a run stays held until two further runs were enqueued)."""
+    def fetch(self, pair, side, age=0, undistorted=False):
+        """Results of one image of the run `age` runs back (0 = last; a run stays held until two further runs were enqueued).
+        undistorted=True (left frames): additionally kps_un = mvKeysUn (ivf_frontend_fetch_undistorted); kps stays mvKeys."""
         cap = self.nfeatures
         kps = np.zeros(cap, KP_DTYPE); desc = np.zeros((cap, 32), np.uint8)
         ur = np.zeros(cap, np.float32); dp = np.zeros(cap, np.float32); q = np.zeros(cap, np.float32)
@@ -114,6 +128,11 @@ class StereoFrontend:
         out = dict(kps=kps[:n].copy(), desc=desc[:n].copy(), quality=q[:n].copy())
         if side == 0:
             out.update(uright=ur[:n].copy(), depth=dp[:n].copy())
+        if undistorted:
+            assert side == 0, "only the left keypoints are undistorted (Frame.cc:145)"
+            ku = np.zeros(cap, KP_DTYPE); nu = C.c_int(0)
+            check(self._lib.ivf_frontend_fetch_undistorted(self._h, int(age), pair, ptr(ku), cap, C.byref(nu)))
+            out["kps_un"] = ku[:nu.value].copy()
         return out
 
     def gather_record_bytes(self):

@@ -121,6 +121,17 @@ class Settings(dict):
         bf = float(self["Camera.bf"]); fx = float(self["Camera.fx"])
         return bf, bf / fx
 
+    def camera(self):
+        """mK and mDistCoef as Tracking builds them (Tracking.cc:101-123): float32 fx, fy, cx, cy; four float32 coefficients
+        k1, k2, p1, p2 and a fifth, k3, only when Camera.k3 != 0 (an absent key reads as 0).  -> iv_slam_amd.camera.Camera"""
+        from .camera import Camera
+        f = lambda key: np.float32(float(self.get(key, 0.0)))
+        dist = [f("Camera.k1"), f("Camera.k2"), f("Camera.p1"), f("Camera.p2")]
+        k3 = f("Camera.k3")
+        if k3 != 0:
+            dist.append(k3)
+        return Camera(f("Camera.fx"), f("Camera.fy"), f("Camera.cx"), f("Camera.cy"), dist)
+
     def rectification(self, side):
         """(K, D, R, P, (width, height)) of LEFT / RIGHT (stereo_kitti.cc:250-272)."""
         return (self[side + ".K"], self[side + ".D"].ravel(), self[side + ".R"], self[side + ".P"],

@@ -5,6 +5,7 @@ System::TrackStereo would take over -- load pair, optional undistort/rectify rem
 heat maps from disk, remapped like the left image, :470-521), extract L/R, stereo match.
 
   python tools/replay_kitti.py SEQUENCE_DIR SETTINGS.yaml [--rectify] [--undistort] [--qual DIR | --fcn WEIGHTS.bin [--fcn-input WxH]] [--batch 16] [--track]
+                                                           [--undistort-keypoints]
   python tools/replay_kitti.py --make-synthetic DIR --frames 12        # writes a small synthetic sequence + settings
 
 Prints one line per frame (keypoints L/R, stereo matches, median depth) and the pairs/s of the device part.
@@ -108,7 +109,7 @@ class Replay:
     """The per-frame device work of the driver, batched: remap (optional) -> StereoFrontend."""
 
     def __init__(self, settings, rectify=False, undistort=False, introspect=False, batch=16, device_id=0, fcn_blob=None, track=False,
-                 fcn_input=None):
+                 fcn_input=None, undistort_keypoints=False):
         import torch
         import iv_slam_amd as iv
         self.torch = torch; self.iv = iv
@@ -135,6 +136,15 @@ class Replay:
             self.size = sL
         self.fe = iv.StereoFrontend(self.size[0], self.size[1], batch, nf, sf, nl, ini, mn, enableIntrospection=introspect or fcn_blob is not None,
                                     bf=bf, b=b, device_id=device_id)
+        # Frame::UndistortKeyPoints / ComputeImageBounds (Frame.cc:696-756) for a lens-distorted camera that is NOT rectified by remaps:
+        # the camera of the settings file (Tracking.cc:101-123) goes to the front end, every left fetch then reports mvKeysUn as "kps"
+        # (the distorted mvKeys stay available as "kps_raw") and the tracker replay uses the undistorted bounds
+        self.camera = None
+        self.bounds = (0.0, 0.0, float(self.size[0]), float(self.size[1]))
+        if undistort_keypoints:
+            self.camera = settings.camera()
+            self.fe.set_camera(self.camera)
+            self.bounds = tuple(float(v) for v in self.camera.image_bounds(self.size[0], self.size[1]))
         self.batch = batch
         self.scale_factors = iv.ORBextractor(nf, sf, nl, ini, mn).GetScaleFactors()
         # online inference of the introspection network (stereo_kitti.cc:493-514): the UN-remapped left image goes in,
@@ -177,7 +187,10 @@ class Replay:
         torch.cuda.current_stream().synchronize()
         self.fe.run(L, R, C)
         self.fe.sync()
-        res = [(self.fe.fetch(k, 0), self.fe.fetch(k, 1)) for k in range(n)]
+        res = [(self.fe.fetch(k, 0, undistorted=self.camera is not None), self.fe.fetch(k, 1)) for k in range(n)]
+        if self.camera is not None:
+            for l, _ in res:
+                l["kps_raw"] = l["kps"]; l["kps"] = l.pop("kps_un")
         if self.track:
             self._track(res)
         return res
@@ -200,7 +213,7 @@ class Replay:
                     valid=np.ones(len(lk), np.uint8), blocks=np.ones(len(lk), np.uint8))
 
     def _track(self, res):
-        bounds = (0.0, 0.0, float(self.size[0]), float(self.size[1]))
+        bounds = self.bounds
         for k in range(len(res)):
             last = self.prev_left if k == 0 else res[k - 1][0]
             if last is not None and (last["uright"] >= 0).any() and len(res[k][0]["kps"]):
@@ -222,6 +235,9 @@ def main():
                                         "u8 resize to WxH, forward at WxH, u8 resize of the map back to the image size)")
     ap.add_argument("--batch", type=int, default=16); ap.add_argument("--max-frames", type=int, default=0)
     ap.add_argument("--track", action="store_true", help="also replay the tracker's cross-frame matcher call (zero-motion prior) on resident frames")
+    ap.add_argument("--undistort-keypoints", action="store_true",
+                    help="Frame::UndistortKeyPoints with the settings file's Camera.k1..k3 (Frame.cc:696-726): report mvKeysUn instead of mvKeys "
+                         "and, with --track, search inside the undistorted image bounds (Frame.cc:728-756)")
     ap.add_argument("--make-synthetic"); ap.add_argument("--frames", type=int, default=12)
     a = ap.parse_args()
     from iv_slam_amd import kitti
@@ -249,7 +265,11 @@ def main():
         fcn_input = tuple(int(v) for v in a.fcn_input.lower().split("x"))
         if len(fcn_input) != 2 or min(fcn_input) < 1:
             ap.error("--fcn-input takes WxH, e.g. 512x512")
-    rp = Replay(S, a.rectify, a.undistort, introspect=bool(a.qual), batch=batch, fcn_blob=blob, track=a.track, fcn_input=fcn_input)
+    rp = Replay(S, a.rectify, a.undistort, introspect=bool(a.qual), batch=batch, fcn_blob=blob, track=a.track, fcn_input=fcn_input,
+                undistort_keypoints=a.undistort_keypoints)
+    if rp.camera is not None:
+        print("camera: %d distortion coefficients, k1 %s; image bounds %s" % (len(rp.camera.dist), "!= 0" if rp.camera.undistorts() else "== 0 (no-op)",
+                                                                               "[%.2f, %.2f] x [%.2f, %.2f]" % (rp.bounds[0], rp.bounds[2], rp.bounds[1], rp.bounds[3])))
     t_dev = 0.0; done = 0
     for i0 in range(0, n, batch):
         idx = [i for i in range(i0, min(i0 + batch, n)) if left[i]]
