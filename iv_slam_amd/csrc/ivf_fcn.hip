@@ -71,10 +71,8 @@ constexpr int kEnc = 512;                      // encoder input size (IF/config:
 constexpr int kSubBatch = 64;                  // images per launch sequence of ivf_fcn_forward_device (r06: see there)
 
 // ---- pre-processing + bilinear resize to 512x512 (stereo_kitti.cc:494-506, models_light.py:19-21) ----
-#ifndef IVF_PREP_ROWS
-#define IVF_PREP_ROWS 2          // measured 1 / 2 / 4 / 8: 176-178 / 151-154 / 153-157 / 161-170 us per 128 images
-#endif
-constexpr int kPrepRows = IVF_PREP_ROWS;       // output rows per thread of k_fcn_prep (grid y = kEnc / kPrepRows)
+// output rows per thread of k_fcn_prep (grid y = kEnc / kPrepRows); measured 1 / 2 / 4 / 8: 176-178 / 151-154 / 153-157 / 161-170 us per 128 images
+constexpr int kPrepRows = 2;
 __global__ void k_fcn_prep(const uint8_t* __restrict__ bgr, size_t imageStride, int rowStride, int w, int h,
                            float* __restrict__ out)
 {
@@ -421,37 +419,12 @@ __global__ __launch_bounds__(512, 4) void k_fcn_stem(const float* __restrict__ X
 // Weights: the expansion's and the projection's A operands come as the f16 hi / lo fragments k_fcn_gemm uses (one
 // 16-byte load per lane and fragment, L2-resident; the projection's are fetched at the top of a group and used after two
 // barriers, the expansion's one group ahead); depthwise taps and all BN scale / shift pairs sit in an LDS table.
-// diagnostic build (tools/build_variant.sh x -DIVF_IRB_TIMING=<input width of the instance: 256 block 2, 128 blocks 3 and 4>): s_memtime sums of wave 0 per
-// phase -- [0] window / table loads issued -> landed in LDS (first barrier), [1] B fragments of the window, [2] B1 expansion, [3] wait at the first
-// barrier of a group, [4] B2 stencil, [5] wait at the second barrier, [6] B3 projection, [7] epilogue; printed by ivf_fcn_destroy
-#ifdef IVF_IRB_TIMING
-__device__ unsigned long long g_irbTim[10];
-#define IRB_TIM(i) do { if (WI == IVF_IRB_TIMING && S == IVF_IRB_TIMING_S) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-    tacc[i] += t_ - tlast; tlast = t_; __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-#define IRB_TIM(i) do { } while (0)
-#endif
-// output rows per tile of blocks 2 / 3 / 4 (compile-time: tools/build_variant.sh measures others)
-#ifndef IVF_IRB_TH2
-#define IVF_IRB_TH2 2
-#endif
-#ifndef IVF_IRB_TH3
-#define IVF_IRB_TH3 4
-#endif
-#ifndef IVF_FCN_HEAD_IL_DEFAULT
-#define IVF_FCN_HEAD_IL_DEFAULT 0
-#endif
-#ifndef IVF_FCN_HEADCHUNK_DEFAULT
-#define IVF_FCN_HEADCHUNK_DEFAULT 0
-#endif
-#ifndef IVF_IRB_TH4
-#define IVF_IRB_TH4 4         // r05, measured per 128 images: block 4 at 1 / 2 / 4 rows 387 / 404 / 327 us; block 3 at 2 / 4 / 8 rows 708 / 468 / 569;
-#endif                        // block 2 at 2 / 4 rows 610 / 730 (profiles/r05_irb_tile_heights.txt): 2, 4, 4
-
-#ifndef IVF_IRB_REP
-#define IVF_IRB_REP 16
-#endif
-constexpr int kIrbRep = IVF_IRB_REP;          // copies of the A fragments of blocks 2-4 in global memory
+// output rows per tile of blocks 2 / 3 / 4.  r05, measured per 128 images: block 4 at 1 / 2 / 4 rows 387 / 404 / 327 us; block 3 at 2 / 4 / 8 rows 708 / 468 / 569;
+// block 2 at 2 / 4 rows 610 / 730 (profiles/r05_irb_tile_heights.txt): 2, 4, 4
+constexpr int kIrbTH2 = 2, kIrbTH3 = 4, kIrbTH4 = 4;
+constexpr int kHeadIlDefault = 0;             // default of the run-time selector IVF_FCN_HEAD_IL (experiment build)
+constexpr int kHeadChunkDefault = 0;          // default of the run-time selector IVF_FCN_HEADCHUNK (experiment build)
+constexpr int kIrbRep = 16;                   // copies of the A fragments of blocks 2-4 in global memory
 template <int S, int CIN, int HID, int COUT, bool RES, int WI, int TH>
 __global__ __launch_bounds__(512, 4) void k_fcn_irb(const float* __restrict__ X, const uint4* __restrict__ WqE_,
                                                 const float* __restrict__ se, const float* __restrict__ be,
@@ -484,9 +457,6 @@ __global__ __launch_bounds__(512, 4) void k_fcn_irb(const float* __restrict__ X,
     const int rx0 = ox0 * S - 1, ry0 = oy0 * S - 1;             // window origin in the input map
     const float* Xb = X + (size_t)b * CIN * WI * WI;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, hh = lane >> 5, col = lane & 31;
-#ifdef IVF_IRB_TIMING
-    unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
-#endif
     // r05: every wave of every resident workgroup reads the SAME few KB of A fragments per hidden group -- 512 waves per XCD on the same
     // cache lines, i.e. on a few L2 channels: measured, the wait for fragments requested a whole B2 + B3 earlier was 19k of a workgroup's
     // 61k cycles (block 3).  The host uploads kIrbRep copies; workgroups on one XCD (linear id = XCD mod 8) take different copies.
@@ -517,11 +487,7 @@ __global__ __launch_bounds__(512, 4) void k_fcn_irb(const float* __restrict__ X,
             const int yy = ry0 + r, xx = ox0 * S - 4 + 4 * q4;
             ok[k] = yy >= 0 && yy < WI && xx >= 0 && xx < WI;
             dst[k] = c * XPL + r * RP + 4 * q4;
-#ifdef IVF_IRB_ABL_PLANE      // timing-only probe (results wrong): every channel's window rows from plane 0 -- is the load phase bound by how many planes a window touches?
-            v4[k] = *(const float4*)(Xb + ((size_t)0 * WI + (ok[k] ? yy : 0)) * WI + (ok[k] ? xx : 0));
-#else
             v4[k] = *(const float4*)(Xb + (ilIn ? ((size_t)(ok[k] ? yy : 0) * CIN + c) * WI : ((size_t)c * WI + (ok[k] ? yy : 0)) * WI) + (ok[k] ? xx : 0));
-#endif
         }
         float4 t4[ITT];                                         // the parameter table: branch-free clamped loads, in flight with the window
 #pragma unroll
@@ -545,7 +511,6 @@ __global__ __launch_bounds__(512, 4) void k_fcn_irb(const float* __restrict__ X,
 #pragma unroll
     for (int q = 0; q < 16; q++) accO[q] = 0.f;
     __syncthreads();
-    IRB_TIM(0);
     // the expansion's B operand (the input window, split into f16 hi / lo) is the same for every hidden group: a wave
     // builds the fragments of its (at most TPW) position tiles once
     constexpr int TPW = (NTE + 7) / 8;
@@ -563,7 +528,6 @@ __global__ __launch_bounds__(512, 4) void k_fcn_irb(const float* __restrict__ X,
                 split_pair(x0, x1, xh[ti][st].u[jj], xl[ti][st].u[jj]);
             }
     }
-    IRB_TIM(1);
 #pragma unroll 1
     for (int g = 0; g < NG; g++) {
         HFrag ph[2], pl[2];                                     // projection fragments of this group: needed two barriers from now
@@ -612,24 +576,17 @@ __global__ __launch_bounds__(512, 4) void k_fcn_irb(const float* __restrict__ X,
             // round trip at the start of every group, although the expansion's own fragments had been loaded a group earlier
             // (inside `if (wv < NTP)` like their use: loaded unconditionally the compiler SINKS them into B3's block, two barriers down, right in
             // front of the MFMAs that need them.  The conservative vmcnt(0) the join costs now falls on waits that have nothing young to wait for)
-#ifdef IVF_IRB_ABL_FRAG        // timing-only probe (results wrong): fragments of group 0 only, loaded once -- what do the per-group fragment loads cost?
-            if (g == 0)
-#endif
             if (wv < NTP) {
 #pragma unroll
                 for (int st = 0; st < 2; st++) { ph[st].q = WqP[((2 * g + st) * 2 + 0) * 64 + lane]; pl[st].q = WqP[((2 * g + st) * 2 + 1) * 64 + lane]; }
             }
-#ifndef IVF_IRB_ABL_FRAG
             {                                                    // next group's expansion fragments: in flight during B2 / B3 (past the end: group 0's again, unused)
                 const int gn = g + 1 < NG ? g + 1 : 0;
 #pragma unroll
                 for (int st = 0; st < K16; st++) { eh[st].q = WqE[((st * NG + gn) * 2 + 0) * 64 + lane]; el[st].q = WqE[((st * NG + gn) * 2 + 1) * 64 + lane]; }
             }
-#endif
         }
-        IRB_TIM(2);
         __syncthreads();
-        IRB_TIM(3);
         {   // B2. depthwise 3x3 (stride S) + BN + ReLU6 of the group
             const int chl = tid >> 4, sub = tid & 15;
             constexpr int PX = TW * TH / 16;                    // pixels per thread: 2, 4 or 8
@@ -657,9 +614,7 @@ __global__ __launch_bounds__(512, 4) void k_fcn_irb(const float* __restrict__ X,
 #pragma unroll
             for (int p = 0; p < PX; p++) dp[p] = __builtin_amdgcn_fmed3f(__builtin_fmaf(o[p], dsc, dsh), 0.f, 6.f);
         }
-        IRB_TIM(4);
         __syncthreads();
-        IRB_TIM(5);
         if (wv < NTP) {   // B3. projection: K slice = this group's 32 hidden channels, N tile = pixels 32 wv .. 32 wv + 31
             const float* src = sD + 32 * wv + col;
 #pragma unroll
@@ -675,7 +630,6 @@ __global__ __launch_bounds__(512, 4) void k_fcn_irb(const float* __restrict__ X,
                 accO = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph[st].v, bh.v, accO, 0, 0, 0);
             }
         }
-        IRB_TIM(6);
     }
     if (wv < NTP) {   // C. BN (+ residual), store
         const int n = 32 * wv + col, y = oy0 + n / TW, x = ox0 + n % TW;
@@ -693,13 +647,6 @@ __global__ __launch_bounds__(512, 4) void k_fcn_irb(const float* __restrict__ X,
         }
         range_flag(amax);
     }
-#ifdef IVF_IRB_TIMING
-    if (WI == IVF_IRB_TIMING && S == IVF_IRB_TIMING_S) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        IRB_TIM(7);
-        if (tid == 0) { for (int i = 0; i < 8; i++) atomicAdd(&g_irbTim[i], tacc[i]); atomicAdd(&g_irbTim[8], 1ull); }
-    }
-#endif
 }
 
 // ---- blocks 5-11 (64 x 64 maps, stride 1, dilation 1 or 2, up to 64 input channels): whole block per launch ----
@@ -1367,12 +1314,7 @@ __global__ __launch_bounds__(256, 1) void k_fcn_conv3x3_all(const float* __restr
 // Geometry, epilogues and the small-batch ranges are k_fcn_conv3x3_all<3>'s; a unit's x window is loaded while the previous unit's MFMAs run, the A
 // operands of a (tile, dx) group two groups ahead.  Wq6 (make_gemm): per unit u = 3 s2 + dy, tile n, dx: [hi of step 2 s2][hi of step 2 s2 + 1][bf6
 // dwords 0-3][bf6 dwords 4-5 in .x .y], 64 lanes x uint4 each.
-#ifndef IVF_DEC_FP6
-#define IVF_DEC_FP6 2       // 0: three f16 products (k_fcn_conv3x3_all); 1: k_fcn_conv3x3_f6; 2: k_fcn_conv3x3_f6r where the ranges are whole K-step pairs, k_fcn_conv3x3_f6 elsewhere
-#endif
-#ifndef IVF_DEC6_ABL
-#define IVF_DEC6_ABL 0       // timing-only ablations (results wrong): 1 no x loads in the loop, 2 no A loads, 4 no f16 MFMAs, 8 no scaled MFMAs
-#endif
+constexpr int kDecFp6Default = 2;      // default of the run-time selector IVF_FCN_DEC6 (experiment build).  0: three f16 products (k_fcn_conv3x3_all); 1: k_fcn_conv3x3_f6; 2: k_fcn_conv3x3_f6r where the ranges are whole K-step pairs, k_fcn_conv3x3_f6 elsewhere
 constexpr int kDecSH = 3;                      // weights of the correction operand: w_hi 2^3 (< 16), w_lo 2^13 (<= 4) in e3m2 (largest 28)
 __global__ __launch_bounds__(256, 1) void k_fcn_conv3x3_f6(const float* __restrict__ X, const uint4* __restrict__ Wq6,
                                                           const float* __restrict__ scale, const float* __restrict__ shift,
@@ -1455,12 +1397,12 @@ __global__ __launch_bounds__(256, 1) void k_fcn_conv3x3_f6(const float* __restri
         // the neighbours' tiles ([0] = left neighbour's tile 3, [5] = right neighbour's tile 0) are NOT kept: 30 registers this one-wave-per-SIMD body does
         // not have beside the next unit's window; the groups with dx = 0 / dx = 2 pull them by DPP when they need them (36 moves per tile instead of 30 per unit)
         __builtin_amdgcn_sched_barrier(0);
-        if (!(IVF_DEC6_ABL & 1)) load_x(S, u + 1);      // the window of the next unit: lands under this unit's MFMAs
+        load_x(S, u + 1);      // the window of the next unit: lands under this unit's MFMAs
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int g = 0; g < 9; g++) {
             const int n = g / 3, dx = g % 3;
-            if (!(IVF_DEC6_ABL & 2)) { if (g + 2 < 9) load_a(ring[(g + 2) % 3], u, g + 2); else load_a(ring[(g + 2) % 3], u + 1, g + 2 - 9); }
+            if (g + 2 < 9) load_a(ring[(g + 2) % 3], u, g + 2); else load_a(ring[(g + 2) % 3], u + 1, g + 2 - 9);
             const AGrp& a = ring[g % 3];
             const i32x8 a6 = {(int)a.q.x, (int)a.q.y, (int)a.q.z, (int)a.q.w, (int)a.r.x, (int)a.r.y, 0, 0};
             int zz = 0;
@@ -1480,11 +1422,8 @@ __global__ __launch_bounds__(256, 1) void k_fcn_conv3x3_f6(const float* __restri
                                dppz(b6[srcI][4], shr, zz), dppz(b6[srcI][5], shr, zz), 0, 0};
                     sbq = dppz(sbv[srcI], shr, zz);
                 }
-                if (!(IVF_DEC6_ABL & 4)) {
                 acc[n][pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.h0.v, f0.v, acc[n][pt], 0, 0, 0);
                 acc[n][pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.h1.v, f1.v, acc[n][pt], 0, 0, 0);
-                }
-                if (!(IVF_DEC6_ABL & 8))
                 acc[n][pt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a6, bq, acc[n][pt], 3, 2, 0, 127 - 10 - kDecSH, 0, sbq);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1550,7 +1489,7 @@ __global__ __launch_bounds__(256, 1) void k_fcn_conv3x3_f6(const float* __restri
 }
 
 // ---- k_fcn_conv3x3_f6r (r06c): the same arithmetic with the two output rows of a wave sharing their input rows ----
-// k_fcn_conv3x3_f6 is bound by its window loads (983 MB per launch through L2 -> L1: every input row is fetched for three tap rows; timing ablations above).  There a
+// k_fcn_conv3x3_f6 is bound by its window loads (983 MB per launch through L2 -> L1: every input row is fetched for three tap rows; timing ablations of commit 6c47b43).  There a
 // lane's column is (row of the pair, 4-pixel group), so the lanes of one B fragment sit on two input rows and each (unit, row) loads its own.  Here a lane is a
 // TWO-pixel group of ONE row (32 lanes x 2 pixels = the 64 pixels of a row) and the wave keeps the accumulators of both output rows side by side: input row r serves
 // output row r with tap row 1 and output row r - 1 with tap row 2 ... -- in unit (s2, dy) output row y0 draws from input row y0 + dy - 1 and output row y0 + 1 from
@@ -1843,9 +1782,6 @@ __global__ __launch_bounds__(256, 2) void k_fcn_expand(const float* __restrict__
     const int myTiles = (nTiles - wave + 3) / 4;
     uint4 ring[RD][2];
     auto aload = [&](int it, int st, uint4 (&r)[2]) {
-#if IVF_EXPAND_ABL & 4
-        if (it > 0) return;                         // timing-only: the A fragments of the first tile are reused for every tile
-#endif
         const uint4* w = Wq + ((size_t)st * nTiles + wave + 4 * min(it, myTiles - 1)) * 128 + lane;
         r[0] = w[0]; r[1] = w[64];
     };
@@ -1864,17 +1800,12 @@ __global__ __launch_bounds__(256, 2) void k_fcn_expand(const float* __restrict__
         HFrag bh[PXT], bl[PXT];
 #pragma unroll
         for (int pt = 0; pt < PXT; pt++) { bh[pt].q = sB[((s * PXT + pt) * 2 + 0) * 64 + sl]; bl[pt].q = sB[((s * PXT + pt) * 2 + 1) * 64 + sl]; }
-#if IVF_EXPAND_ABL & 2
-#pragma unroll
-        for (int pt = 0; pt < PXT; pt++) acc[pt][s & 15] += __builtin_bit_cast(float, al.u[0] ^ bh[pt].u[1] ^ ah.u[2] ^ bl[pt].u[3]);
-#else
 #pragma unroll
         for (int pt = 0; pt < PXT; pt++) acc[pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al.v, bh[pt].v, acc[pt], 0, 0, 0);
 #pragma unroll
         for (int pt = 0; pt < PXT; pt++) acc[pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.v, bl[pt].v, acc[pt], 0, 0, 0);
 #pragma unroll
         for (int pt = 0; pt < PXT; pt++) acc[pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.v, bh[pt].v, acc[pt], 0, 0, 0);
-#endif
     };
     auto store_rows = [&](int n, int r0, int r1, const f32x16 (&acc)[PXT], const float4 (&sc4)[4], const float4 (&sh4)[4]) {
         const int cb = n * 32 + 4 * kg;
@@ -1889,12 +1820,8 @@ __global__ __launch_bounds__(256, 2) void k_fcn_expand(const float* __restrict__
 #pragma unroll
             for (int p = 0; p < PXT; p++) o[p] = __builtin_amdgcn_fmed3f(acc[p][r] * sc + sh, 0.f, 6.f);
             float* yo = yb + (size_t)ro * HW;
-#if IVF_EXPAND_ABL & 1
-            asm volatile("" :: "v"(o[0]), "v"(o[PXT - 1]), "v"(yo));
-#else
             if constexpr (PXT == 4) *(float4*)yo = make_float4(o[0], o[1], o[2], o[3]);
             else *(float2*)yo = make_float2(o[0], o[1]);
-#endif
         }
     };
     auto load_bn = [&](int n, float4 (&sc4)[4], float4 (&sh4)[4]) {
@@ -1950,45 +1877,21 @@ __global__ __launch_bounds__(256, 2) void k_fcn_expand(const float* __restrict__
 //   * both LDS stages are double buffered, one barrier per chunk;
 //   * workgroups are renumbered so that the row pairs of one image run on the same XCD (shared L2 for halo rows).
 // dwP: per hidden channel 12 floats = 9 taps, BN scale, BN shift, pad.
-#ifdef IVF_DWPW_TIMING
-// diagnostic build only (make TIMING=1): per-phase cycle sums of wave 0 of every workgroup of k_fcn_dwpw<5,4,6,1>
-__device__ unsigned long long g_dwpwTim[8];
-#define DWPW_TIM(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-    tacc[i] += t_ - tlast; tlast = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define DWPW_TIM(i) do { } while (0)
-#endif
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 static __device__ __forceinline__ f32x2 pkfma(f32x2 a, float w, f32x2 c) { return __builtin_elementwise_fma(a, (f32x2){w, w}, c); }
-// timing-only ablations of k_fcn_dwpw, compile-time so that the product build carries none of it (make EXTRA=-DIVF_DWPW_ABL=<mask>,
-// tools/dwpw_ablate.sh): 1 window loads hit chunk 0 (no HBM), 4 no barriers, 8 no A-fragment loads in the loop, 16 no window loads
-// in the loop, 32 no MFMAs, 64 no stencil arithmetic, 128 no A-fragment stores to LDS, 256 no B reads from LDS / split, 512 no
-// depthwise stores to LDS.  Results are wrong by construction.
-#ifndef IVF_DWPW_ABL
-#define IVF_DWPW_ABL 0
-#endif
-#ifndef IVF_EXPAND_ABL
-#define IVF_EXPAND_ABL 0      // timing-only ablations of k_fcn_expand: 1 no stores, 2 no MFMAs, 4 no A-fragment loads after the first tile
-#endif
-constexpr int kAbl = IVF_DWPW_ABL;
-#ifndef IVF_DWPW_OCC
-#define IVF_DWPW_OCC 2
-#endif
-#ifndef IVF_DWPW_PACKED
-#define IVF_DWPW_PACKED 1     // 0: the stencil's in-thread taps as plain v_fma_f32 instead of v_pk_fma_f32 (tools/probe/issue_model.hip:
-                              // packed f32 VALU does not hide under MFMAs; in THIS kernel the stencil and the MFMAs of a workgroup are
-                              // separated by barriers anyway, measured 100.7 vs 101.1 us per image, so the packed form stays)
-#endif
+// Measured and rejected: the stencil's in-thread taps as plain v_fma_f32 instead of v_pk_fma_f32 (tools/probe/issue_model.hip: packed f32 VALU does not
+// hide under MFMAs; in THIS kernel the stencil and the MFMAs of a workgroup are separated by barriers anyway), 100.7 vs 101.1 us per image.
+constexpr int kDwpwOcc = 2;       // workgroups per CU the 4-wave instances with five or more output tiles are built for
 template <int S> struct DwSetT { float4 own[3][2 * S]; float par; float hl[3], hr[3]; };   // par: parameter (tid & 15) of this thread's channel;
                                                                      // hl / hr: halo pixels across the workgroup edge (256-wide maps only)
 
 template <int TILES, int DIL, int LW, int S_, int NW = 4>    // LW = log2 of the (square) OUTPUT map size: 6, 7 (one row per workgroup),
                                                  // 8 (half a row); S_ = stride of the depthwise layer (input map = S_ x larger);
                                                  // NW = waves = 32-pixel tiles per workgroup (8: four image rows, 64 x 64 maps only)
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TILES >= 5 ? IVF_DWPW_OCC : 3)) void k_fcn_dwpw(const float* __restrict__ X, const float* __restrict__ dwP,
+__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TILES >= 5 ? kDwpwOcc : 3)) void k_fcn_dwpw(const float* __restrict__ X, const float* __restrict__ dwP,
                                                     const uint4* __restrict__ Wq, const float* __restrict__ scale,
                                                     const float* __restrict__ shift, const float* __restrict__ res,
-                                                    float* __restrict__ Y, int K, int Cout, int nTiles, int abl)
+                                                    float* __restrict__ Y, int K, int Cout, int nTiles, int /* reserved, always 0 */)
 {
     constexpr int NT = 64 * NW, NPX = 32 * NW, TPC = NPX / 8;       // threads, pixels per workgroup; threads per channel of a chunk
     constexpr int kPitch = NPX + 4;                 // floats per hidden channel row in LDS: the pixels + bank skew
@@ -2036,9 +1939,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TILES >= 5 ? IVF_DWPW_OCC :
     const float* Xb = X + (size_t)b * K * HWi;
     const float* Wf = (const float*)Wq;
     const int nChunks = K / 16;                      // odd for the 144-channel block: see the tail after the loop
-#ifdef IVF_DWPW_TIMING
-    unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
-#endif
 
     // window and depthwise-parameter loads run two chunks ahead; each of the 16 threads of a channel fetches ONE of its
     // 12 parameters and the stencil broadcasts them with DPP row_share.  The A fragments (L2-resident, needed only at
@@ -2046,8 +1946,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TILES >= 5 ? IVF_DWPW_OCC :
     const int parIdx = kc * 12 + min(g & 15, 11);
     auto issue = [&](DwSet& S, int c) {
         c = min(c, nChunks - 1);                    // refills past the end are redundant re-loads (branch-free loop)
-        if (kAbl & 1) c = 0;
-        if ((kAbl & 16) && c >= 3) return;
         const float* P = Xb + (size_t)(16 * c + kc) * HWi;
         S.par = dwP[c * 192 + parIdx];
 #pragma unroll
@@ -2065,7 +1963,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TILES >= 5 ? IVF_DWPW_OCC :
     float2 wreg[NWREG];
     auto issue_w = [&](int c) {
         c = min(c, nChunks - 1);
-        if ((kAbl & 8) && c >= 2) return;
 #pragma unroll
         for (int j = 0; j < NWREG; j++)
             if (!WTAIL || j + 1 < NWREG || tid + NT * j < TILES * 256)
@@ -2075,11 +1972,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TILES >= 5 ? IVF_DWPW_OCC :
     auto shl1 = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x101, 0xF, 0xF, true)); };
     float o[8];
     auto stencil = [&](const DwSet& S) {
-        if (kAbl & 64) {
-            o[0] = S.own[1][0].x; o[1] = S.own[1][0].y; o[2] = S.own[1][0].z; o[3] = S.own[1][0].w;
-            o[4] = S.own[1][1].x; o[5] = S.own[1][1].y; o[6] = S.own[1][1].z; o[7] = S.own[0][0].x + S.par;
-            return;
-        }
         float wk[9];
         const int pi = __builtin_bit_cast(int, S.par);
 #define ROW_SHARE(k) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, pi, 0x150 + (k), 0xF, 0xF, true))
@@ -2117,7 +2009,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TILES >= 5 ? IVF_DWPW_OCC :
             const float w0 = masked ? wk[ky * 3] * rowM[ky] : wk[ky * 3], w1 = masked ? wk[ky * 3 + 1] * rowM[ky] : wk[ky * 3 + 1],
                         w2 = masked ? wk[ky * 3 + 2] * rowM[ky] : wk[ky * 3 + 2];
             const float w0L = w0 * mL, w2R = w2 * mR;
-            if constexpr (IVF_DWPW_PACKED && PAIR && (DIL == 2 || DIL == 4)) {
+            if constexpr (PAIR && (DIL == 2 || DIL == 4)) {
                 // packed-f32 FMAs (v_pk_fma_f32: two pixels per instruction, full rate) for every tap that stays inside the
                 // thread's 8 pixels; the halo taps stay DPP FMAs.  Per pixel the order centre, left, right is that of the scalar path.
                 const float4 a = ky == 2 ? part[0] : S.own[ky][0], c4 = ky == 2 ? part[1] : S.own[ky][1];
@@ -2179,7 +2071,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TILES >= 5 ? IVF_DWPW_OCC :
                 o[7] = __builtin_fmaf(S.hr[ky], w2, o[7]);
             }
         }
-        if constexpr (IVF_DWPW_PACKED && PAIR && (DIL == 2 || DIL == 4)) {
+        if constexpr (PAIR && (DIL == 2 || DIL == 4)) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const f32x2 v = pkfma(O[i], dsc, (f32x2){dsh, dsh});
@@ -2192,11 +2084,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TILES >= 5 ? IVF_DWPW_OCC :
     };
     auto publish = [&](int buf) {
         float* dst = &sD[buf][kc * kPitch + 8 * g];
-        if (!(kAbl & 512)) {
-            *(float4*)dst = make_float4(o[0], o[1], o[2], o[3]);
-            *(float4*)(dst + 4) = make_float4(o[4], o[5], o[6], o[7]);
-        } else asm volatile("" :: "v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "v"(o[4]), "v"(o[5]), "v"(o[6]), "v"(o[7]));
-        if (kAbl & 128) { asm volatile("" :: "v"(wreg[0].x), "v"(wreg[NWREG - 1].y)); return; }
+        *(float4*)dst = make_float4(o[0], o[1], o[2], o[3]);
+        *(float4*)(dst + 4) = make_float4(o[4], o[5], o[6], o[7]);
 #pragma unroll
         for (int j = 0; j < NWREG; j++)
             if (!WTAIL || j + 1 < NWREG || tid + NT * j < TILES * 256) *(float2*)&sW[buf][(tid + NT * j) * 2] = wreg[j];
@@ -2211,20 +2100,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TILES >= 5 ? IVF_DWPW_OCC :
         // B operand: this lane's pixel, hidden channels 8*kg .. 8*kg+7 of the chunk, split into f16 hi / lo
         HFrag bh, bl;
         const float* dB = &sD[cur][8 * kg * kPitch + 32 * wave + col];
-        if (kAbl & 256) {
 #pragma unroll
-            for (int jj = 0; jj < 4; jj++) { bh.u[jj] = 0x3c003c00u + cur + lane; bl.u[jj] = 0x1c001c00u + cur; }
-        } else {
-#pragma unroll
-            for (int jj = 0; jj < 4; jj++) split_pair(dB[2 * jj * kPitch], dB[(2 * jj + 1) * kPitch], bh.u[jj], bl.u[jj]);
-        }
-        DWPW_TIM(5);
+        for (int jj = 0; jj < 4; jj++) split_pair(dB[2 * jj * kPitch], dB[(2 * jj + 1) * kPitch], bh.u[jj], bl.u[jj]);
         const uint4* wA = (const uint4*)&sW[cur][0] + lane;
-        if (kAbl & 32) {
-            acc[0][0] += __builtin_bit_cast(float, bh.u[0] ^ bl.u[1]) + __builtin_bit_cast(float, bh.u[2] ^ bl.u[3]);
-            acc[0][1] += __builtin_bit_cast(float, bh.u[1] ^ bl.u[0]) + __builtin_bit_cast(float, bh.u[3] ^ bl.u[2]);
-            return;
-        }
 #pragma unroll
         for (int t = 0; t < TILES; t += 2) {        // two tiles at a time: consecutive MFMAs hit different accumulators
             HFrag ah[2], al[2];
@@ -2252,46 +2130,27 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TILES >= 5 ? IVF_DWPW_OCC :
     issue_w(1);                                     // weights before the window: in-order return lets the next
     issue(SA, 2);                                   // stencil wait for them with the window loads still in flight
     __syncthreads();
-#ifdef IVF_DWPW_TIMING
-    tlast = __builtin_amdgcn_s_memtime();
-#endif
     for (int c = 0; c + 1 < nChunks; c += 2) {
         // buffer 0 holds chunk c; set B = window of chunk c+1, set A = window of chunk c+2 (both in flight)
         multiply(0);
-        DWPW_TIM(0);
         stencil(SB);
-        DWPW_TIM(1);
         publish(1);
-        DWPW_TIM(4);
         __builtin_amdgcn_sched_barrier(0);          // pin the issue order: A fragments, then the far-ahead window
         issue_w(c + 2);
         __builtin_amdgcn_sched_barrier(0);
         issue(SB, c + 3);
         __builtin_amdgcn_sched_barrier(0);
-        DWPW_TIM(2);
-        if (!(kAbl & 4)) __syncthreads();
-        DWPW_TIM(3);
+        __syncthreads();
         multiply(1);
-        DWPW_TIM(0);
         stencil(SA);
-        DWPW_TIM(1);
         publish(0);
-        DWPW_TIM(4);
         __builtin_amdgcn_sched_barrier(0);          // pin the issue order: A fragments, then the far-ahead window
         issue_w(c + 3);
         __builtin_amdgcn_sched_barrier(0);
         issue(SA, c + 4);
         __builtin_amdgcn_sched_barrier(0);
-        DWPW_TIM(2);
-        if (!(kAbl & 4)) __syncthreads();
-        DWPW_TIM(3);
+        __syncthreads();
     }
-#ifdef IVF_DWPW_TIMING
-    if (TILES == 5 && DIL == 4 && tid == 0) {
-        for (int i = 0; i < 6; i++) atomicAdd(&g_dwpwTim[i], tacc[i]);
-        atomicAdd(&g_dwpwTim[7], 1ull);
-    }
-#endif
     if (nChunks & 1) multiply(0);                   // odd chunk count (the 144-channel block): the last chunk sits in buffer 0.
                                                     // A peeled tail, not an exit inside the loop: that costs the loop its
                                                     // counted vmcnt waits (measured on the 64-wide kernels: 226 -> 357 us)
@@ -2530,18 +2389,9 @@ __global__ __launch_bounds__(512, 2) void k_fcn_dwpw8(const float* __restrict__ 
 //     (sched_group_barrier); the phase's first LDS reads are requested before the stencil phase by waves 4-7.
 // Measured and removed: weights through registers, pieces spread over the MFMA steps, a three-deep fragment
 // ring, four 64-pixel waves, the chunked schedule.  Ablation switches of the first version: commit 0a06b2f.
+// The compile-time ablation masks, phase timers and A/B knobs of this translation unit as a whole: last in commit 6c47b43.
 // Output / residual: the sub-image's pixels are 4 apart in x, so stores are 4-byte pieces of rows that the three sibling workgroups
 // (same image, same y phase, same XCD) complete in L2.
-#if defined(IVF_F4_TIMING) || defined(IVF_D2_TIMING)
-__device__ unsigned long long g_f4Tim[16];      // diagnostic build (make EXTRA=-DIVF_F4_TIMING): cycle sums per phase, waves 0 and 4
-__device__ unsigned long long g_f4Whole[8];     // wave 0: prologue (input gather ... first barrier), interval loop, epilogue; workgroups
-#endif
-#ifdef IVF_F4_TIMING
-#define F4_TIM(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-                       tacc[i] += t_ - tlast; tlast = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define F4_TIM(i) do { } while (0)
-#endif
 // Activation layout between the whole-block kernels of the 64 x 64 stage (r04): TILE-MAJOR.  Every workgroup of these kernels owns
 // a tile of 256 pixels of one image (16 tiles per image) for ALL channels.  In planes (NCHW) those 256 pixels are scattered over
 // each channel plane (dilation 4: every fourth pixel of every fourth row), so a lane's dword touches a 64-byte line of which the
@@ -2574,51 +2424,17 @@ __device__ __forceinline__ void lay_pixel(int lay, int tile, int off, int& y, in
     else { y = 4 * (off >> 4) + (tile >> 2); x = 4 * (off & 15) + (tile & 3); }
 }
 
-// issue priority of the two halves of a whole-block workgroup (waves w and w + 4 share a SIMD; its vector issue is arbitrated by priority, then age):
-//   0 none   1 / 2 static: waves 4-7 / waves 0-3 at priority 1   3 / 4 per phase: priority 1 during the MFMA phase / during the stencil phase
-#ifndef IVF_PRIO
-#define IVF_PRIO 0
-#endif
-#define IVF_PRIO_STATIC() do { if (IVF_PRIO == 1 && wave >= 4) __builtin_amdgcn_s_setprio(1); if (IVF_PRIO == 2 && wave < 4) __builtin_amdgcn_s_setprio(1); } while (0)
-#define IVF_PRIO_MFMA(on) do { if (IVF_PRIO == 3) __builtin_amdgcn_s_setprio(on); } while (0)
-#define IVF_PRIO_STEN(on) do { if (IVF_PRIO == 4) __builtin_amdgcn_s_setprio(on); } while (0)
+// Measured and rejected (profiles/r05_stem_irb_latency.txt): a raised issue priority (s_setprio) for one half of a whole-block workgroup (waves w and w + 4
+// share a SIMD), static or per MFMA / stencil phase -- nothing beyond +-1 % except block 17 (worse with every setting).
 constexpr int kF4Cin = 160, kF4Hid = 960, kF4Groups = 60;
 constexpr int kF4HP = 20;                         // floats per 16-pixel sub-row of a hidden plane in LDS (80 B rows)
-// LDS-DMA addressing per kernel: 1 = wave-uniform base in an SGPR pair + one 32-bit lane offset, 0 = a 64-bit pointer per lane.  Measured (us per 128 images, alternated): k_fcn_irbd4<true>
-// 961 / 966 -> 946 / 946 (its 24 B of scratch go); k_fcn_irbd4h 1,790 / 1,796 -> 1,813 / 1,827; k_fcn_irbd2 +-0.5 %.
-#ifndef IVF_F4_DMA_SADDR
-#define IVF_F4_DMA_SADDR 1
-#endif
-#ifndef IVF_H4_DMA_SADDR
-#define IVF_H4_DMA_SADDR 0
-#endif
-#ifndef IVF_W4_DMA_SADDR
-#define IVF_W4_DMA_SADDR 0
-#endif
-#ifndef IVF_D2_DMA_SADDR
-#define IVF_D2_DMA_SADDR 0
-#endif
-#ifndef IVF_F4_WALK
-#define IVF_F4_WALK 0         // blocks 15 / 16 as a persistent grid (see k_fcn_irbd2): 953 -> 1,138 us, the tile loop makes the 256-register body spill; off
-#endif
-#ifndef IVF_RES_FROM_FRAGS
-#define IVF_RES_FROM_FRAGS 1
-#endif
-#ifndef IVF_D2_WALK_ALL
-#define IVF_D2_WALK_ALL 0
-#endif
-#ifndef IVF_D2_RES_FROM_FRAGS
-#define IVF_D2_RES_FROM_FRAGS IVF_RES_FROM_FRAGS       // the same for k_fcn_irbd2's residual instances (blocks 6, 7, 9-11, 13, 14)
-#endif
-#ifndef IVF_F4_CS
-#define IVF_F4_CS 324         // floats per channel plane of sH: 16 rows x kF4HP + 4, so that the four 16-lane groups of E's b32 stores hit different banks
-#endif
-constexpr int kF4CS = IVF_F4_CS;
+// floats per channel plane of sH: 16 rows x kF4HP + 4, so that the four 16-lane groups of E's b32 stores hit different banks
+constexpr int kF4CS = 324;
 constexpr int kF4DP = 260;                        // floats per channel of the depthwise output in LDS
 constexpr int kF4ParB = 1024;                     // bytes per parameter slot (16 channels x 12 floats = 768 used)
-#ifndef IVF_F4_DMA_A
-#define IVF_F4_DMA_A 5        // weight pieces per wave of the half that reaches the barrier first (waves 0-3); waves 4-7 share the rest.
-#endif                        // Measured 2 / 3 / 4 / 5 / 6: 100.5 / 99.9 / 99.1 / 97.4 / 98.0 us per image
+// weight pieces per wave of the half that reaches the barrier first (waves 0-3); waves 4-7 share the rest.
+// Measured 2 / 3 / 4 / 5 / 6: 100.5 / 99.9 / 99.1 / 97.4 / 98.0 us per image
+constexpr int kF4DmaA = 5;
 constexpr int kF4WSlots = 3, kF4PSlots = 4;  // weight / parameter buffers: consumed in interval it, landed for it + 1, arriving for it + 2
 constexpr size_t kF4Lds = (size_t)2 * 16 * kF4CS * 4 + (size_t)2 * 16 * kF4DP * 4 + 2 * kF4WSlots * 10240 + kF4PSlots * kF4ParB +
                           2 * 160 * 4;        // + the projection's BN scale / shift of this workgroup's 160 output channels
@@ -2636,9 +2452,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 //   (commit "WIP: FP6 correction products"): they need 11 more live registers than the 256 the two-waves-per-SIMD body has -- 916-986 us without spills,
 //   2.8 ms with -- and are not in the tree.  NOT the default: one percent of the forward does not pay for 2.4 x the reference error; the experiment build
 //   carries the kernels (IVF_FCN_FP6=1) and tests/test_gpu_fcn.py keeps them at the goldens' bar.
-#ifndef IVF_F4_FP6
-#define IVF_F4_FP6 0
-#endif
+#define IVF_F4_FP6 0              // default of the run-time selector IVF_FCN_FP6; 1 also builds the FP6 kernels into the product library
 #if IVF_F4_FP6 || defined(IVF_EXPERIMENT)
 #define IVF_F4_FP6_BUILT 1
 #else
@@ -2682,28 +2496,17 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
 {
     const int g0 = SPLIT ? (int)(blockIdx.z * kF4Groups / gridDim.z) : 0, g1 = SPLIT ? (int)((blockIdx.z + 1) * kF4Groups / gridDim.z) : kF4Groups;
     extern __shared__ __attribute__((aligned(16))) uint4 f4smem[];
-    // nT = tiles of the launch (16 per image); blocks 15 / 16 may run as a persistent grid that walks them (see k_fcn_irbd2)
-    constexpr bool kWalk = IVF_F4_WALK && RES && !SPLIT;
-    const int perX_ = nT >> 3, strideX_ = (int)gridDim.x >> 3;
-    int slot_ = (int)blockIdx.x >> 3;
-    do {
-#ifdef IVF_F4_TIMING
-    const unsigned long long tk0 = __builtin_amdgcn_s_memtime();
-#endif
+    // nT = tiles of the launch (16 per image), one per workgroup.  Measured and rejected: blocks 15 / 16 as a persistent grid that walks them (see
+    // k_fcn_irbd2), 953 -> 1,138 us -- the tile loop makes the 256-register body spill.
+    const int perX = nT >> 3, slot = (int)blockIdx.x >> 3;          // tiles per XCD, this workgroup's tile among them
     float* const sH = (float*)f4smem;                               // [2][16 ch][kF4CS >= 16 rows x kF4HP]
     float* const sD = sH + 2 * 16 * kF4CS;                          // [2][16 ch][kF4DP]
     uint4* const sWE = (uint4*)(sD + 2 * 16 * kF4DP);               // [slots][5 K steps][hi, lo][64 lanes]
     uint4* const sWP = sWE + kF4WSlots * 640;                       // [slots][5 tiles][hi, lo][64 lanes]
     float* const sPar = (float*)(sWP + kF4WSlots * 640);            // [slots][16 ch][12]: 9 taps (x dw BN scale), dw BN shift, expansion BN scale, shift
     float* const sBN = sPar + kF4PSlots * (kF4ParB / 4);            // [scale 160 | shift 160] of the projection (epilogue)
-#if IVF_F4_WALK
-    int tid_ = threadIdx.x;
-    asm volatile("" : "+v"(tid_));      // opaque per tile: otherwise every lane-dependent constant of the body is hoisted out of the tile walk and kept live across it (spills)
-    const int tid = tid_, lane = tid & 63, wave = tid >> 6;
-#else
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#endif
-    const int nwg = nT, L = (int)(blockIdx.x & 7) * perX_ + slot_;                    // consecutive L on one XCD (nT = 16 * images)
+    const int nwg = nT, L = (int)(blockIdx.x & 7) * perX + slot;                      // consecutive L on one XCD (nT = 16 * images)
     const int b = L >> 4, py = (L >> 2) & 3, px = L & 3;
     const int tile0 = blockIdx.y * 5;
     constexpr int HW = 4096;
@@ -2716,32 +2519,25 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
     const unsigned ldsBase = (unsigned)(uintptr_t)f4smem;
     const unsigned ldsWE = ldsBase + (unsigned)((uint8_t*)sWE - (uint8_t*)f4smem), ldsWP = ldsBase + (unsigned)((uint8_t*)sWP - (uint8_t*)f4smem),
                    ldsPar = ldsBase + (unsigned)((uint8_t*)sPar - (uint8_t*)f4smem);
-#if IVF_F4_DMA_SADDR      // r05: wave-uniform base in an SGPR pair + ONE 32-bit lane offset (16 lane): the per-lane 64-bit pointers of WE / WP / par (6 registers, kept live across the
-                       // whole kernel) and their 64-bit vector adds per piece are gone
+    // r05: wave-uniform base in an SGPR pair + ONE 32-bit lane offset (16 lane): the per-lane 64-bit pointers of WE / WP / par (6 registers, kept live
+    // across the whole kernel) and their 64-bit vector adds per piece are gone.  Measured (us per 128 images, alternated): k_fcn_irbd4<true> 961 / 966 ->
+    // 946 / 946 (its 24 B of scratch go).  Measured and rejected in the other three kernels, which keep a 64-bit pointer per lane: k_fcn_irbd4h
+    // 1,790 / 1,796 -> 1,813 / 1,827; k_fcn_irbd2 +-0.5 %.
     const unsigned voff16 = (unsigned)lane * 16u;
     auto dma16 = [voff16](const void* sbase, unsigned ldsAddr) {
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff16), "s"(sbase), "s"(ldsAddr) : "memory");
     };
-#undef IVF_DMA_LANE
-#define IVF_DMA_LANE(x) 0
-#else
-    auto dma16 = [](const void* src, unsigned ldsAddr) {
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(ldsAddr) : "memory");
-    };
-#undef IVF_DMA_LANE
-#define IVF_DMA_LANE(x) (x)
-#endif
     const int uwave = __builtin_amdgcn_readfirstlane(wave);
     auto piece = [&](int it, int c) {           // piece c of what interval `it` consumes: WE[it] (c < 10), WP[it - 2] (c < 20), par[it] (c = 20)
         const int nb = it % kF4WSlots;
         if (c < 10) {
-            if (it < g1) dma16(WE + ((size_t)it * 10 + c) * 64 + IVF_DMA_LANE(lane), ldsWE + (unsigned)(nb * 640 + c * 64) * 16u);
+            if (it < g1) dma16(WE + ((size_t)it * 10 + c) * 64, ldsWE + (unsigned)(nb * 640 + c * 64) * 16u);
         } else if (c < 20) {
             const int c2 = c - 10, gp = it - 2;
             if (gp >= g0 && gp < g1)
-                dma16(WP + (((size_t)gp * tilesP + tile0) * 2 + c2) * 64 + IVF_DMA_LANE(lane), ldsWP + (unsigned)(nb * 640 + c2 * 64) * 16u);
+                dma16(WP + (((size_t)gp * tilesP + tile0) * 2 + c2) * 64, ldsWP + (unsigned)(nb * 640 + c2 * 64) * 16u);
         } else if (c == 20) {
-            if (it < g1 && lane < 48) dma16(par + (size_t)it * 192 + IVF_DMA_LANE(lane * 4), ldsPar + (unsigned)((it % kF4PSlots) * kF4ParB));
+            if (it < g1 && lane < 48) dma16(par + (size_t)it * 192, ldsPar + (unsigned)((it % kF4PSlots) * kF4ParB));
         }
     };
     auto dma = [&](int it) {                    // all 21 pieces (<= 1 KB each), piece c by wave c % 8
@@ -2749,7 +2545,7 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
         for (int r = 0; r < 3; r++) piece(it, uwave + 8 * r);
     };
     auto dma_late = [&](int it) {               // the same pieces, most of them by waves 0-3, which reach the barrier first
-        constexpr int NA = IVF_F4_DMA_A, NB = 4 * NA >= 21 ? 0 : (21 - 4 * NA + 3) / 4;
+        constexpr int NA = kF4DmaA, NB = 4 * NA >= 21 ? 0 : (21 - 4 * NA + 3) / 4;
         if (uwave < 4) {
 #pragma unroll
             for (int r = 0; r < NA; r++) { const int c = uwave + 4 * r; if (c < 21) piece(it, c); }
@@ -2829,10 +2625,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-#ifdef IVF_F4_TIMING
-    unsigned long long tacc[7] = {0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
-    const unsigned long long tk1 = tlast;
-#endif
     // ---- MFMA phase, branch-free form.  Intervals 0, 1 run P on zeroed operands (sD and the first two sWP slots are cleared in the
     // prologue), intervals 60, 61 run E into planes nobody reads: no `it`-dependent control flow inside the phase.
     struct MPre { float dv[8]; float2 eb[4]; HFrag ea0[2], pa0[2]; };
@@ -2856,7 +2648,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
         HFrag ea[2][2], pa[2][2], ph, pl;
         ea[0][0] = m.ea0[0]; ea[0][1] = m.ea0[1]; pa[0][0] = m.pa0[0]; pa[0][1] = m.pa0[1];
         f32x4 e0 = {0.f, 0.f, 0.f, 0.f}, e1 = {0.f, 0.f, 0.f, 0.f};
-        F4_TIM(4);
 #pragma unroll
         for (int s5 = 0; s5 < 5; s5++) {        // E(it): hidden group `it` = W_E[16 x 160] . X[160 x 32 pixels of this wave]
             if (s5 + 1 < 5) { ea[(s5 + 1) & 1][0].q = wE[(2 * s5 + 2) * 64]; ea[(s5 + 1) & 1][1].q = wE[(2 * s5 + 3) * 64]; }
@@ -2874,7 +2665,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
             for (int i = 0; i < 6; i++) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 1, 0); }
             __builtin_amdgcn_sched_barrier(0);
         }
-        F4_TIM(5);
         // C layout of E: column = lane & 15 (sub-column), row = 4 (lane >> 4) + r (hidden channel of the group)
         float* hp = sH + cur * (16 * kF4CS) + (4 * (lane >> 4)) * kF4CS + (2 * wave) * kF4HP + (lane & 15);
 #pragma unroll
@@ -2895,7 +2685,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-        F4_TIM(6);
     };
     // FP6 form of the MFMA phase: E = 10 x 16x16x32 f16 (hi * hi; P's B splits behind them) + 6 x 16x16x128 bf6 x fp6 (both corrections); P as in r05.
     auto mfma_main6 = [&](int it, MPre& m) {
@@ -2909,7 +2698,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
 #pragma unroll
         for (int c = 0; c < 3; c++) { q6[c] = wE[(5 + c) * 64]; r6[c] = wE2[c * 64]; }
         f32x4 e0 = {0.f, 0.f, 0.f, 0.f}, e1 = {0.f, 0.f, 0.f, 0.f};
-        F4_TIM(4);
 #pragma unroll
         for (int s5 = 0; s5 < 5; s5++) {
             if (s5 + 1 < 5) ea[(s5 + 1) & 1].q = wE[(s5 + 1) * 64];
@@ -2928,7 +2716,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
         ecorr(0, std::integral_constant<int, 0>{});
         ecorr(1, std::integral_constant<int, 1>{});
         ecorr(2, std::integral_constant<int, 2>{});
-        F4_TIM(5);
         float* hp = sH + cur * (16 * kF4CS) + (4 * (lane >> 4)) * kF4CS + (2 * wave) * kF4HP + (lane & 15);
         auto eepi = [&](int r) {                // E's epilogue, one row: BN + ReLU6 -> planes
             hp[r * kF4CS] = __builtin_amdgcn_fmed3f(__builtin_fmaf(e0[r], m.eb[r].x, m.eb[r].y), 0.f, 6.f);
@@ -2952,7 +2739,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        F4_TIM(6);
     };
     auto stencil_phase = [&](int it) {          // S(it - 1): 3x3 on the 16 x 16 planes of group it - 1, + BN + ReLU6
         const int g = it - 1;
@@ -2987,42 +2773,30 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
                                          __builtin_amdgcn_fmed3f(o[6], 0.f, 6.f), __builtin_amdgcn_fmed3f(o[7], 0.f, 6.f));
     };
 
-    IVF_PRIO_STATIC();
     for (int it = g0; it < g1 + 2; it++) {
-        F4_TIM(0);
         {
             MPre m;
             mfma_pre(it, m); __builtin_amdgcn_sched_barrier(0);
             auto mm = [&]() { if constexpr (FP6) mfma_main6(it, m); else mfma_main(it, m); };
-            if (wave < 4) { IVF_PRIO_MFMA(1); mm(); IVF_PRIO_MFMA(0); F4_TIM(1); IVF_PRIO_STEN(1); stencil_phase(it); IVF_PRIO_STEN(0); F4_TIM(2); }
-            else { IVF_PRIO_STEN(1); stencil_phase(it); IVF_PRIO_STEN(0); F4_TIM(2); __builtin_amdgcn_sched_barrier(0); IVF_PRIO_MFMA(1); mm(); IVF_PRIO_MFMA(0); F4_TIM(1); }
+            if (wave < 4) { mm(); stencil_phase(it); }
+            else { stencil_phase(it); __builtin_amdgcn_sched_barrier(0); mm(); }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the pieces of it + 1, requested an interval ago
-        dma_late(it + 2); F4_TIM(0);                             // land during it + 1; their slots were last read in it - 1
+        dma_late(it + 2);                             // land during it + 1; their slots were last read in it - 1
         __syncthreads();
-        F4_TIM(3);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef IVF_F4_TIMING
-    const unsigned long long tk2 = __builtin_amdgcn_s_memtime();
-#ifndef IVF_F4_TIM_H4ONLY        // (a variant build that times k_fcn_irbd4h alone)
-    if (lane == 0 && (wave == 0 || wave == 4)) {
-        for (int i = 0; i < 7; i++) atomicAdd(&g_f4Tim[(wave ? 8 : 0) + i], tacc[i]);
-        atomicAdd(&g_f4Tim[(wave ? 8 : 0) + 7], 1ull);
-    }
-#endif
-#endif
 
     // ---- epilogue: BN (+ residual) of the projection, 4-byte pieces (the sub-image's pixels are 4 apart)
     const int n = lane & 31;
     const int oy = 4 * (2 * wave + (n >> 4)) + py, ox = 4 * (n & 15) + px;      // this lane's pixel
     // the residual values of all five tiles are requested at once (the input fragments are dead: 80 registers), BN parameters from LDS.
     // Lane's channels of tile t: cb + (q & 3) + 8 (q >> 2), cb = 32 (tile0 + t) + 4 (lane >> 5)
-    // r05 (IVF_RES_FROM_FRAGS): the residual IS the block's input, which this wave still holds as split-f16 B fragments of the same 32 pixels
+    // r05: the residual IS the block's input, which this wave still holds as split-f16 B fragments of the same 32 pixels
     // (hi + lo = the 22-bit value the expansion multiplied; the residual add then differs from the exact f32 by <= 2^-22 relative).  Re-reading
     // it from memory cost the epilogue a round trip with every CU of the chip asking at once (phase timers: 34k of a workgroup's ~230k cycles).
     // The fragments are transposed to the accumulator layout tile by tile through a wave-private 4.6 KB piece of the (now idle) hidden planes.
-    constexpr bool kResFrags = RES && !SPLIT && IVF_RES_FROM_FRAGS && !FP6;      // FP6: the exact lo halves are gone after the prologue
+    constexpr bool kResFrags = RES && !SPLIT && !FP6;      // FP6: the exact lo halves are gone after the prologue
     float* const sxw = (float*)f4smem + wave * (32 * 36);
     float rvAll[5][16];
     if (RES && !SPLIT && !kResFrags) {
@@ -3035,11 +2809,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
             for (int q = 0; q < 16; q++) rvAll[t][q] = rp[(size_t)(t * 32 + (q & 3) + 8 * (q >> 2)) * rcs];
         __builtin_amdgcn_sched_barrier(0);
     }
-#ifdef IVF_F4_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long tkA = __builtin_amdgcn_s_memtime();
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     size_t ob; int ocs;
     lay_addr(layOut, Cout, b, oy, ox, ob, ocs);
     float* const yp = (SPLIT ? part + (size_t)blockIdx.z * (nwg / 16) * Cout * HW : Y) + ob + (size_t)(tile0 * 32 + 4 * (lane >> 5)) * ocs;
@@ -3086,17 +2855,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4(const float* __restrict__ 
         }
     }
     if (!SPLIT) range_flag(amaxOut);            // SPLIT: k_fcn_split_reduce checks the finished sums
-#ifdef IVF_F4_TIMING
-    __builtin_amdgcn_sched_barrier(0);
-    const unsigned long long tkB = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (tid == 0) {
-        const unsigned long long tk3 = __builtin_amdgcn_s_memtime();
-        atomicAdd(&g_f4Whole[0], tk1 - tk0); atomicAdd(&g_f4Whole[1], tk2 - tk1); atomicAdd(&g_f4Whole[2], tk3 - tk2); atomicAdd(&g_f4Whole[3], 1ull);
-        atomicAdd(&g_f4Whole[4], tkA - tk2); atomicAdd(&g_f4Whole[5], tkB - tkA); atomicAdd(&g_f4Whole[6], tk3 - tkB);
-    }
-#endif
-    } while (kWalk && (slot_ += strideX_) < perX_);      // tiles of this workgroup
 }
 
 // ---- k_fcn_irbd4h (r05): block 17 (160 -> 960 -> 320, no residual) in ONE pass over the hidden groups ----
@@ -3125,24 +2883,6 @@ constexpr int kH4CS = kH4Rows * kF4HP + 4;        // floats per channel plane of
 constexpr int kH4DP = 128 + 4;                    // floats per channel of the depthwise output
 constexpr int kH4Cout = 320, kH4TilesP = 10;
 constexpr size_t kH4Lds = (size_t)2 * 16 * kH4CS * 4 + (size_t)2 * 16 * kH4DP * 4 + kF4WSlots * 10240 + kF4PSlots * kF4ParB + 2 * kH4Cout * 4 + 10240;
-#ifndef IVF_H4_ABL
-#define IVF_H4_ABL 0          // timing-only ablations (compile time; results wrong): 1 no projection-fragment loads in the loop, 2 E's A fragments read once,
-#endif                        // 4 no LDS-DMA in the loop, 8 no stencil, 16 no halo expansion, 32 no P MFMAs, 64 no E MFMAs
-#ifndef IVF_H4_DMA_SKIP0
-#define IVF_H4_DMA_SKIP0 1    // the wave that also expands the halo row (wave 0) issues no LDS-DMA pieces: 1,846 / 1,861 vs 1,874 / 1,911 us per 128 images
-                              // (a wave's pieces consecutive, one M0 + one address per wave and the instruction's immediate offset for the rest -- the offset
-                              // moves the LDS address too -- is no faster: 1,823 / 1,842 vs 1,812 / 1,829: the cost of a piece is not its scalar set-up)
-#endif
-#ifndef IVF_H4_HALO_WAVE
-#define IVF_H4_HALO_WAVE 0
-#endif
-#ifndef IVF_H4_WALK
-#define IVF_H4_WALK 0         // block 17 as a persistent grid: 1,785 -> 1,888 us (the tile loop around a 242-register body spills 104 B per lane); off
-#endif
-#ifndef IVF_H4_DMA_A
-#define IVF_H4_DMA_A 3        // expansion-weight pieces per wave of the half that reaches the barrier first (waves 0-3); waves 4-7 share the rest of the 11.
-                              // Measured 1 / 2 / 3: 1,905 / 1,881 / 1,849 us per 128 images
-#endif
 template <bool FP6 = false>      // FP6 (r06): the expansion's correction products on bf6 x fp6, see k_fcn_irbd4; WE then points to the FP6 form (make_fused4: dWE6)
 __global__ __launch_bounds__(512, 2) void k_fcn_irbd4h(const float* __restrict__ X, const uint4* __restrict__ WE, const float* __restrict__ par,
                                                       const uint4* __restrict__ WP, const float* __restrict__ scP, const float* __restrict__ shP,
@@ -3150,67 +2890,41 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4h(const float* __restrict__
 {
     constexpr int g1 = kF4Groups;
     extern __shared__ __attribute__((aligned(16))) uint4 f4smem[];
-    // nT = tiles of the launch (32 per image); the grid may be one workgroup per CU that walks them (see k_fcn_irbd2)
-    const int perX_ = nT >> 3, strideX_ = (int)gridDim.x >> 3;
-    int slot_ = (int)blockIdx.x >> 3;
-    do {
+    // nT = tiles of the launch (32 per image), one per workgroup.  Measured and rejected: block 17 as a persistent grid that walks them (see k_fcn_irbd2),
+    // 1,785 -> 1,888 us -- the tile loop around a 242-register body spills 104 B per lane.
+    const int perX = nT >> 3, slot = (int)blockIdx.x >> 3;          // tiles per XCD, this workgroup's tile among them
     float* const sH = (float*)f4smem;                               // [2][16 ch][kH4CS]
     float* const sD = sH + 2 * 16 * kH4CS;                          // [2][16 ch][kH4DP]
     uint4* const sWE = (uint4*)(sD + 2 * 16 * kH4DP);               // [slots][5 K steps][hi, lo][64 lanes]
     float* const sPar = (float*)(sWE + kF4WSlots * 640);            // [slots][16 ch][12]
     float* const sBN = sPar + kF4PSlots * (kF4ParB / 4);            // [scale 320 | shift 320] of the projection (epilogue)
     uint4* const sXH = (uint4*)(sBN + 2 * kH4Cout);                 // [5 K steps][hi, lo][64 lanes]: input fragments of the halo sub-row
-#if IVF_H4_WALK
-    int tid_ = threadIdx.x;
-    asm volatile("" : "+v"(tid_));      // opaque per tile: otherwise every lane-dependent constant of the body is hoisted out of the tile walk and kept live across it (spills)
-    const int tid = tid_, lane = tid & 63, wave = tid >> 6;
-#else
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#endif
-    const int L = (int)(blockIdx.x & 7) * perX_ + slot_;                              // consecutive L on one XCD (nT = 32 * images)
+    const int L = (int)(blockIdx.x & 7) * perX + slot;                                // consecutive L on one XCD (nT = 32 * images)
     const int b = L >> 5, py = (L >> 3) & 3, px = (L >> 1) & 3, half = L & 1;
     const int r0 = 8 * half;                                        // first own sub-row
     const int haloRow = half ? 7 : 8, haloSlot = half ? 0 : 9;      // row slot s holds sub-row r0 - 1 + s
 
     const unsigned ldsBase = (unsigned)(uintptr_t)f4smem;
     const unsigned ldsWE = ldsBase + (unsigned)((uint8_t*)sWE - (uint8_t*)f4smem), ldsPar = ldsBase + (unsigned)((uint8_t*)sPar - (uint8_t*)f4smem);
-#if IVF_H4_DMA_SADDR      // r05: wave-uniform base in an SGPR pair + ONE 32-bit lane offset (16 lane): the per-lane 64-bit pointers of WE / WP / par (6 registers, kept live across the
-                       // whole kernel) and their 64-bit vector adds per piece are gone
-    const unsigned voff16 = (unsigned)lane * 16u;
-    auto dma16 = [voff16](const void* sbase, unsigned ldsAddr) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff16), "s"(sbase), "s"(ldsAddr) : "memory");
-    };
-#undef IVF_DMA_LANE
-#define IVF_DMA_LANE(x) 0
-#else
     auto dma16 = [](const void* src, unsigned ldsAddr) {
         asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(ldsAddr) : "memory");
     };
-#undef IVF_DMA_LANE
-#define IVF_DMA_LANE(x) (x)
-#endif
     const int uwave = __builtin_amdgcn_readfirstlane(wave);
     auto piece = [&](int it, int c) {           // piece c of what interval `it` consumes: WE[it] (c < 10), par[it] (c = 10)
         if (it >= g1) return;
-        if (c < 10) dma16(WE + ((size_t)it * 10 + c) * 64 + IVF_DMA_LANE(lane), ldsWE + (unsigned)((it % kF4WSlots) * 640 + c * 64) * 16u);
-        else if (c == 10 && lane < 48) dma16(par + (size_t)it * 192 + IVF_DMA_LANE(lane * 4), ldsPar + (unsigned)((it % kF4PSlots) * kF4ParB));
+        if (c < 10) dma16(WE + ((size_t)it * 10 + c) * 64 + lane, ldsWE + (unsigned)((it % kF4WSlots) * 640 + c * 64) * 16u);
+        else if (c == 10 && lane < 48) dma16(par + (size_t)it * 192 + lane * 4, ldsPar + (unsigned)((it % kF4PSlots) * kF4ParB));
     };
     auto dma = [&](int it) { piece(it, uwave); if (uwave < 3) piece(it, uwave + 8); };
-    auto dma_late = [&](int it) {               // the same 11 pieces, most of them by waves 0-3, which reach the barrier first
-#if IVF_H4_DMA_SKIP0            // wave 0 also expands the halo row: the pieces go to waves 1-3 (4 + 4 + 3)
+    // the same 11 pieces by waves 1-3 (4 + 4 + 3), which reach the barrier first; wave 0 also expands the halo row and issues none: 1,846 / 1,861 vs
+    // 1,874 / 1,911 us per 128 images with waves 0-3 at 3 pieces each and waves 4-7 sharing the rest (1 / 2 / 3 pieces each: 1,905 / 1,881 / 1,849).
+    // Measured and rejected: a wave's pieces consecutive, one M0 + one address per wave and the instruction's immediate offset for the rest (the offset
+    // moves the LDS address too) -- 1,823 / 1,842 vs 1,812 / 1,829: the cost of a piece is not its scalar set-up.
+    auto dma_late = [&](int it) {
         if (uwave >= 1 && uwave < 4) {
 #pragma unroll
             for (int r = 0; r < 4; r++) { const int c = __builtin_amdgcn_readfirstlane((uwave - 1) + 3 * r); if (c < 11) piece(it, c); }
-        }
-        return;
-#endif
-        constexpr int NA = IVF_H4_DMA_A, NB = 4 * NA >= 11 ? 0 : (11 - 4 * NA + 3) / 4;
-        if (uwave < 4) {
-#pragma unroll
-            for (int r = 0; r < NA; r++) { const int c = uwave + 4 * r; if (c < 11) piece(it, c); }
-        } else {
-#pragma unroll
-            for (int r = 0; r < NB; r++) { const int c = 4 * NA + (uwave - 4) + 4 * r; if (c < 11) piece(it, c); }
         }
     };
     dma(0);
@@ -3298,9 +3012,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4h(const float* __restrict__
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-#ifdef IVF_F4_TIMING
-    unsigned long long tacc[7] = {0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
-#endif
     struct MPre { float dv[8]; float2 eb[4]; HFrag ea0[2]; };
     auto mfma_pre = [&](int it, MPre& m) {      // every LDS read of the phase that depends on no MFMA
         const int cur = it & 1, ws = it % kF4WSlots;
@@ -3320,9 +3031,8 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4h(const float* __restrict__
         ea[0][0] = m.ea0[0]; ea[0][1] = m.ea0[1];
         uint4 q6[2]; uint2 r6[2];                   // FP6: the correction operands of the current / next step
         f32x4 e0 = {0.f, 0.f, 0.f, 0.f}, e1 = {0.f, 0.f, 0.f, 0.f};
-        const bool haloWave = uwave == IVF_H4_HALO_WAVE;
+        const bool haloWave = uwave == 0;
         const int gp = it - 2;
-        F4_TIM(4);
 #pragma unroll
         for (int jj = 0; jj < 4; jj++) split_pair(m.dv[2 * jj], m.dv[2 * jj + 1], ph.u[jj], pl.u[jj]);      // P's B fragment
         // E(it) and P(it - 2) step by step: K step s5 of the expansion, then output tile s5 of the projection -- the expansion's A
@@ -3360,17 +3070,13 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4h(const float* __restrict__
                     }
                 }
             } else {
-            if (s5 + 1 < 5) {
-                if (IVF_H4_ABL & 2) { ea[(s5 + 1) & 1][0] = ea[s5 & 1][0]; ea[(s5 + 1) & 1][1] = ea[s5 & 1][1]; }
-                else { ea[(s5 + 1) & 1][0].q = wE[(2 * s5 + 2) * 64]; ea[(s5 + 1) & 1][1].q = wE[(2 * s5 + 3) * 64]; }
-            }
-            if (!(IVF_H4_ABL & 64))
+            if (s5 + 1 < 5) { ea[(s5 + 1) & 1][0].q = wE[(2 * s5 + 2) * 64]; ea[(s5 + 1) & 1][1].q = wE[(2 * s5 + 3) * 64]; }
             {   // E(it): hidden group `it` = W_E[16 x 160] . X[160 x 16 pixels of this wave's sub-row]
                 const HFrag &ah = ea[s5 & 1][0], &al = ea[s5 & 1][1];
                 e0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al.v, bh[s5].v, e0, 0, 0, 0);
                 e0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah.v, bl[s5].v, e0, 0, 0, 0);
                 e0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah.v, bh[s5].v, e0, 0, 0, 0);
-                if (haloWave && !(IVF_H4_ABL & 16)) {                     // wave-uniform: the sub-row just outside the half, fragments from LDS
+                if (haloWave) {                     // wave-uniform: the sub-row just outside the half, fragments from LDS
                     HFrag xh_, xl_;                 // (requested a K step ahead like the A fragments: 1,881-1,887 vs 1,841-1,868 us, not kept)
                     xh_.q = sXH[(2 * s5) * 64 + lane]; xl_.q = sXH[(2 * s5 + 1) * 64 + lane];
                     e1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al.v, xh_.v, e1, 0, 0, 0);
@@ -3382,17 +3088,14 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4h(const float* __restrict__
             {   // P(it - 2), tile s5: out[32 channels x 32 pixels] += W_P[32 x 16] . D[16 x 32 pixels]
                 const int t = s5;
                 const HFrag &ah = pw[t][0], &al = pw[t][1];
-                if (!(IVF_H4_ABL & 32)) {
                 pacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al.v, ph.v, pacc[t], 0, 0, 0);
                 pacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.v, pl.v, pacc[t], 0, 0, 0);
                 pacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.v, ph.v, pacc[t], 0, 0, 0);
-                }
                 __builtin_amdgcn_sched_barrier(0);
-                if (!(IVF_H4_ABL & 1)) wp_load(gp + 1, t);                 // the same tile of the next group, behind the MFMAs that read this one
+                wp_load(gp + 1, t);                 // the same tile of the next group, behind the MFMAs that read this one
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        F4_TIM(5);
         // E's epilogue: BN + ReLU6 -> planes.  C layout of E: column = lane & 15 (sub-column), row = 4 (lane >> 4) + r (hidden channel of the group)
         float* hp = sH + cur * (16 * kH4CS) + (4 * (lane >> 4)) * kH4CS + (lane & 15);
 #pragma unroll
@@ -3400,11 +3103,10 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4h(const float* __restrict__
             hp[r * kH4CS + (wave + 1) * kF4HP] = __builtin_amdgcn_fmed3f(__builtin_fmaf(e0[r], m.eb[r].x, m.eb[r].y), 0.f, 6.f);
             if (haloWave) hp[r * kH4CS + haloSlot * kF4HP] = __builtin_amdgcn_fmed3f(__builtin_fmaf(e1[r], m.eb[r].x, m.eb[r].y), 0.f, 6.f);
         }
-        F4_TIM(6);
     };
     auto stencil_phase = [&](int it) {          // S(it - 1): 3x3 on the 8 own rows of group it - 1, + BN + ReLU6
         const int g = it - 1;
-        if (g < 0 || g >= g1 || (IVF_H4_ABL & 8)) return;
+        if (g < 0 || g >= g1) return;
         const float* hp = sH + (g & 1) * (16 * kH4CS);
         const float4* pq = (const float4*)(sPar + (g % kF4PSlots) * (kF4ParB / 4) + sch * 12);
         const float4 w03 = pq[0], w47 = pq[1], w8s = pq[2];          // taps 0-3 | 4-7 | tap 8, shift, (expansion BN)
@@ -3433,31 +3135,19 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4h(const float* __restrict__
                                    __builtin_amdgcn_fmed3f(o[2], 0.f, 6.f), __builtin_amdgcn_fmed3f(o[3], 0.f, 6.f));
     };
 
-    IVF_PRIO_STATIC();
     for (int it = 0; it < g1 + 2; it++) {
-        F4_TIM(0);
         {
             MPre m;
             mfma_pre(it, m); __builtin_amdgcn_sched_barrier(0);
-            if (wave < 4) { IVF_PRIO_MFMA(1); mfma_main(it, m); IVF_PRIO_MFMA(0); F4_TIM(1); IVF_PRIO_STEN(1); stencil_phase(it); IVF_PRIO_STEN(0); F4_TIM(2); }
-            else { IVF_PRIO_STEN(1); stencil_phase(it); IVF_PRIO_STEN(0); F4_TIM(2); __builtin_amdgcn_sched_barrier(0); IVF_PRIO_MFMA(1); mfma_main(it, m); IVF_PRIO_MFMA(0); F4_TIM(1); }
+            if (wave < 4) { mfma_main(it, m); stencil_phase(it); }
+            else { stencil_phase(it); __builtin_amdgcn_sched_barrier(0); mfma_main(it, m); }
         }
         // everything older than this interval's ten projection-fragment loads has landed: the DMA pieces of it + 1, requested an interval ago
-        if (IVF_H4_ABL & 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); else
         asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        F4_TIM(3);
-        if (!(IVF_H4_ABL & 4)) dma_late(it + 2);
-        F4_TIM(0);                               // land during it + 1; their slots were last read in it - 1
+        dma_late(it + 2);                        // land during it + 1; their slots were last read in it - 1
         __syncthreads();
-        F4_TIM(3);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if defined(IVF_F4_TIMING) && !defined(IVF_F4_TIM_D4ONLY)
-    if (lane == 0 && (wave == 0 || wave == 4)) {
-        for (int i = 0; i < 7; i++) atomicAdd(&g_f4Tim[(wave ? 8 : 0) + i], tacc[i]);
-        atomicAdd(&g_f4Tim[(wave ? 8 : 0) + 7], 1ull);
-    }
-#endif
 
     // ---- epilogue: BN of the projection; the sub-image's pixels are 4 apart in planes (layOut 0: the decoder reads planes)
     const int n = lane & 31;
@@ -3480,7 +3170,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd4h(const float* __restrict__
         }
     }
     range_flag(amaxOut);
-    } while (IVF_H4_WALK && (slot_ += strideX_) < perX_);      // tiles of this workgroup
 }
 
 #ifdef IVF_EXPERIMENT      // opt-in variant (IVF_FCN_ROLES=1) with a run-time ablation mask: experiment builds only
@@ -3625,21 +3314,9 @@ __global__ __launch_bounds__(1024) void k_fcn_irbd4w(const float* __restrict__ X
     const unsigned ldsBase = (unsigned)(uintptr_t)f4smem;
     const unsigned ldsWE = ldsBase + (unsigned)((uint8_t*)sWE - (uint8_t*)f4smem), ldsWP = ldsBase + (unsigned)((uint8_t*)sWP - (uint8_t*)f4smem),
                    ldsPar = ldsBase + (unsigned)((uint8_t*)sPar - (uint8_t*)f4smem);
-#if IVF_W4_DMA_SADDR      // r05: wave-uniform base in an SGPR pair + ONE 32-bit lane offset (16 lane): the per-lane 64-bit pointers of WE / WP / par (6 registers, kept live across the
-                       // whole kernel) and their 64-bit vector adds per piece are gone
-    const unsigned voff16 = (unsigned)lane * 16u;
-    auto dma16 = [voff16](const void* sbase, unsigned ldsAddr) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff16), "s"(sbase), "s"(ldsAddr) : "memory");
-    };
-#undef IVF_DMA_LANE
-#define IVF_DMA_LANE(x) 0
-#else
     auto dma16 = [](const void* src, unsigned ldsAddr) {
         asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(ldsAddr) : "memory");
     };
-#undef IVF_DMA_LANE
-#define IVF_DMA_LANE(x) (x)
-#endif
     // Every piece is ALWAYS issued (a group index outside [g0, g1) is clamped: its slot is one nobody reads in that interval), so a wave's
     // count of outstanding requests is known: the three pieces of a wave are spread over its interval (before the stencil, before P, at
     // the end) and the wait in front of the barrier lets exactly the two youngest stay in flight.
@@ -3647,13 +3324,13 @@ __global__ __launch_bounds__(1024) void k_fcn_irbd4w(const float* __restrict__ X
         const int nb = it % kF4WSlots;
         if (c < 10) {
             const int ge = min(it, g1 - 1);
-            dma16(WE + ((size_t)ge * 10 + c) * 64 + IVF_DMA_LANE(lane), ldsWE + (unsigned)(nb * 640 + c * 64) * 16u);
+            dma16(WE + ((size_t)ge * 10 + c) * 64 + lane, ldsWE + (unsigned)(nb * 640 + c * 64) * 16u);
         } else if (c < 20) {
             const int c2 = c - 10, gp = min(max(it - 2, g0), g1 - 1);
-            dma16(WP + (((size_t)gp * tilesP + tile0) * 2 + c2) * 64 + IVF_DMA_LANE(lane), ldsWP + (unsigned)(nb * 640 + c2 * 64) * 16u);
+            dma16(WP + (((size_t)gp * tilesP + tile0) * 2 + c2) * 64 + lane, ldsWP + (unsigned)(nb * 640 + c2 * 64) * 16u);
         } else if (c == 20) {
             const int ge = min(it, g1 - 1);
-            if (lane < 48) dma16(par + (size_t)ge * 192 + IVF_DMA_LANE(lane * 4), ldsPar + (unsigned)((it % kF4PSlots) * kF4ParB));
+            if (lane < 48) dma16(par + (size_t)ge * 192 + lane * 4, ldsPar + (unsigned)((it % kF4PSlots) * kF4ParB));
         }
     };
     auto dma = [&](int it) {                    // all 21 pieces (<= 1 KB each), piece c by P wave c % 8
@@ -3801,16 +3478,13 @@ __global__ __launch_bounds__(256) void k_fcn_split_reduce(const float* __restric
 // DIL 1 (blocks 5-7, ONE 64 x 64 "sub-image"): strip = 4 rows x 64 columns, wave w = half a row (row w >> 1, columns 32 (w & 1) ..),
 // the two halo rows are eight 16-pixel blocks, one per wave.  PITCH = floats per plane row (+ 4 pad), CS = floats per channel plane
 // (+ 4 / + 4: the four 16-lane groups of E's stores, 4 channels apart, start 16 banks apart).
-#ifndef IVF_D2_HALO_LOW
-#define IVF_D2_HALO_LOW 1     // r05: 542 / 330 / 622 / 348 -> 524 / 315 / 609 / 338 us per 128 images (<96,96> / <64,64> / <96,160> / <64,96>)
-#endif
 template <int CIN, int COUT, int DIL = 2>
 struct D2Cfg {
     static constexpr int ROWS = DIL == 2 ? 8 : 4, COLS = DIL == 2 ? 32 : 64, PITCH = COLS + 4, CS = (ROWS + 2) * PITCH + 4;
     static constexpr int KS = CIN / 32, TILES = COUT / 32, HID = 6 * CIN, NG = HID / 16;
     static constexpr int NPE = 2 * KS, NPP = 2 * TILES, NP = NPE + NPP + 1;              // 1 KB pieces per interval (+ parameters)
     static constexpr int WSLOT = (NPE + NPP) * 64;                                        // uint4 per weight slot
-    static constexpr bool WALK = IVF_D2_WALK_ALL || !(CIN == 96 && COUT == 160);                          // may run as a persistent grid (k_fcn_irbd2)
+    static constexpr bool WALK = !(CIN == 96 && COUT == 160);      // may run as a persistent grid (k_fcn_irbd2)
     static constexpr size_t LDS = (size_t)2 * 16 * CS * 4 + (size_t)2 * 16 * kF4DP * 4 + (size_t)3 * WSLOT * 16 + 4 * kF4ParB + 2 * COUT * 4;
 };
 
@@ -3835,15 +3509,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd2(const float* __restrict__ 
     const int perX_ = nT >> 3, strideX_ = (int)gridDim.x >> 3;
     int slot_ = (int)blockIdx.x >> 3;
     do {
-#ifdef IVF_D2_TIMING      // diagnostic build: -DIVF_D2_TIMING=<CIN * 1000 + COUT> times that instance like IVF_F4_TIMING times k_fcn_irbd4
-    constexpr bool kTimed = CIN * 1000 + COUT == IVF_D2_TIMING && !SPLIT;
-    const unsigned long long tk0 = __builtin_amdgcn_s_memtime();
-    unsigned long long tacc[7] = {0, 0, 0, 0, 0, 0, 0}, tlast = tk0, tk1 = 0;
-#define D2_TIM(i) do { if (kTimed) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-    tacc[i] += t_ - tlast; tlast = t_; __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-#define D2_TIM(i) do { } while (0)
-#endif
     float* const sH = (float*)d2smem;                               // [2][16 ch][kD2CS]
     float* const sD = sH + 2 * 16 * kD2CS;                          // [2][16 ch][kF4DP]
     uint4* const sW = (uint4*)(sD + 2 * 16 * kF4DP);                // [3 slots][E: KS x (hi, lo) | P: TILES x (hi, lo)][64 lanes]
@@ -3857,31 +3522,19 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd2(const float* __restrict__ 
     constexpr int HW = 4096;
     const unsigned ldsBase = (unsigned)(uintptr_t)d2smem;
     const unsigned ldsW = ldsBase + (unsigned)((uint8_t*)sW - (uint8_t*)d2smem), ldsPar = ldsBase + (unsigned)((uint8_t*)sPar - (uint8_t*)d2smem);
-#if IVF_D2_DMA_SADDR      // r05: wave-uniform base in an SGPR pair + ONE 32-bit lane offset (16 lane): the per-lane 64-bit pointers of WE / WP / par (6 registers, kept live across the
-                       // whole kernel) and their 64-bit vector adds per piece are gone
-    const unsigned voff16 = (unsigned)lane * 16u;
-    auto dma16 = [voff16](const void* sbase, unsigned ldsAddr) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff16), "s"(sbase), "s"(ldsAddr) : "memory");
-    };
-#undef IVF_DMA_LANE
-#define IVF_DMA_LANE(x) 0
-#else
     auto dma16 = [](const void* src, unsigned ldsAddr) {
         asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(ldsAddr) : "memory");
     };
-#undef IVF_DMA_LANE
-#define IVF_DMA_LANE(x) (x)
-#endif
     const int uwave = __builtin_amdgcn_readfirstlane(wave);
     auto piece = [&](int it, int c) {           // piece c of what interval `it` consumes: WE[it] (c < NPE), WP[it - 2] (c < NPE + NPP), par[it]
         const int nb = it % 3;
         if (c < NPE) {
-            if (it < g1) dma16(WE + ((size_t)it * NPE + c) * 64 + IVF_DMA_LANE(lane), ldsW + (unsigned)(nb * WSLOT + c * 64) * 16u);
+            if (it < g1) dma16(WE + ((size_t)it * NPE + c) * 64 + lane, ldsW + (unsigned)(nb * WSLOT + c * 64) * 16u);
         } else if (c < NPE + NPP) {
             const int gp = it - 2;
-            if (gp >= g0 && gp < g1) dma16(WP + ((size_t)gp * NPP + (c - NPE)) * 64 + IVF_DMA_LANE(lane), ldsW + (unsigned)(nb * WSLOT + c * 64) * 16u);
+            if (gp >= g0 && gp < g1) dma16(WP + ((size_t)gp * NPP + (c - NPE)) * 64 + lane, ldsW + (unsigned)(nb * WSLOT + c * 64) * 16u);
         } else if (c == NPE + NPP) {
-            if (it < g1 && lane < 48) dma16(par + (size_t)it * 192 + IVF_DMA_LANE(lane * 4), ldsPar + (unsigned)((it & 3) * kF4ParB));
+            if (it < g1 && lane < 48) dma16(par + (size_t)it * 192 + lane * 4, ldsPar + (unsigned)((it & 3) * kF4ParB));
         }
     };
     auto dma_all = [&](int it) {
@@ -3906,9 +3559,10 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd2(const float* __restrict__ 
     const int r0 = DIL == 2 ? 8 * strip + wave : 4 * strip + (wave >> 1);        // (sub-)image row of blocks 0, 1
     const int c0 = DIL == 2 ? 0 : 32 * (wave & 1);                                // their first column
     // r05: which half of the workgroup expands the four halo blocks (DIL 2).  Phase timers: with waves 4-7 (stencil first, MFMA phase last -- the half that
-    // reaches the barrier last) waves 0-3 idled 960 of an interval's 3,040 cycles at the barrier (k_fcn_irbd2<64,64>); with waves 0-3 the halves arrive together
-    const bool hasHalo = DIL == 1 || (IVF_D2_HALO_LOW ? wave < 4 : wave >= 4);
-    const bool above = DIL == 2 ? (IVF_D2_HALO_LOW ? wave < 2 : wave < 6) : wave < 4;
+    // reaches the barrier last) waves 0-3 idled 960 of an interval's 3,040 cycles at the barrier (k_fcn_irbd2<64,64>); with waves 0-3 the halves arrive together.
+    // Measured and rejected: waves 4-7, 524 / 315 / 609 / 338 -> 542 / 330 / 622 / 348 us per 128 images (<96,96> / <64,64> / <96,160> / <64,96>)
+    const bool hasHalo = DIL == 1 || wave < 4;
+    const bool above = DIL == 2 ? wave < 2 : wave < 4;
     const int rH = above ? ROWS * strip - 1 : ROWS * strip + ROWS, cH = DIL == 2 ? 16 * (wave & 1) : 16 * (wave & 3);   // halo block
     constexpr int SUB = 64 / DIL;                                                 // rows / columns of a sub-image
     const bool haloIn = hasHalo && rH >= 0 && rH < SUB;
@@ -4003,7 +3657,7 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd2(const float* __restrict__ 
         }
         // C layout of E: column = lane & 15, row = 4 (lane >> 4) + r (hidden channel of the group)
         float* hpl = sH + cur * (16 * kD2CS) + (4 * (lane >> 4)) * kD2CS + (lane & 15);
-        if (DIL == 1 || (IVF_D2_HALO_LOW ? uwave < 4 : uwave >= 4)) {           // E(it), block 2: this wave's 16 pixels of a halo row (its fragments are read once more)
+        if (DIL == 1 || uwave < 4) {           // E(it), block 2: this wave's 16 pixels of a halo row (its fragments are read once more)
             f32x4 e2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < KS; s++) {
@@ -4072,41 +3726,26 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd2(const float* __restrict__ 
                                          __builtin_amdgcn_fmed3f(o[6], 0.f, 6.f), __builtin_amdgcn_fmed3f(o[7], 0.f, 6.f));
     };
 
-#ifdef IVF_D2_TIMING
-    tk1 = tlast = __builtin_amdgcn_s_memtime();
-#endif
-    IVF_PRIO_STATIC();
     for (int it = g0; it < g1 + 2; it++) {
-        D2_TIM(0);
         {
             MPre m;
             mfma_pre(it, m); __builtin_amdgcn_sched_barrier(0);
-            if (wave < 4) { IVF_PRIO_MFMA(1); mfma_main(it, m); IVF_PRIO_MFMA(0); D2_TIM(1); IVF_PRIO_STEN(1); stencil_phase(it); IVF_PRIO_STEN(0); D2_TIM(2); }
-            else { IVF_PRIO_STEN(1); stencil_phase(it); IVF_PRIO_STEN(0); D2_TIM(2); __builtin_amdgcn_sched_barrier(0); IVF_PRIO_MFMA(1); mfma_main(it, m); IVF_PRIO_MFMA(0); D2_TIM(1); }
+            if (wave < 4) { mfma_main(it, m); stencil_phase(it); }
+            else { stencil_phase(it); __builtin_amdgcn_sched_barrier(0); mfma_main(it, m); }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the pieces of it + 1, requested an interval ago
-        D2_TIM(3);
         dma_late(it + 2);                                        // land during it + 1; their slots were last read in it - 1
-        D2_TIM(0);
         __syncthreads();
-        D2_TIM(3);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef IVF_D2_TIMING
-    const unsigned long long tk2 = __builtin_amdgcn_s_memtime();
-    if (kTimed && lane == 0 && (wave == 0 || wave == 4)) {
-        for (int i = 0; i < 7; i++) atomicAdd(&g_f4Tim[(wave ? 8 : 0) + i], tacc[i]);
-        atomicAdd(&g_f4Tim[(wave ? 8 : 0) + 7], 1ull);
-    }
-#endif
 
     // ---- epilogue: BN (+ residual) of the projection; pixel n of the wave's row -> image (2 r0 + py, 2 n + px)
     const int n = lane & 31;
     const int oy = DIL * r0 + py, ox = DIL * (c0 + n) + px;         // this lane's pixel
     // the residual values of all tiles are requested at once (the input fragments are dead), BN parameters from LDS
-    // r05 (IVF_RES_FROM_FRAGS, see k_fcn_irbd4): the residual is this wave's own input fragments (blocks 0, 1 = its 32 pixels, CIN = COUT), transposed per tile
+    // r05 (see k_fcn_irbd4): the residual is this wave's own input fragments (blocks 0, 1 = its 32 pixels, CIN = COUT), transposed per tile
     // through a wave-private 4.6 KB piece of the hidden planes, which nobody touches after the loop's last barrier
-    constexpr bool kResFrags = RES && !SPLIT && IVF_D2_RES_FROM_FRAGS && CIN == COUT;
+    constexpr bool kResFrags = RES && !SPLIT && CIN == COUT;
     float* const sxw = (float*)d2smem + wave * (32 * 36);
     static_assert(!kResFrags || (size_t)2 * 16 * kD2CS * 4 >= (size_t)8 * 32 * 36 * 4, "the transposition scratch lives in the hidden planes");
     float rvAll[TILES][16];
@@ -4166,15 +3805,6 @@ __global__ __launch_bounds__(512, 2) void k_fcn_irbd2(const float* __restrict__ 
         }
     }
     if (!SPLIT) range_flag(amaxOut);            // SPLIT: k_fcn_split_reduce checks the finished sums
-#ifdef IVF_D2_TIMING
-    if (kTimed) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) {
-            const unsigned long long tk3 = __builtin_amdgcn_s_memtime();
-            atomicAdd(&g_f4Whole[0], tk1 - tk0); atomicAdd(&g_f4Whole[1], tk2 - tk1); atomicAdd(&g_f4Whole[2], tk3 - tk2); atomicAdd(&g_f4Whole[3], 1ull);
-        }
-    }
-#endif
     } while (kWalk && (slot_ += strideX_) < perX_);      // tiles of this workgroup
 }
 
@@ -4190,10 +3820,7 @@ __global__ void k_fcn_last(const float* __restrict__ X, const float* __restrict_
 }
 
 // ---- bilinear to out_size, logistic, u8 truncation (models_light.py:198-199, :25-26; stereo_kitti.cc:511) ----
-#ifndef IVF_OUT_ROWS
-#define IVF_OUT_ROWS 8
-#endif
-constexpr int kOutRows = IVF_OUT_ROWS;        // output rows per workgroup of k_fcn_out
+constexpr int kOutRows = 8;                   // output rows per workgroup of k_fcn_out
 __global__ __launch_bounds__(256) void k_fcn_out(const float* __restrict__ L, int lh, int lw, int oh, int ow, float sy_, float sx_,
                                                 float* __restrict__ costF, uint8_t* __restrict__ costU, int* __restrict__ status, int rowsPerWg,
                                                 size_t uImageStride, int uRowStride)       // the u8 map's strides (r06: it may be a pitched plane of the front end)
@@ -4349,7 +3976,7 @@ void launch_gemm(const Gemm& g, const float* X, const float* res, float* Y, int 
     if (g.taps == 9) {
         static const bool old9 = IVF_EXP_ENV("IVF_FCN_OLD3X3") != nullptr;
         static const bool split9 = IVF_EXP_ENV("IVF_FCN_3X3_SPLIT") != nullptr;      // the r01 kernel: one workgroup per output-channel tile
-        static const int dec6 = IVF_EXP_ENV("IVF_FCN_DEC6") ? atoi(IVF_EXP_ENV("IVF_FCN_DEC6")) : IVF_DEC_FP6;
+        static const int dec6 = IVF_EXP_ENV("IVF_FCN_DEC6") ? atoi(IVF_EXP_ENV("IVF_FCN_DEC6")) : kDecFp6Default;
         if (!old9 && !split9 && dec6 >= 2 && g.dWq6 && H == 64 && W == 64 && g.act == 2 && !res)
             hipLaunchKernelGGL(k_fcn_conv3x3_f6r, dim3(8 * B), dim3(256), 0, s, X, g.dWq6, g.dScale, g.dShift, Y, g.cin, g.cout,
                                (const float*)nullptr, 0.f, (float*)nullptr, (float*)nullptr);
@@ -4416,7 +4043,6 @@ static thread_local char g_lastDwpw[96] = "";
 bool launch_dwpw(const Dw& d, const Gemm& g, const float* X, const float* res, float* Y, int H, int W, int B, hipStream_t s)
 {
     static const bool off = IVF_EXP_ENV("IVF_FCN_NOFUSE") != nullptr;
-    const int abl = kAbl;                                                   // ablation builds keep the 4-wave kernels
     const int tiles = (g.cout + 31) / 32;
     if (off || H != W || (H != 64 && H != 128 && H != 256) || d.c % 16 || g.taps != 1 || g.nTiles != tiles || g.act != 0) return false;
     if (d.stride == 2) {                                                    // blocks 2 (256 -> 128) and 4 (128 -> 64)
@@ -4424,9 +4050,9 @@ bool launch_dwpw(const Dw& d, const Gemm& g, const float* X, const float* res, f
         if (!s2 || d.dil != 1 || tiles != 1 || (H != 256 && H != 128)) return false;
         const int Ho = H / 2, wg = Ho * Ho / 128;
         if (Ho == 128)
-            hipLaunchKernelGGL((k_fcn_dwpw<1, 1, 7, 2>), dim3(wg * B, 1), dim3(256), 0, s, X, d.dPack, g.dWq, g.dScale, g.dShift, res, Y, d.c, g.cout, g.nTiles, abl);
+            hipLaunchKernelGGL((k_fcn_dwpw<1, 1, 7, 2>), dim3(wg * B, 1), dim3(256), 0, s, X, d.dPack, g.dWq, g.dScale, g.dShift, res, Y, d.c, g.cout, g.nTiles, 0);
         else
-            hipLaunchKernelGGL((k_fcn_dwpw<1, 1, 6, 2>), dim3(wg * B, 1), dim3(256), 0, s, X, d.dPack, g.dWq, g.dScale, g.dShift, res, Y, d.c, g.cout, g.nTiles, abl);
+            hipLaunchKernelGGL((k_fcn_dwpw<1, 1, 6, 2>), dim3(wg * B, 1), dim3(256), 0, s, X, d.dPack, g.dWq, g.dScale, g.dShift, res, Y, d.c, g.cout, g.nTiles, 0);
         return true;
     }
     if (d.stride != 1) return false;
@@ -4443,16 +4069,16 @@ bool launch_dwpw(const Dw& d, const Gemm& g, const float* X, const float* res, f
     snprintf(g_lastDwpw, sizeof g_lastDwpw, "ivffcn::k_fcn_dwpw<" #T ", " #D "> %d->%d", d.c, g.cout);                      \
     if (LWV == 6 && (nwEnv == 8 || (nwEnv != 4 && T <= 2)))                                                                 \
         hipLaunchKernelGGL((k_fcn_dwpw<T, D, LWV, 1, (LWV == 6 ? 8 : 4)>), dim3(wgpi / 2 * B, GY), dim3(512), 0, s, X, d.dPack, g.dWq, g.dScale,    \
-                           g.dShift, res, Y, d.c, g.cout, g.nTiles, abl);                                                   \
+                           g.dShift, res, Y, d.c, g.cout, g.nTiles, 0);                                                   \
     else hipLaunchKernelGGL((k_fcn_dwpw<T, D, LWV, 1>), dim3(wgpi * B, GY), blk, 0, s, X, d.dPack, g.dWq, g.dScale, g.dShift, res, Y, d.c, \
-                       g.cout, g.nTiles, abl); } while (0)
+                       g.cout, g.nTiles, 0); } while (0)
 #define DWPW8(D, T) do { snprintf(g_lastDwpw, sizeof g_lastDwpw, "ivffcn::k_fcn_dwpw8<" #D ", " #T "> %d->%d", d.c, g.cout);             \
     hipLaunchKernelGGL((k_fcn_dwpw8<D, T>), dim3(wgpi * B), dim3(512), 0, s, X, d.dPack, g.dWq, g.dScale, g.dShift, res, Y, d.c, \
                        g.cout, g.nTiles); } while (0)
     // 8-wave kernel per shape (measured per 64 images, 4-wave vs 8-wave): 576->160 dil 2: 294 vs 258 (on by default);
     // 960->160 dil 4: 460 vs 472, 576->96: 213 vs 228, 384->64: 148 vs 167 (off).  IVF_FCN_DWPW8 = bit mask by tile count.
     static const int w8 = IVF_EXP_ENV("IVF_FCN_DWPW8") ? (int)strtol(IVF_EXP_ENV("IVF_FCN_DWPW8"), nullptr, 0) : -1;
-    if (H == 64 && !abl) {
+    if (H == 64) {
         auto on = [&](bool dflt) { return w8 < 0 ? dflt : (w8 >> tiles & 1) != 0; };
         if (tiles == 5 && d.dil == 2 && on(true)) { DWPW8(2, 5); return true; }
         if (tiles == 5 && d.dil == 4 && on(false)) { DWPW8(4, 5); return true; }
@@ -4469,7 +4095,7 @@ bool launch_dwpw(const Dw& d, const Gemm& g, const float* X, const float* res, f
     else if (tiles == 5 && d.dil == 4) DWPW(5, 4, 6, 1);
     else if (tiles == 10 && d.dil == 4) {
         static const bool one = IVF_EXP_ENV("IVF_FCN_NODWPW10") == nullptr;      // one pass over the hidden tensor with an 8-wave workgroup
-        if (one && !abl) DWPW8(4, 10); else DWPW(5, 4, 6, 2);
+        if (one) DWPW8(4, 10); else DWPW(5, 4, 6, 2);
     }
     else return false;
 #undef DWPW
@@ -4802,12 +4428,10 @@ int split_ways(int n, int groups, int cout)
     return std::max(ns, 1);
 }
 // Persistent form of a whole-block kernel (r05): one workgroup per CU that walks its XCD's tiles, when every workgroup gets at least two.
-#ifndef IVF_PERSIST
-#define IVF_PERSIST 1
-#endif
+constexpr int kPersistDefault = 1;      // default of the run-time selector IVF_FCN_PERSIST (experiment build)
 int persistent_grid(const ivf_fcn* f, int tiles)
 {
-    static const int mode = IVF_EXP_ENV("IVF_FCN_PERSIST") ? atoi(IVF_EXP_ENV("IVF_FCN_PERSIST")) : IVF_PERSIST;      // 0 = one tile per workgroup
+    static const int mode = IVF_EXP_ENV("IVF_FCN_PERSIST") ? atoi(IVF_EXP_ENV("IVF_FCN_PERSIST")) : kPersistDefault;      // 0 = one tile per workgroup
     const int g = f->numCU & ~7;                                                                                       // whole XCD slots
     return (mode && g >= 8 && tiles >= 2 * g && tiles % 8 == 0) ? g : tiles;
 }
@@ -4833,7 +4457,7 @@ int forward_device(ivf_fcn* f, const uint8_t* dBgr, size_t imageStride, int rowS
     // r05: the 512^2 / 256^2 / 128^2 stage (prep, stem, blocks 2-4) runs in CHUNKS of images, back to back per chunk: a chunk's tensors
     // (12.6 MB f32 input planes, 4.2 MB stem output, 1.6 MB block outputs per image) are written and read back while they are still in the
     // 256 MB Infinity Cache instead of after the whole batch (403 MB + 537 MB + ... at 128 images) has gone through HBM
-    static const int headChunkEnv = IVF_EXP_ENV("IVF_FCN_HEADCHUNK") ? atoi(IVF_EXP_ENV("IVF_FCN_HEADCHUNK")) : IVF_FCN_HEADCHUNK_DEFAULT;
+    static const int headChunkEnv = IVF_EXP_ENV("IVF_FCN_HEADCHUNK") ? atoi(IVF_EXP_ENV("IVF_FCN_HEADCHUNK")) : kHeadChunkDefault;
     int headChunk = headChunkEnv;
     if (headChunk <= 0 || headChunk >= n) headChunk = 0;
     if (!headChunk) {
@@ -4848,7 +4472,7 @@ int forward_device(ivf_fcn* f, const uint8_t* dBgr, size_t imageStride, int rowS
     // conv0 + block 1's depthwise layer in one kernel, unless an experiment switch asks for another kernel on block 1
     static const bool stem = IVF_EXP_ENV("IVF_FCN_NOSTEM") == nullptr && IVF_EXP_ENV("IVF_FCN_WIDE256") == nullptr && IVF_EXP_ENV("IVF_FCN_NOFUSE") == nullptr;
     // r05: the three tensors between the stem and block 4 row-interleaved ([y][channel][x]) when all four kernels are the whole-block ones
-    static const int headIlEnv = IVF_EXP_ENV("IVF_FCN_HEAD_IL") ? atoi(IVF_EXP_ENV("IVF_FCN_HEAD_IL")) : IVF_FCN_HEAD_IL_DEFAULT;
+    static const int headIlEnv = IVF_EXP_ENV("IVF_FCN_HEAD_IL") ? atoi(IVF_EXP_ENV("IVF_FCN_HEAD_IL")) : kHeadIlDefault;
     const int headIl = (headIlEnv && stem && (irbMask & 7u) == 7u) ? 1 : 0;
     const bool chunkedHead = headChunk > 0 && stem && (irbMask & 7u) == 7u;
     if (headChunk > 0 && !chunkedHead) {            // an experiment switch took a head kernel away: the plain schedule
@@ -4871,9 +4495,9 @@ int forward_device(ivf_fcn* f, const uint8_t* dBgr, size_t imageStride, int rowS
             hipLaunchKernelGGL((k_fcn_irb<S_, CIN_, HID_, COUT_, RES_, WI_, TH_>), dim3(WI_ / S_ / 32, WI_ / S_ / TH_, nb), dim3(512), 0, s, (const float*)(X_), \
                                (const uint4*)f->dIrbWE[T_], f->pw[IP_].dScale, f->pw[IP_].dShift, f->dw[ID_].dW, f->dw[ID_].dScale, f->dw[ID_].dShift, (const uint4*)f->dIrbWP[T_], \
                                f->pw[IP_ + 1].dScale, f->pw[IP_ + 1].dShift, (Y_), (const float4*)f->dIrbTab[T_], headIl, (T_ < 2 ? headIl : 0))
-            IRBC(2, 16, 96, 24, false, 256, IVF_IRB_TH2, 1, 1, o1, o2, 0);
-            IRBC(1, 24, 144, 24, true, 128, IVF_IRB_TH3, 3, 2, o2, o3, 1);
-            IRBC(2, 24, 144, 32, false, 128, IVF_IRB_TH4, 5, 3, o3, o4, 2);
+            IRBC(2, 16, 96, 24, false, 256, kIrbTH2, 1, 1, o1, o2, 0);
+            IRBC(1, 24, 144, 24, true, 128, kIrbTH3, 3, 2, o2, o3, 1);
+            IRBC(2, 24, 144, 32, false, 128, kIrbTH4, 5, 3, o3, o4, 2);
 #undef IRBC
         }
         STAGE("prep + stem + blocks 2-4, chunked");
@@ -4944,9 +4568,9 @@ int forward_device(ivf_fcn* f, const uint8_t* dBgr, size_t imageStride, int rowS
             hipLaunchKernelGGL((k_fcn_irb<S_, CIN_, HID_, COUT_, RES_, WI_, TH_>), dim3(WI_ / S_ / 32, WI_ / S_ / TH_, n), dim3(512), 0, s, x, \
                                (const uint4*)f->dIrbWE[i - 1], ex.dScale, ex.dShift, d.dW, d.dScale, d.dShift, (const uint4*)f->dIrbWP[i - 1], pj.dScale, pj.dShift, y, \
                                (const float4*)f->dIrbTab[i - 1], headIl, (i < 3 ? headIl : 0))
-            if (i == 1) IRB(2, 16, 96, 24, false, 256, IVF_IRB_TH2);
-            else if (i == 2) IRB(1, 24, 144, 24, true, 128, IVF_IRB_TH3);
-            else IRB(2, 24, 144, 32, false, 128, IVF_IRB_TH4);
+            if (i == 1) IRB(2, 16, 96, 24, false, 256, kIrbTH2);
+            else if (i == 2) IRB(1, 24, 144, 24, true, 128, kIrbTH3);
+            else IRB(2, 24, 144, 32, false, 128, kIrbTH4);
 #undef IRB
             ip += 2; id++;
             H = (H - 1) / d.stride + 1; W = (W - 1) / d.stride + 1;
@@ -5044,7 +4668,7 @@ int forward_device(ivf_fcn* f, const uint8_t* dBgr, size_t imageStride, int rowS
                     hipLaunchKernelGGL(k_fcn_irbd4h<true>, dim3(32 * n), dim3(512), kH4Lds, s, x, F.dWE6, F.dPar, F.dWP, pj.dScale, pj.dShift, y, layIn, layOut, 32 * n);
                 else
 #endif
-                hipLaunchKernelGGL(k_fcn_irbd4h<false>, dim3(IVF_H4_WALK ? persistent_grid(f, 32 * n) : 32 * n), dim3(512), kH4Lds, s, x, F.dWE, F.dPar, F.dWP, pj.dScale, pj.dShift, y,
+                hipLaunchKernelGGL(k_fcn_irbd4h<false>, dim3(32 * n), dim3(512), kH4Lds, s, x, F.dWE, F.dPar, F.dWP, pj.dScale, pj.dShift, y,
                                    layIn, layOut, 32 * n);
                 kname = "k_fcn_irbd4h";
             }
@@ -5057,7 +4681,7 @@ int forward_device(ivf_fcn* f, const uint8_t* dBgr, size_t imageStride, int rowS
                                    (float*)nullptr, layIn, layOut, 16 * n);
 #endif
             else if (bk.res)
-                hipLaunchKernelGGL((k_fcn_irbd4<true>), dim3(IVF_F4_WALK && grid.y == 1 ? persistent_grid(f, 16 * n) : 16 * n, grid.y, 1), dim3(512), kF4Lds, s, x, F.dWE, F.dPar, F.dWP, pj.dScale,
+                hipLaunchKernelGGL((k_fcn_irbd4<true>), dim3(16 * n, grid.y, 1), dim3(512), kF4Lds, s, x, F.dWE, F.dPar, F.dWP, pj.dScale,
                                    pj.dShift, x, y, F.cout, F.tilesP, (float*)nullptr, layIn, layOut, 16 * n);
             else
                 hipLaunchKernelGGL((k_fcn_irbd4<false>), grid, dim3(512), kF4Lds, s, x, F.dWE, F.dPar, F.dWP, pj.dScale, pj.dShift, (const float*)nullptr, y, F.cout, F.tilesP,
@@ -5144,7 +4768,7 @@ int forward_device(ivf_fcn* f, const uint8_t* dBgr, size_t imageStride, int rowS
             static const int splitMode = IVF_EXP_ENV("IVF_FCN_SPLIT") ? atoi(IVF_EXP_ENV("IVF_FCN_SPLIT")) : 1;
             int nd = 1;
             if (splitMode && g.cin == 320) { const int ways[] = {15, 10, 6, 5, 3, 2}; for (int w : ways) if (w * n <= 16) { nd = w; break; } }
-            static const int dec6 = IVF_EXP_ENV("IVF_FCN_DEC6") ? atoi(IVF_EXP_ENV("IVF_FCN_DEC6")) : IVF_DEC_FP6;      // 0: three f16 products (k_fcn_conv3x3_all, r02-r05)
+            static const int dec6 = IVF_EXP_ENV("IVF_FCN_DEC6") ? atoi(IVF_EXP_ENV("IVF_FCN_DEC6")) : kDecFp6Default;      // 0: three f16 products (k_fcn_conv3x3_all, r02-r05)
             const bool use6 = dec6 && g.dWq6 != nullptr;
             if (nd > 1) {
                 if (use6 && dec6 >= 2 && (30 / nd) % 3 == 0)      // ranges of whole K-step pairs
@@ -5349,51 +4973,6 @@ void ivf_fcn_destroy(ivf_fcn* f)
     if (!f) return;
     (void)hipSetDevice(f->device);
     (void)hipDeviceSynchronize();
-#if defined(IVF_F4_TIMING) || defined(IVF_D2_TIMING)
-    {
-        unsigned long long t[16] = {};
-        if (hipMemcpyFromSymbol(t, HIP_SYMBOL(ivffcn::g_f4Tim), sizeof t) == hipSuccess && t[7]) {
-            for (int w = 0; w < 2; w++) {
-                const double n = (double)t[8 * w + 7];
-                fprintf(stderr, "[irbd4 timing] wave %d: workgroups %.0f; cycles per workgroup: dma issue %.0f  mfma phase %.0f (first reads %.0f, E loop %.0f, split + P loop %.0f, epilogue %.0f)  stencil phase %.0f  wait + barrier %.0f\n",
-                        4 * w, n, t[8 * w] / n, (t[8 * w + 1] + t[8 * w + 4] + t[8 * w + 5] + t[8 * w + 6]) / n, t[8 * w + 4] / n, t[8 * w + 5] / n, t[8 * w + 6] / n, t[8 * w + 1] / n, t[8 * w + 2] / n, t[8 * w + 3] / n);
-            }
-            unsigned long long z[16] = {};
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(ivffcn::g_f4Tim), z, sizeof z);
-            unsigned long long wv[8] = {};
-            if (hipMemcpyFromSymbol(wv, HIP_SYMBOL(ivffcn::g_f4Whole), sizeof wv) == hipSuccess && wv[3])
-                fprintf(stderr, "[irbd4 whole] workgroups %llu; s_memtime ticks per workgroup (wave 0): prologue %.0f  interval loop %.0f  epilogue %.0f "
-                                "(residual loads issued -> landed %.0f, BN + stores issued %.0f, stores drained %.0f)\n",
-                        wv[3], (double)wv[0] / wv[3], (double)wv[1] / wv[3], (double)wv[2] / wv[3], (double)wv[4] / wv[3], (double)wv[5] / wv[3], (double)wv[6] / wv[3]);
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(ivffcn::g_f4Whole), z, sizeof wv);
-        }
-    }
-#endif
-#ifdef IVF_IRB_TIMING
-    {
-        unsigned long long t[10] = {};
-        if (hipMemcpyFromSymbol(t, HIP_SYMBOL(ivffcn::g_irbTim), sizeof t) == hipSuccess && t[8]) {
-            const double n = (double)t[8];
-            fprintf(stderr, "[irb timing WI=%d S=%d] workgroups %.0f; cycles per workgroup (wave 0): loads -> LDS %.0f  window fragments %.0f  B1 expansion %.0f  "
-                            "barrier-1 wait %.0f  B2 stencil %.0f  barrier-2 wait %.0f  B3 projection %.0f  epilogue %.0f\n", IVF_IRB_TIMING, IVF_IRB_TIMING_S, n,
-                    t[0] / n, t[1] / n, t[2] / n, t[3] / n, t[4] / n, t[5] / n, t[6] / n, t[7] / n);
-            unsigned long long z[10] = {};
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(ivffcn::g_irbTim), z, sizeof z);
-        }
-    }
-#endif
-#ifdef IVF_DWPW_TIMING
-    {
-        unsigned long long t[8] = {};
-        if (hipMemcpyFromSymbol(t, HIP_SYMBOL(ivffcn::g_dwpwTim), sizeof t) == hipSuccess && t[7]) {
-            const double n = (double)t[7];
-            fprintf(stderr, "[dwpw timing] workgroups %llu; cycles per workgroup: LDS read + split %.0f  MFMA %.0f  stencil %.0f  publish %.0f  issue %.0f  barrier %.0f\n",
-                    t[7], t[5] / n, t[0] / n, t[1] / n, t[4] / n, t[2] / n, t[3] / n);
-            unsigned long long z[8] = {};
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(ivffcn::g_dwpwTim), z, sizeof z);
-        }
-    }
-#endif
     for (int i = 0; i < ivf_fcn::kProbe; i++) {
         if (f->probe0[i]) (void)hipEventDestroy(f->probe0[i]);
         if (f->probe1[i]) (void)hipEventDestroy(f->probe1[i]);
