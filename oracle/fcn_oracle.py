@@ -79,15 +79,22 @@ def relu6(x):
     return np.clip(x, F(0), F(6))
 
 
-def forward(W, bgr_u8, out_size, enc_size=(512, 512), return_taps=False):
-    """W: {state_dict name: f32 array}.  Returns (cost_f32 HxW, cost_u8 HxW[, taps])."""
+def forward(W, bgr_u8, out_size, enc_size=(512, 512), return_taps=False, resume=None):
+    """W: {state_dict name: f32 array}.  Returns (cost_f32 HxW, cost_u8 HxW[, taps]).
+    resume = (i, x): start after block i from its recorded output x (taps["block<i>"], kept for i >= 14) instead of from the image --
+    tests/fcn_probe.py's networks share their encoder."""
     from iv_slam_amd.fcn_weights import BLOCKS          # architecture table (data)
     taps = {}
-    x = bilinear(preprocess(bgr_u8), *enc_size)
-    taps["resized"] = x
-    x = relu6(bn(conv2d(x, W["encoder.features.0.0.weight"], 2, 1), W, "encoder.features.0.1"))
-    taps["f0"] = x
+    if resume is None:
+        x = bilinear(preprocess(bgr_u8), *enc_size)
+        taps["resized"] = x
+        x = relu6(bn(conv2d(x, W["encoder.features.0.0.weight"], 2, 1), W, "encoder.features.0.1"))
+        taps["f0"] = x
+    else:
+        x = np.ascontiguousarray(resume[1], np.float32)
     for i, (inp, oup, t, s, d, res) in enumerate(BLOCKS, start=1):
+        if resume is not None and i <= resume[0]:
+            continue
         p = "encoder.features.%d.conv" % i
         y = x
         if t == 1:
@@ -101,6 +108,8 @@ def forward(W, bgr_u8, out_size, enc_size=(512, 512), return_taps=False):
         taps.setdefault("block_absmax", {})[i] = float(np.abs(x).max())     # the un-clamped activations (linear bottleneck + residual)
         if i in (7, 17):
             taps["f%d" % i] = x
+        if i >= 14:
+            taps["block%d" % i] = x
     y = np.maximum(bn(conv2d(x, W["decoder.cbr.0.weight"], 1, 1), W, "decoder.cbr.1"), F(0))
     y = conv2d(y, W["decoder.conv_last.weight"]) + W["decoder.conv_last.bias"][None, :, None, None]
     taps["logits"] = y.astype(np.float32)
