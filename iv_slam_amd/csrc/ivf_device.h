@@ -171,6 +171,17 @@ namespace ivf {
 // thread-local error message behind ivf_last_error() (ivf_api.hip)
 int set_error(int code, const char* fmt, ...);
 
+// host-side services of ivf_api.hip for the other translation units of the C-ABI: the calling thread's growable device / pinned
+// scratch (pooled: see ScratchSlot) and the device-id check
+int thread_scratch(int device, size_t need, uint8_t** out);
+int thread_pinned(size_t need, uint8_t** out);
+int have_device(int dev);
+
+// One image of a front-end batch, as ivf_frame_create_from_frontend (ivf_api.hip) resolves it, and the frame made of it (ivf_match.hip,
+// which alone knows struct ivf_frame): `count` keypoints of at most `cap` are valid once `done` has passed; uright == nullptr: no stereo
+struct BatchImage { const ivf_keypoint* kps; const uint8_t* desc; const float* uright; const int* count; int cap; hipEvent_t done; };
+int frame_from_batch(int device, const BatchImage& src, const ivf_bounds& bounds, ivf_frame** out);
+
 // launchers (ivf_kernels.hip)
 void launch_stereo_args(const Config& hc, const Config* dc, const StereoArgs& A, int nPairs, hipStream_t s);
 void launch_ingest(const Config& hc, const Config* dc, const Buffers& b, const uint8_t* src0, const uint8_t* src1,
@@ -201,3 +212,9 @@ void launch_bow_transform(const int* childStart, const int* child, const uint8_t
                           int* leaf, int* nodeAt, hipStream_t s);
 
 }  // namespace ivf
+
+// error returns of the host code (ivf_api.hip, ivf_match.hip, ivf_track.hip)
+#define fail ivf::set_error
+#define HIPCHK(expr)                                                                                   \
+    do { hipError_t e_ = (expr);                                                                        \
+         if (e_ != hipSuccess) return fail(IVF_E_NO_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)

@@ -39,10 +39,6 @@ using namespace ivf;
 
 namespace {
 
-#define fail ivf::set_error
-#define HIPCHK(expr)                                                                                   \
-    do { hipError_t e_ = (expr);                                                                        \
-         if (e_ != hipSuccess) return fail(IVF_E_NO_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
 #define DEVINL __device__ __forceinline__
 
 constexpr int kGC = 64, kGR = 48;                 // FRAME_GRID_COLS / ROWS (ORB/include/Frame.h:43-44)

@@ -362,6 +362,100 @@ def all_searches_scenario(iv, seed, w, h, nfeat, img_seed, strict):
     return True
 
 
+# The rotation filter shared by the six searches that take mbCheckOrientation, on hand-made histograms.  A case lists
+# (angle difference in degrees, matches with that difference, survives ComputeThreeMaxima); 30-degree steps fall into the
+# bins 0..11 by construction (rot * (1 / 30), rounded).
+_ROT_BINS = {
+    "20-10-3-1": [(60, 20, True), (150, 10, True), (240, 3, True), (330, 1, False)],     # only the fourth bin goes
+    "30-2-2": [(90, 30, True), (0, 2, False), (180, 2, False)],                          # 2 < 0.1 * 30: only the top bin stays
+    "20-10-1": [(30, 20, True), (120, 10, True), (210, 1, False)],                       # 1 < 0.1 * 20: the third goes
+    "tie-10-10-10-10": [(30, 10, True), (90, 10, True), (150, 10, True), (210, 10, False)],   # strict '>': the three lowest bins stay
+    "359.9-is-bin-12": [(0, 20, True), (30, 10, True), (60, 5, True), (359.9, 1, False)],      # bin 12, a fourth bin: not wrapped into bin 0
+}
+_ROT_CASES = [(name, True) for name in _ROT_BINS] + [("20-10-3-1", False)]              # orientation check off: nothing goes
+_ROT_ENTRIES = ["SearchByProjection", "SearchForInitialization", "SearchByBoW", "SearchByBoWKeyFrames", "SearchForTriangulation",
+                "SearchByProjectionReloc"]
+
+
+def rot_scene(name):
+    """Frame 1 on a 40 px lattice inside 320 x 240 (octave 0, random descriptors), frame 2 = frame 1 shuffled: every keypoint has
+    one partner at its own position with its own descriptor (distance 0, every other descriptor ~128 bits away), and the angle
+    differences of the case.  -> dict with the frames, the queries of the projection searches and what survives."""
+    bins = _ROT_BINS[name]
+    rng = np.random.default_rng(4242)
+    rot = np.concatenate([np.full(c, r, np.float32) for r, c, _ in bins])
+    keep = np.concatenate([np.full(c, s, bool) for _, c, s in bins])
+    n = len(rot)
+    assert n <= 48
+    order = rng.permutation(n)                                   # bins interleaved in keypoint order
+    rot, keep = rot[order], keep[order]
+    k1 = np.zeros(n, O.KP_DTYPE)
+    k1["x"] = 20 + 40 * (np.arange(n) % 8); k1["y"] = 20 + 40 * (np.arange(n) // 8); k1["size"] = 31; k1["response"] = 50
+    d1 = rng.integers(0, 256, (n, 32)).astype(np.uint8)
+    whole = rot == np.round(rot)
+    a2 = np.where(whole, 200, 0).astype(np.float32)              # 200: most differences come out negative first (rot < 0 -> + 360)
+    k1["angle"] = np.where(whole, (a2 + rot) % 360, rot).astype(np.float32)
+    perm = rng.permutation(n)
+    k2 = k1[perm].copy(); d2 = d1[perm].copy(); k2["angle"] = a2[perm]
+    q = dict(u=k1["x"].copy(), v=k1["y"].copy(), ur=np.zeros(n, np.float32), radius=np.full(n, 10, np.float32),
+             min_level=np.full(n, -1, np.int32), max_level=np.ones(n, np.int32), level=np.zeros(n, np.int32), angle=k1["angle"].copy(),
+             desc=d1, valid=np.ones(n, np.uint8), blocks=np.ones(n, np.uint8))
+    return dict(n=n, k1=k1, d1=d1, k2=k2, d2=d2, q=q, keep=keep, perm=perm, inv=np.argsort(perm), fv={5: list(range(n))},
+                bounds=(0.0, 0.0, 320.0, 240.0), prev=np.stack([k1["x"], k1["y"]], axis=1).astype(np.float32))
+
+
+def rot_expected(S, entry, ori):
+    """the hand-computed result: every match of a surviving bin, in the entry point's own indexing"""
+    keep = S["keep"] if ori else np.ones(S["n"], bool)
+    if entry in ("SearchByProjection", "SearchByProjectionReloc", "SearchByBoW"):       # per frame-2 keypoint: its frame-1 partner
+        return np.where(keep[S["perm"]], S["perm"], -1).astype(np.int32)
+    return np.where(keep, S["inv"], -1).astype(np.int32)                                # per frame-1 keypoint: its frame-2 partner
+
+
+_ROT_F12 = np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32)                      # pure translation: epipolar lines are the rows
+_ROT_SCALE = (1.2 ** np.arange(8)).astype(np.float32)
+
+
+def rot_oracle(S, entry, ori):
+    n = S["n"]; ones = np.ones(n, np.uint8); zeros = np.zeros(n, np.uint8); nost = np.full(n, -1, np.float32)
+    k1, d1, k2, d2, q, bd, fv = S["k1"], S["d1"], S["k2"], S["d2"], S["q"], S["bounds"], S["fv"]
+    if entry == "SearchByProjection": return O.search_by_projection(k2, d2, nost, bd, q, ori)
+    if entry == "SearchForInitialization": return O.search_for_initialization(k1, d1, k2, d2, bd, S["prev"], 10, 0.9, ori)[::2]
+    if entry == "SearchByBoW": return O.search_by_bow(k1, d1, ones, fv, k2, d2, fv, 0.7, ori)
+    if entry == "SearchByBoWKeyFrames": return O.search_by_bow_keyframes(k1, d1, ones, fv, k2, d2, ones, fv, 0.75, ori)
+    if entry == "SearchForTriangulation":
+        return O.search_for_triangulation(k1, d1, zeros, zeros, fv, k2, d2, zeros, zeros, fv, _ROT_F12, 1e6, 120.0, _ROT_SCALE,
+                                          _ROT_SCALE * _ROT_SCALE, False, ori)
+    return O.search_by_projection_reloc(k2, d2, bd, q, 100, ori)
+
+
+def rot_device(iv, S, entry, ori):
+    n = S["n"]; ones = np.ones(n, np.uint8); zeros = np.zeros(n, np.uint8); nost = np.full(n, -1, np.float32)
+    k1, d1, k2, d2, q, bd, fv = S["k1"], S["d1"], S["k2"], S["d2"], S["q"], S["bounds"], S["fv"]
+    if entry == "SearchByProjection": return iv.ORBmatcher(0.9, ori).SearchByProjection(k2, d2, nost, bd, q)
+    if entry == "SearchForInitialization": return iv.ORBmatcher(0.9, ori).SearchForInitialization(k1, d1, k2, d2, bd, S["prev"], 10)[::2]
+    if entry == "SearchByBoW": return iv.ORBmatcher(0.7, ori).SearchByBoW(k1, d1, ones, fv, k2, d2, fv)
+    if entry == "SearchByBoWKeyFrames": return iv.ORBmatcher(0.75, ori).SearchByBoWKeyFrames(k1, d1, ones, fv, k2, d2, ones, fv)
+    if entry == "SearchForTriangulation":
+        return iv.ORBmatcher(0.6, ori).SearchForTriangulation(k1, d1, zeros, zeros, fv, k2, d2, zeros, zeros, fv, _ROT_F12, 1e6, 120.0,
+                                                              _ROT_SCALE, _ROT_SCALE * _ROT_SCALE, False)
+    return iv.ORBmatcher(0.9, ori).SearchByProjectionReloc(k2, d2, bd, q, 100)
+
+
+@pytest.mark.parametrize("case,ori", _ROT_CASES, ids=[c + ("" if o else "-orientation-off") for c, o in _ROT_CASES])
+@pytest.mark.parametrize("entry", _ROT_ENTRIES)
+def test_rotation_filter_on_hand_made_histograms(iv, entry, case, ori):
+    """The extractor scenarios reject only a few noise bins and never tie.  Here every match is certain (one candidate at
+    distance 0) and the bin populations are chosen, so the surviving matches are known by hand: the oracle and the device path
+    must both give exactly them."""
+    S = rot_scene(case)
+    exp = rot_expected(S, entry, ori)
+    om, on = rot_oracle(S, entry, ori)
+    gm, gn = rot_device(iv, S, entry, ori)
+    assert on == int((exp >= 0).sum()) and np.array_equal(om, exp)
+    assert gn == on and np.array_equal(gm, om)
+
+
 def test_bow_transform_and_vectors(iv):
     """DBoW2 transform (descriptor -> word / node / weight), BowVector, FeatureVector, and the
     feature vectors feeding SearchByBoW end to end."""
