@@ -416,6 +416,36 @@ int  ivf_tracker_search_local(ivf_tracker* t, const uint8_t* d_records, size_t r
                               int max_points_per_frame, const uint8_t* d_occupied, float th, float nn_ratio, float cos_limit,
                               float* d_point_quality, float* d_key_quality, int32_t* d_assign, int32_t* d_nmatches, void* hip_stream);
 
+/* Batched Optimizer::PoseOptimization (ORB/src/Optimizer.cc:251-503), the call between the two searches: for frame slot f = record
+ * d_frames[f], one 6-dof pose vertex and one unary edge per keypoint that holds a map point -- EdgeSE3ProjectXYZOnlyPose where
+ * mvuRight < 0, EdgeStereoSE3ProjectXYZOnlyPose otherwise -- with information mvInvLevelSigma2[octave] (1.0f / (sf * sf) of
+ * cfg.scale_factors, as the ORBextractor constructor derives it) and a Huber kernel of width deltaMono / deltaStereo TIMES THE MAP
+ * POINT'S QUALITY SCORE (:315-320, :342, :380), optimised by g2o's Levenberg-Marquardt on the dense 6x6 system in n_rounds rounds of
+ * at most 10 iterations; after every round the edges are re-classified against 5.991 / 7.815 (:423-490), the kernels are dropped after
+ * round min(2, n_rounds - 2), and a frame with fewer than 10 edges stops after its first round (:492).  One HIP kernel, one workgroup
+ * per frame, double arithmetic where the reference uses it; the sums over edges are taken in a fixed order (bit-identical re-runs).
+ * d_xw [n_frames][nfeatures][3] = pMP->GetWorldPos() of the point keypoint i holds; d_has_point [n_frames][nfeatures] = mvpMapPoints[i]
+ * != NULL (keypoints past the record's count are ignored); d_quality [n_frames][nfeatures] or NULL (= 1.0f) = the qual_score of
+ * :315-320; n_rounds = FLAGS_optimizer_pose_opt_iter_count (default 4), 1..4.
+ * d_poses [n_frames][12] in: pFrame->mTcw (row-major 3x4), out: the pose SetPose receives; d_outlier [n_frames][nfeatures] = mvbOutlier
+ * (0 where there is no point); d_ninliers [n_frames] = the return value (0 with fewer than 3 correspondences: pose unchanged; -1 for a
+ * record index outside [0, n_records): pose unchanged); d_chi2 [n_frames][nfeatures] (nullable) = mvChi2 as logging == true records it
+ * in round n_rounds - 1, 0 where there is no point or that round did not run.  n_frames <= max_pairs.
+ * Asynchronous on hip_stream; obeys the handle's one-call-at-a-time rule like the two searches. */
+int  ivf_tracker_optimize_pose(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_frames, int n_frames,
+                               const float* d_xw, const uint8_t* d_has_point, const float* d_quality, int n_rounds, float* d_poses,
+                               uint8_t* d_outlier, int32_t* d_ninliers, float* d_chi2, void* hip_stream);
+/* The inputs of ivf_tracker_optimize_pose from what the two searches wrote, without leaving the device.
+ * from_pairs: after ivf_tracker_run on the same d_pairs / d_poses_pairs ([n_pairs][2][12] or NULL = identity): d_xw[p][i2] =
+ * Frame::UnprojectStereo(d_assign[p][i2]) of the LAST record of pair p under its last pose (ORB/src/Frame.cc:958-972, the float / gemm
+ * arithmetic ivf_tracker_run projects with), d_has_point[p][i2] = 1; 0 (and xw = 0) where d_assign is -1, the last keypoint has no
+ * depth or the last record index is outside the block.  The frames to optimise are the pairs' cur records.
+ * from_local: after ivf_tracker_search_local: d_xw[f][i] = d_points[d_point_offsets[f] + d_assign[f][i]].pos. */
+int  ivf_tracker_points_from_pairs(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_pairs, int n_pairs,
+                                   const float* d_poses_pairs, const int32_t* d_assign, float* d_xw, uint8_t* d_has_point, void* hip_stream);
+int  ivf_tracker_points_from_local(ivf_tracker* t, const ivf_local_point* d_points, const int32_t* d_point_offsets, const int32_t* d_assign,
+                                   int n_frames, float* d_xw, uint8_t* d_has_point, void* hip_stream);
+
 /* ---- introspection FCN forward (IF/networks/models_light/models_light.py:18-28; called at
  * ORB/Examples/Stereo/stereo_kitti.cc:231-247 (load) and :493-514 (pre-process, forward, u8 truncation)) ----
  * weights_blob: the model's state_dict f32 tensors in state_dict order, num_batches_tracked skipped

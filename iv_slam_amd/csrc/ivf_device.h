@@ -206,6 +206,38 @@ void launch_pack_gather(const Buffers& b, const ivf_keypoint* kpsUn, int nf, int
 // k_undistort_keys (ivf_rectify.hip): frame f reads kps + f * kpStride and count[f * cntStride], writes out + f * outStride (elements)
 void launch_undistort_keys(const UndistortCam& cam, bool passThrough, const ivf_keypoint* kps, size_t kpStride, const int* count, int cntStride,
                            int nFrames, int cap, ivf_keypoint* out, size_t outStride, hipStream_t s);
+// gather record (ivf_frontend_pack_gather_block): {int32 n; int32 pad[3]; ivf_keypoint kps[nf]; uint8 desc[nf][32]; float uright[nf]; float depth[nf]}
+__device__ __forceinline__ int rec_count(const uint8_t* r, int nf) { const int n = *(const int*)r; return n < 0 ? 0 : (n > nf ? nf : n); }
+__device__ __forceinline__ const ivf_keypoint* rec_kps(const uint8_t* r) { return (const ivf_keypoint*)(r + 16); }
+__device__ __forceinline__ const uint8_t* rec_desc(const uint8_t* r, int nf) { return r + 16 + (size_t)nf * 24; }
+__device__ __forceinline__ const float* rec_uright(const uint8_t* r, int nf) { return (const float*)(r + 16 + (size_t)nf * 56); }
+__device__ __forceinline__ const float* rec_depth(const uint8_t* r, int nf) { return (const float*)(r + 16 + (size_t)nf * 60); }
+// cv::gemm on CV_32F operands: double accumulation of (double)a * (double)b, + (double)c, one narrowing
+__device__ __forceinline__ void mul_add(const float* R, const float* p, const float* t, float* out)
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+        out[i] = (float)((double)R[3 * i] * (double)p[0] + (double)R[3 * i + 1] * (double)p[1] + (double)R[3 * i + 2] * (double)p[2] + (double)t[i]);
+}
+// -R.t() * t (Frame::UpdatePoseMatrices, Frame.cc:549-555; ORBmatcher.cc:1385)
+__device__ __forceinline__ void neg_rt_mul(const float* R, const float* t, float* out)
+{
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+        out[j] = (float)(-((double)R[j] * (double)t[0] + (double)R[3 + j] * (double)t[1] + (double)R[6 + j] * (double)t[2]));
+}
+
+// what ivf_pose.hip needs of a tracker handle (ivf_track.hip alone knows struct ivf_tracker).  tracker_begin: the argument checks every
+// tracker entry point shares, hipSetDevice and the wait for the handle's previous call; tracker_end: the event the next call waits for
+struct TrackerView {
+    int nf, nlevels, maxPairs;
+    size_t recBytes;
+    float fx, fy, cx, cy, invfx, invfy, bf;
+    float scale[kMaxLevels];
+};
+int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n_records, int n_items, hipStream_t st, TrackerView* v);
+int tracker_end(ivf_tracker* t, hipStream_t st);
+
 void launch_hamming_pairs(const uint8_t* a, const uint8_t* b, const int* pairs, int n, int* dist, hipStream_t s);
 void launch_distinct_median(const uint8_t* desc, int n, int* median, hipStream_t s);
 void launch_bow_transform(const int* childStart, const int* child, const uint8_t* nodeDesc, const uint8_t* desc, int n, int nidLevel,

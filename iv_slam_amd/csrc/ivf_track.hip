@@ -61,33 +61,11 @@ struct TrackParams {                               // uniform kernel arguments
 // gets nmatches = -1, assign = -1 and is otherwise skipped
 DEVINL bool rec_ok(const TrackParams& P, int r) { return (unsigned)r < (unsigned)P.nRecords; }
 
-// gather record: {int32 n; int32 pad[3]; ivf_keypoint kps[nf]; uint8 desc[nf][32]; float uright[nf]; float depth[nf]}
-DEVINL int rec_count(const uint8_t* r, int nf) { const int n = *(const int*)r; return n < 0 ? 0 : (n > nf ? nf : n); }
-DEVINL const ivf_keypoint* rec_kps(const uint8_t* r) { return (const ivf_keypoint*)(r + 16); }
-DEVINL const uint8_t* rec_desc(const uint8_t* r, int nf) { return r + 16 + (size_t)nf * 24; }
-DEVINL const float* rec_uright(const uint8_t* r, int nf) { return (const float*)(r + 16 + (size_t)nf * 56); }
-DEVINL const float* rec_depth(const uint8_t* r, int nf) { return (const float*)(r + 16 + (size_t)nf * 60); }
-
 // per-query record written by k_track_prepare: projection (u, v), ur = u - bf * invzc, and the packed
 // {octave, minLevel + 1, maxLevel + 1, flags: bit 0 valid, bit 1 blocks}
 struct __attribute__((aligned(16))) Query { float u, v, ur; unsigned bits; };
 DEVINL unsigned pack_bits(int oct, int lo, int hi, int valid, int blocks)
 { return (unsigned)oct | ((unsigned)(lo + 1) << 8) | ((unsigned)(hi + 1) << 16) | ((unsigned)valid << 24) | ((unsigned)blocks << 25); }
-
-// cv::gemm on CV_32F operands: double accumulation of (double)a * (double)b, + (double)c, one narrowing
-DEVINL void mul_add(const float* R, const float* p, const float* t, float* out)
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-        out[i] = (float)((double)R[3 * i] * (double)p[0] + (double)R[3 * i + 1] * (double)p[1] + (double)R[3 * i + 2] * (double)p[2] + (double)t[i]);
-}
-// -R.t() * t (Frame::UpdatePoseMatrices, Frame.cc:549-555; ORBmatcher.cc:1385)
-DEVINL void neg_rt_mul(const float* R, const float* t, float* out)
-{
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-        out[j] = (float)(-((double)R[j] * (double)t[0] + (double)R[3 + j] * (double)t[1] + (double)R[6 + j] * (double)t[2]));
-}
 
 DEVINL int hamming256(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1)
 {
@@ -952,6 +930,31 @@ struct ivf_tracker {
     hipEvent_t evDone = nullptr;          // end of the previous run: the scratch above belongs to ONE run at a time
     bool ran = false;
 };
+
+namespace ivf {
+int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n_records, int n_items, hipStream_t st, TrackerView* v)
+{
+    if (!t) return fail(IVF_E_INVALID, "null argument");
+    if (reads_records && record_bytes != t->P.recBytes)
+        return fail(IVF_E_INVALID, "record_bytes %zu: records of %d features are %zu bytes", record_bytes, t->P.nf, t->P.recBytes);
+    if (reads_records && n_records < 1) return fail(IVF_E_INVALID, "n_records must be >= 1");
+    if (n_items < 0 || n_items > t->cfg.max_pairs) return fail(IVF_E_INVALID, "%d frames / pairs outside [0,%d]", n_items, t->cfg.max_pairs);
+    HIPCHK(hipSetDevice(t->cfg.device_id));
+    if (t->ran) HIPCHK(hipStreamWaitEvent(st, t->evDone, 0));                          // the handle runs one call at a time
+    const TrackParams& P = t->P;
+    v->nf = P.nf; v->nlevels = P.nlevels; v->maxPairs = t->cfg.max_pairs; v->recBytes = P.recBytes;
+    v->fx = P.fx; v->fy = P.fy; v->cx = P.cx; v->cy = P.cy; v->invfx = P.invfx; v->invfy = P.invfy; v->bf = P.bf;
+    for (int l = 0; l < kMaxLevels; l++) v->scale[l] = P.scale[l];
+    return IVF_OK;
+}
+int tracker_end(ivf_tracker* t, hipStream_t st)
+{
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(t->evDone, st));
+    t->ran = true;
+    return IVF_OK;
+}
+}  // namespace ivf
 
 extern "C" {
 

@@ -85,3 +85,45 @@ class BatchTracker:
                                                  None if point_quality is None else point_quality.data_ptr(),
                                                  None if key_quality is None else key_quality.data_ptr(),
                                                  assign.data_ptr(), nmatches.data_ptr(), stream_ptr))
+
+    def points_from_pairs(self, records, pairs, assign, xw, has_point, poses=None, stream_ptr=None):
+        """The map points behind run()'s assignments: xw[p, i2] = Frame::UnprojectStereo(assign[p, i2]) of the LAST record of pair p under
+        its last pose (ORB/src/Frame.cc:958-972), has_point[p, i2] = 1 where there is one.  pairs / poses / assign as run() took and
+        wrote them; xw: torch.float32 [n_pairs, nfeatures, 3], has_point: torch.uint8 [n_pairs, nfeatures].  Asynchronous."""
+        n_rec = records.numel() // self.record_bytes
+        n_pairs = pairs.shape[0]
+        assert pairs.element_size() == 4 and pairs.is_contiguous() and assign.element_size() == 4 and assign.numel() >= n_pairs * self.nfeatures
+        assert poses is None or (poses.is_contiguous() and poses.numel() == n_pairs * 24), "poses are per PAIR: [n_pairs, 2, 12]"
+        assert xw.element_size() == 4 and xw.numel() >= n_pairs * self.nfeatures * 3 and has_point.element_size() == 1 and has_point.numel() >= n_pairs * self.nfeatures
+        check(self._lib.ivf_tracker_points_from_pairs(self._h, records.data_ptr(), self.record_bytes, n_rec, pairs.data_ptr(), n_pairs,
+                                                      None if poses is None else poses.data_ptr(), assign.data_ptr(), xw.data_ptr(),
+                                                      has_point.data_ptr(), stream_ptr))
+
+    def points_from_local(self, points, point_offsets, assign, xw, has_point, stream_ptr=None):
+        """The map points behind search_local()'s assignments: xw[f, i] = points[point_offsets[f] + assign[f, i]].pos.  Asynchronous."""
+        n_frames = point_offsets.numel() - 1
+        assert point_offsets.element_size() == 4 and assign.element_size() == 4 and assign.numel() >= n_frames * self.nfeatures
+        assert xw.element_size() == 4 and xw.numel() >= n_frames * self.nfeatures * 3 and has_point.element_size() == 1 and has_point.numel() >= n_frames * self.nfeatures
+        check(self._lib.ivf_tracker_points_from_local(self._h, points.data_ptr(), point_offsets.data_ptr(), assign.data_ptr(), n_frames,
+                                                      xw.data_ptr(), has_point.data_ptr(), stream_ptr))
+
+    def optimize_pose(self, records, frames, xw, has_point, poses, outlier, ninliers, quality=None, n_rounds=4, chi2=None, stream_ptr=None):
+        """Optimizer::PoseOptimization (ORB/src/Optimizer.cc:251-503) for n_frames frames in one kernel launch.  frames: torch.int32
+        [n_frames] record indices; xw: torch.float32 [n_frames, nfeatures, 3] world position of the point each keypoint holds;
+        has_point: torch.uint8 [n_frames, nfeatures]; quality: torch.float32 [n_frames, nfeatures] or None (= 1): the map point's quality
+        score, which scales the edge's Huber width; poses: torch.float32 [n_frames, 12] in/out (mTcw -> the optimised pose);
+        outlier: torch.uint8 [n_frames, nfeatures] (mvbOutlier); ninliers: torch.int32 [n_frames]; chi2: torch.float32
+        [n_frames, nfeatures] or None (mvChi2 of the last round).  Asynchronous on the given stream."""
+        n_rec = records.numel() // self.record_bytes
+        n_frames = frames.numel()
+        nf = self.nfeatures
+        assert frames.element_size() == 4 and frames.is_contiguous() and poses.is_contiguous() and poses.element_size() == 4 and poses.numel() == n_frames * 12
+        assert xw.is_contiguous() and xw.element_size() == 4 and xw.numel() >= n_frames * nf * 3
+        assert has_point.element_size() == 1 and has_point.numel() >= n_frames * nf and outlier.element_size() == 1 and outlier.numel() >= n_frames * nf
+        assert ninliers.element_size() == 4 and ninliers.numel() >= n_frames
+        for q in (quality, chi2):
+            assert q is None or (q.is_contiguous() and q.element_size() == 4 and q.numel() >= n_frames * nf)
+        check(self._lib.ivf_tracker_optimize_pose(self._h, records.data_ptr(), self.record_bytes, n_rec, frames.data_ptr(), n_frames,
+                                                  xw.data_ptr(), has_point.data_ptr(), None if quality is None else quality.data_ptr(),
+                                                  int(n_rounds), poses.data_ptr(), outlier.data_ptr(), ninliers.data_ptr(),
+                                                  None if chi2 is None else chi2.data_ptr(), stream_ptr))

@@ -4,7 +4,7 @@ reference's stereo driver (introspective_ORB_SLAM/Examples/Stereo/stereo_kitti.c
 System::TrackStereo would take over -- load pair, optional undistort/rectify remap, optional cost image (predicted
 heat maps from disk, remapped like the left image, :470-521), extract L/R, stereo match.
 
-  python tools/replay_kitti.py SEQUENCE_DIR SETTINGS.yaml [--rectify] [--undistort] [--qual DIR | --fcn WEIGHTS.bin [--fcn-input WxH]] [--batch 16] [--track]
+  python tools/replay_kitti.py SEQUENCE_DIR SETTINGS.yaml [--rectify] [--undistort] [--qual DIR | --fcn WEIGHTS.bin [--fcn-input WxH]] [--batch 16] [--track [--optimize-pose]]
                                                            [--undistort-keypoints]
   python tools/replay_kitti.py --make-synthetic DIR --frames 12        # writes a small synthetic sequence + settings
 
@@ -109,11 +109,12 @@ class Replay:
     """The per-frame device work of the driver, batched: remap (optional) -> StereoFrontend."""
 
     def __init__(self, settings, rectify=False, undistort=False, introspect=False, batch=16, device_id=0, fcn_blob=None, track=False,
-                 fcn_input=None, undistort_keypoints=False):
+                 fcn_input=None, undistort_keypoints=False, optimize_pose=False):
         import torch
         import iv_slam_amd as iv
         self.torch = torch; self.iv = iv
         self.track = track; self.prev_left = None
+        self.optimize_pose = optimize_pose; self.tracker = None
         self.S = settings
         self.dev = torch.device("cuda:%d" % device_id)
         nf, sf, nl, ini, mn, _ = settings.extractor_params()
@@ -193,7 +194,39 @@ class Replay:
                 l["kps_raw"] = l["kps"]; l["kps"] = l.pop("kps_un")
         if self.track:
             self._track(res)
+        if self.optimize_pose and n > 1:
+            self._optimize(res)
         return res
+
+    # ---- the batched tracker chain on the batch's own gather block, never leaving the device: ivf_tracker_run (zero-motion prior, identity
+    # poses) -> ivf_tracker_points_from_pairs (the last frame's stereo points) -> ivf_tracker_optimize_pose (Optimizer::PoseOptimization,
+    # ORB/src/Optimizer.cc:251-503).  Pairs are (k - 1, k) inside the batch; res[k][0]["pose_opt"] = (inliers, edges, Tcw relative to k - 1).
+    def _optimize(self, res):
+        torch = self.torch
+        n = len(res)
+        nf = self.fe.nfeatures
+        if self.tracker is None:
+            S = self.S
+            bf, b = S.stereo()
+            self.tracker = self.iv.BatchTracker(nf, self.scale_factors, float(S["Camera.fx"]), float(S["Camera.fy"]), float(S["Camera.cx"]),
+                                                float(S["Camera.cy"]), float(bf), self.bounds, max_pairs=self.batch, b=float(b))
+        tr = self.tracker
+        block = torch.zeros(self.batch * self.fe.gather_record_bytes(), dtype=torch.uint8, device=self.dev)
+        self.fe.pack_gather_block(block)
+        self.fe.sync()
+        pairs = torch.tensor([(k - 1, k) for k in range(1, n)], dtype=torch.int32, device=self.dev)
+        m = n - 1
+        assign = torch.empty((m, nf), dtype=torch.int32, device=self.dev); nm = torch.empty(m, dtype=torch.int32, device=self.dev)
+        xw = torch.empty((m, nf, 3), dtype=torch.float32, device=self.dev); has = torch.empty((m, nf), dtype=torch.uint8, device=self.dev)
+        poses = torch.tensor([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], dtype=torch.float32, device=self.dev).repeat(m, 1).contiguous()
+        outl = torch.empty((m, nf), dtype=torch.uint8, device=self.dev); ninl = torch.empty(m, dtype=torch.int32, device=self.dev)
+        tr.run(block, pairs, assign, nm)
+        tr.points_from_pairs(block, pairs, assign, xw, has)
+        tr.optimize_pose(block, pairs[:, 1].contiguous(), xw, has, poses, outl, ninl)
+        torch.cuda.synchronize()
+        ninl = ninl.cpu().numpy(); edges = has.sum(1).cpu().numpy(); poses = poses.cpu().numpy()
+        for k in range(1, n):
+            res[k][0]["pose_opt"] = (int(ninl[k - 1]), int(edges[k - 1]), poses[k - 1].reshape(3, 4))
 
     # ---- pose-free replay of the tracker's matcher call (Tracking::TrackWithMotionModel, ORB/src/Tracking.cc:1303-1342):
     # the previous frame's stereo points are searched for in the current frame around their OLD image position (zero-motion
@@ -235,6 +268,9 @@ def main():
                                         "u8 resize to WxH, forward at WxH, u8 resize of the map back to the image size)")
     ap.add_argument("--batch", type=int, default=16); ap.add_argument("--max-frames", type=int, default=0)
     ap.add_argument("--track", action="store_true", help="also replay the tracker's cross-frame matcher call (zero-motion prior) on resident frames")
+    ap.add_argument("--optimize-pose", action="store_true",
+                    help="with --track: the batched chain ivf_tracker_run -> points_from_pairs -> optimize_pose (Optimizer::PoseOptimization) on the "
+                         "pairs inside every batch; reports the inliers per frame")
     ap.add_argument("--undistort-keypoints", action="store_true",
                     help="Frame::UndistortKeyPoints with the settings file's Camera.k1..k3 (Frame.cc:696-726): report mvKeysUn instead of mvKeys "
                          "and, with --track, search inside the undistorted image bounds (Frame.cc:728-756)")
@@ -246,6 +282,8 @@ def main():
         return 0
     if not a.sequence or not a.settings:
         ap.error("SEQUENCE_DIR and SETTINGS.yaml are required")
+    if a.optimize_pose and not a.track:
+        ap.error("--optimize-pose needs --track")
     S = kitti.Settings.load(a.settings)
     left, right, ts = kitti.LoadImages(a.sequence)
     n = len(ts) if not a.max_frames else min(len(ts), a.max_frames)
@@ -266,7 +304,7 @@ def main():
         if len(fcn_input) != 2 or min(fcn_input) < 1:
             ap.error("--fcn-input takes WxH, e.g. 512x512")
     rp = Replay(S, a.rectify, a.undistort, introspect=bool(a.qual), batch=batch, fcn_blob=blob, track=a.track, fcn_input=fcn_input,
-                undistort_keypoints=a.undistort_keypoints)
+                undistort_keypoints=a.undistort_keypoints, optimize_pose=a.optimize_pose)
     if rp.camera is not None:
         print("camera: %d distortion coefficients, k1 %s; image bounds %s" % (len(rp.camera.dist), "!= 0" if rp.camera.undistorts() else "== 0 (no-op)",
                                                                                "[%.2f, %.2f] x [%.2f, %.2f]" % (rp.bounds[0], rp.bounds[2], rp.bounds[1], rp.bounds[3])))
@@ -289,7 +327,9 @@ def main():
             med = float(np.median(l["depth"][m])) if m.any() else float("nan")
             print("frame %6d t=%.3f  kps L/R %4d/%4d  stereo matches %4d  median depth %.2f%s" %
                   (i, ts[i], len(l["kps"]), len(r["kps"]), int(m.sum()), med,
-                   "  tracked from previous frame %4d" % l["tracked"][1] if "tracked" in l else ""))
+                   ("  tracked from previous frame %4d" % l["tracked"][1] if "tracked" in l else "") +
+                   ("  pose optimisation %4d inliers of %4d edges, |t| %.3f m" % (l["pose_opt"][0], l["pose_opt"][1], float(np.linalg.norm(l["pose_opt"][2][:, 3])))
+                    if "pose_opt" in l else "")))
     if done:
         print("%d pairs, device part (upload + remap + extract + match + fetch) %.1f pairs/s" % (done, done / t_dev))
     return 0
