@@ -60,7 +60,7 @@ int         ivf_version(void);
 const char* ivf_last_error(void);
 int         ivf_device_count(void);                 /* number of visible HIP devices (0 if none) */
 long long   ivf_debug_launch_count(void);           /* measurement aid: kernel launches this process has issued through the library */
-/* Build provenance: the first 16 hex digits of sha256 over iv_slam_amd/csrc/{*.hip sorted, ivf_device.h} and include/{* sorted},
+/* Build provenance: the first 16 hex digits of sha256 over iv_slam_amd/csrc/{*.hip sorted, *.h sorted} and include/{* sorted},
  * taken when the library was linked (iv_slam_amd/csrc/Makefile).  iv_slam_amd/_lib.py recomputes it from the sources next to
  * the library and refuses to load a library built from anything else: a stale .so cannot produce a test result or a bench line.
  * r05: the hash also covers the build's variant flags, returned by ivf_build_flags() -- "" for the product, "-DIVF_EXPERIMENT" for the

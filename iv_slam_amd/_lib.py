@@ -192,7 +192,7 @@ def source_build_id(flags=""):
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     inc = os.path.join(os.path.dirname(_HERE), "include")
-    files = sorted(glob.glob(os.path.join(csrc, "*.hip"))) + [os.path.join(csrc, "ivf_device.h")] + sorted(glob.glob(os.path.join(inc, "*")))
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip"))) + sorted(glob.glob(os.path.join(csrc, "*.h"))) + sorted(glob.glob(os.path.join(inc, "*")))
     if not os.path.isfile(os.path.join(inc, "ivfront.h")) or not os.path.isfile(os.path.join(csrc, "ivf_device.h")):
         return None
     h = hashlib.sha256()

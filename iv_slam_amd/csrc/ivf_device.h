@@ -197,10 +197,6 @@ void launch_describe(const Config& hc, const Config* dc, const Buffers& b, const
                      int costPitch, int nImg, int nSides, hipStream_t s);
 void launch_stereo(const Config& hc, const Config* dc, const Buffers& b, int nPairs, float bf, float bb, hipStream_t s);
 void launch_test_retain_best(const float* dResp, int n, int nPoints, int* dOrder, hipStream_t s);
-void launch_grid_build(const ivf_keypoint* kps, int n, float minX, float minY, float invW, float invH, int* start, int* idx, hipStream_t s);
-void launch_grid_window(const ivf_keypoint* kps, const uint8_t* desc, const int* start, const int* idx, float minX, float minY,
-                        float invW, float invH, int nq, const float* qu, const float* qv, const float* qr, const int* qminL,
-                        const int* qmaxL, const uint8_t* qdesc, const uint8_t* qvalid, int cap, int* count, int* cand, hipStream_t s);
 // kpsUn != nullptr: the records carry these keypoints (mvKeysUn of the left frames, addressed like b.kps: pair p at 2 * p * nf) instead of b.kps
 void launch_pack_gather(const Buffers& b, const ivf_keypoint* kpsUn, int nf, int nPairs, uint8_t* block, size_t recBytes, hipStream_t s);
 // k_undistort_keys (ivf_rectify.hip): frame f reads kps + f * kpStride and count[f * cntStride], writes out + f * outStride (elements)
@@ -228,7 +224,8 @@ __device__ __forceinline__ void neg_rt_mul(const float* R, const float* t, float
 }
 
 // what ivf_pose.hip needs of a tracker handle (ivf_track.hip alone knows struct ivf_tracker).  tracker_begin: the argument checks every
-// tracker entry point shares, hipSetDevice and the wait for the handle's previous call; tracker_end: the event the next call waits for
+// tracker entry point shares, hipSetDevice and the wait for the handle's previous call; tracker_end: the event the next call waits for;
+// v may be null (ivf_track.hip's own entry points)
 struct TrackerView {
     int nf, nlevels, maxPairs;
     size_t recBytes;
@@ -237,11 +234,6 @@ struct TrackerView {
 };
 int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n_records, int n_items, hipStream_t st, TrackerView* v);
 int tracker_end(ivf_tracker* t, hipStream_t st);
-
-void launch_hamming_pairs(const uint8_t* a, const uint8_t* b, const int* pairs, int n, int* dist, hipStream_t s);
-void launch_distinct_median(const uint8_t* desc, int n, int* median, hipStream_t s);
-void launch_bow_transform(const int* childStart, const int* child, const uint8_t* nodeDesc, const uint8_t* desc, int n, int nidLevel,
-                          int* leaf, int* nodeAt, hipStream_t s);
 
 }  // namespace ivf
 

@@ -9,12 +9,13 @@
 //   k_describe      IC_Angle + rBRIEF + output assembly             (:78-148, :1253-1294; Frame.cc:130-143)
 //   k_stereo_match  row-band Hamming + 11x11 SAD + parabola         (Frame::ComputeStereoMatches Frame.cc:758-915)
 //   k_stereo_gate   median gate                                     (Frame.cc:918-931)
-//   k_hamming_pairs DescriptorDistance                              (ORBmatcher.cc:1700-1716)
+// The matchers' kernels (k_hamming_pairs, k_distinct_median, k_bow_transform, k_grid_build, k_grid_window) are in ivf_match.hip, next
+// to their callers; hamming256 and wave_min_u32, which the stereo matcher shares with them, come from ivf_grid.h.
 //
 // Everything here is integer/byte work bounded by HBM bandwidth; there is no GEMM shape in this
 // part of the path, so no MFMA.  Compiled with -ffp-contract=off: float expressions must round
 // exactly like the reference's un-fused CPU code.
-#include "ivf_device.h"
+#include "ivf_grid.h"
 #include <cstdlib>
 
 namespace ivf {
@@ -62,17 +63,6 @@ DEVINL bool xcd_tile_image(int nTiles, int nImg, int& tile, int& img)
     const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
     img = (j / nTiles) * 8 + xcd; tile = j % nTiles;
     return img < nImg;
-}
-DEVINL unsigned wave_min_u32(unsigned v)
-{
-    unsigned t;
-    t = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false); v = t < v ? t : v;   // row_shr:1
-    t = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false); v = t < v ? t : v;   // row_shr:2
-    t = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false); v = t < v ? t : v;   // row_shr:4
-    t = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false); v = t < v ? t : v;   // row_shr:8
-    t = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xa, 0xf, false); v = t < v ? t : v;   // row_bcast:15
-    t = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xc, 0xf, false); v = t < v ? t : v;   // row_bcast:31
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1936,24 +1926,6 @@ __global__ __launch_bounds__(256) void k_describe(const Config* __restrict__ cfg
 #endif
 }
 
-// ------------------------------------------------------------------------------------------------
-// DescriptorDistance (ORBmatcher.cc:1700-1716): 256-bit Hamming = 8 x v_bcnt_u32_b32
-// ------------------------------------------------------------------------------------------------
-DEVINL int hamming256(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1)
-{
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-__global__ void k_hamming_pairs(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
-                                const int* __restrict__ pairs, int n, int* __restrict__ dist)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint4* pa = (const uint4*)(a + (size_t)pairs[2 * i] * 32);
-    const uint4* pb = (const uint4*)(b + (size_t)pairs[2 * i + 1] * 32);
-    dist[i] = hamming256(pa[0], pa[1], pb[0], pb[1]);
-}
-
 // The pyramid scales of a wave in LDS (r06).  `cfg->scale[octave]` with an octave that came out of a keypoint record is a vector load BEHIND that record -- one
 // more dependent round trip per candidate in kernels that are chains of them.  Lane 0 copies the table from scalar loads into the wave's own LDS row (LDS
 // operations of one wave execute in order: no workgroup barrier); the lookup is then a conflict-free `ds_read`.  (A local array + a select chain was tried
@@ -2397,81 +2369,6 @@ void launch_stereo(const Config& hc, const Config* dc, const Buffers& b, int nPa
     A.bf = bf; A.bb = bb; A.rowCnt = b.rowCnt; A.rowList = b.rowList;
     launch_stereo_args(hc, dc, A, nPairs, s);
 }
-// ---- MapPoint::ComputeDistinctiveDescriptors (ORB/src/MapPoint.cc:281-305): per observed descriptor the median of
-// its Hamming distances to all n (the 0 of the diagonal included) = sorted row [(int)(0.5*(n-1))].  Distances live in
-// 0..256, so the median is read off a 257-bin LDS histogram instead of a sort: the smallest value whose cumulative count
-// exceeds the index.  One workgroup per row.
-__global__ __launch_bounds__(256) void k_distinct_median(const uint8_t* __restrict__ desc, int n, int* __restrict__ median)
-{
-    __shared__ int hist[257 + 7];
-    const int i = blockIdx.x, tid = threadIdx.x;
-    for (int k = tid; k < 264; k += 256) hist[k] = 0;
-    __syncthreads();
-    const uint4* pi = (const uint4*)(desc + (size_t)i * 32);
-    const uint4 a0 = pi[0], a1 = pi[1];
-    for (int j = tid; j < n; j += 256) {
-        const uint4* pj = (const uint4*)(desc + (size_t)j * 32);
-        const int d = j == i ? 0 : hamming256(a0, a1, pj[0], pj[1]);
-        atomicAdd(&hist[d], 1);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const int target = (int)(0.5 * (n - 1));
-        int acc = 0, v = 0;
-        for (; v < 257; v++) { acc += hist[v]; if (acc > target) break; }
-        median[i] = v;
-    }
-}
-
-void launch_distinct_median(const uint8_t* desc, int n, int* median, hipStream_t s)
-{
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_distinct_median, dim3(n), dim3(256), 0, s, desc, n, median);
-}
-
-// ---- DBoW2 vocabulary-tree descent (TemplatedVocabulary.h:1217-1259): 16 lanes per descriptor, one child per lane per
-// round, (distance << 16 | position) min-reduction across the 16 lanes = "first minimum in child order"
-__global__ __launch_bounds__(256) void k_bow_transform(const int* __restrict__ childStart, const int* __restrict__ child,
-                                                      const uint8_t* __restrict__ nodeDesc, const uint8_t* __restrict__ desc,
-                                                      int n, int nidLevel, int* __restrict__ leaf, int* __restrict__ nodeAt)
-{
-    const int f = (blockIdx.x * 256 + threadIdx.x) >> 4, sub = threadIdx.x & 15;
-    const bool live = f < n;
-    const uint4* pf = (const uint4*)(desc + (size_t)(live ? f : 0) * 32);
-    const uint4 a0 = pf[0], a1 = pf[1];
-    int node = 0, level = 0, nid = 0;
-    for (;;) {
-        const int c0 = childStart[node], c1 = childStart[node + 1];
-        if (c1 == c0) break;                                              // leaf (uniform within the 16 lanes)
-        ++level;
-        unsigned best = 0xffffffffu;
-        for (int c = c0 + sub; c < c1; c += 16) {
-            const int id = child[c];
-            const uint4* pn = (const uint4*)(nodeDesc + (size_t)id * 32);
-            const unsigned key = ((unsigned)hamming256(a0, a1, pn[0], pn[1]) << 16) | (unsigned)(c - c0);
-            best = min(best, key);
-        }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) best = min(best, (unsigned)__shfl_xor((int)best, o, 16));
-        node = child[c0 + (int)(best & 0xffffu)];
-        if (level == nidLevel) nid = node;
-    }
-    if (live && sub == 0) { leaf[f] = node; nodeAt[f] = nidLevel <= 0 ? 0 : nid; }
-}
-
-void launch_bow_transform(const int* childStart, const int* child, const uint8_t* nodeDesc, const uint8_t* desc, int n, int nidLevel,
-                          int* leaf, int* nodeAt, hipStream_t s)
-{
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_bow_transform, dim3((n * 16 + 255) / 256), dim3(256), 0, s, childStart, child, nodeDesc, desc, n, nidLevel, leaf, nodeAt);
-}
-
-void launch_hamming_pairs(const uint8_t* a, const uint8_t* b, const int* pairs, int n, int* dist, hipStream_t s)
-{
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_hamming_pairs, dim3((n + 255) / 256), dim3(256), 0, s, a, b, pairs, n, dist);
-}
-
 // ------------------------------------------------------------------------------------------------
 // k_pack_gather: one workgroup = one stereo pair; copies the left frame's {count, keypoints, descriptors, uRight} into
 // one contiguous record {n, kps, desc, uRight, depth} of the all-gather block (depth so that a receiving rank can
@@ -2512,134 +2409,6 @@ void launch_pack_gather(const Buffers& b, const ivf_keypoint* kpsUn, int nf, int
 {
     // the kernel itself is the one a handle without a camera runs: mvKeysUn is laid out like b.kps (left frame of pair p at 2 * p * nf)
     hipLaunchKernelGGL(k_pack_gather, dim3(nPairs), dim3(256), 0, s, b.count, kpsUn ? kpsUn : b.kps, b.desc, b.uright, b.depth, nf, (unsigned*)block, recBytes / 4);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Device-resident frame grid (Frame::AssignFeaturesToGrid / GetFeaturesInArea, ORB/src/Frame.cc:415-430, 615-680).
-// k_grid_build: ONE workgroup builds the 64x48 bucket grid of a frame in CSR form with the buckets in the reference's
-//   enumeration order (cell = ix * 48 + iy) and the keypoints of a bucket in insertion order (a stable counting sort:
-//   the rank of a keypoint inside its bucket = keypoints of the same bucket in earlier 256-blocks + earlier threads of
-//   its own block).  start: [64*48 + 1], idx: [n].
-// k_grid_window: one wave per query.  The buckets of one grid column are contiguous in `idx`, so the window is at most
-//   64 contiguous runs; every run is walked 64 candidates at a time: octave / |dx| < r / |dy| < r filters as the
-//   reference applies them (:636-664), Hamming distance of the survivors against the query descriptor, and an ordered,
-//   ballot-compacted append of (index, distance) to the query's candidate list (cap entries; count may exceed cap =
-//   overflow, the host then re-does that query through the pair path).
-// ------------------------------------------------------------------------------------------------
-constexpr int kGC = 64, kGR = 48;
-__global__ __launch_bounds__(256) void k_grid_build(const ivf_keypoint* __restrict__ kps, int n, float minX, float minY,
-                                                   float invW, float invH, int* __restrict__ start, int* __restrict__ idx)
-{
-    __shared__ int cnt[kGC * kGR];
-    __shared__ int part[256];
-    __shared__ int blk[256];
-    const int tid = threadIdx.x;
-    for (int c = tid; c < kGC * kGR; c += 256) cnt[c] = 0;
-    __syncthreads();
-    auto cell_of = [&](int i) {
-        const int px = (int)roundf((kps[i].x - minX) * invW), py = (int)roundf((kps[i].y - minY) * invH);   // Frame::PosInGrid :672-673
-        return (px < 0 || px >= kGC || py < 0 || py >= kGR) ? -1 : px * kGR + py;
-    };
-    for (int i = tid; i < n; i += 256) { const int c = cell_of(i); if (c >= 0) atomicAdd(&cnt[c], 1); }
-    __syncthreads();
-    // exclusive prefix over the 3072 buckets: 12 per thread + a block scan of the partial sums
-    constexpr int PER = kGC * kGR / 256;
-    int local[PER], sum = 0;
-#pragma unroll
-    for (int k = 0; k < PER; k++) { local[k] = sum; sum += cnt[tid * PER + k]; }
-    part[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const int v = tid >= off ? part[tid - off] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    const int base = part[tid] - sum;
-#pragma unroll
-    for (int k = 0; k < PER; k++) { start[tid * PER + k] = base + local[k]; cnt[tid * PER + k] = base + local[k]; }   // cnt becomes the fill cursor
-    if (tid == 255) start[kGC * kGR] = part[255];
-    __syncthreads();
-    for (int i0 = 0; i0 < n; i0 += 256) {
-        const int i = i0 + tid;
-        const int c = i < n ? cell_of(i) : -1;
-        blk[tid] = c;
-        __syncthreads();
-        if (c >= 0) {
-            int before = 0;
-            for (int t = 0; t < tid; t++) before += blk[t] == c ? 1 : 0;
-            idx[cnt[c] + before] = i;
-        }
-        __syncthreads();
-        if (c >= 0) atomicAdd(&cnt[c], 1);
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void k_grid_window(const ivf_keypoint* __restrict__ kps, const uint8_t* __restrict__ desc,
-                                                    const int* __restrict__ start, const int* __restrict__ idx,
-                                                    float minX, float minY, float invW, float invH, int nq,
-                                                    const float* __restrict__ qu, const float* __restrict__ qv,
-                                                    const float* __restrict__ qr, const int* __restrict__ qminL,
-                                                    const int* __restrict__ qmaxL, const uint8_t* __restrict__ qdesc,
-                                                    const uint8_t* __restrict__ qvalid, int cap, int* __restrict__ count,
-                                                    int2* __restrict__ cand)
-{
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (q >= nq) return;
-    int total = 0;
-    if (!qvalid || qvalid[q]) {
-        const float x = qu[q], y = qv[q], r = qr[q];
-        const int minL = qminL[q], maxL = qmaxL[q];
-        // Frame::GetFeaturesInArea :620-634
-        const int x0 = max(0, (int)floorf((x - minX - r) * invW)), x1 = min(kGC - 1, (int)ceilf((x - minX + r) * invW));
-        const int y0 = max(0, (int)floorf((y - minY - r) * invH)), y1 = min(kGR - 1, (int)ceilf((y - minY + r) * invH));
-        if (x0 < kGC && x1 >= 0 && y0 < kGR && y1 >= 0) {
-            const bool chk = (minL > 0) || (maxL >= 0);
-            const uint4* qd = (const uint4*)(qdesc + (size_t)q * 32);
-            const uint4 qa = qd[0], qb = qd[1];
-            for (int ix = x0; ix <= x1; ix++) {
-                const int s = start[ix * kGR + y0], e = start[ix * kGR + y1 + 1];      // buckets iy = y0..y1 are contiguous
-                for (int j0 = s; j0 < e; j0 += 64) {
-                    const int j = j0 + lane;
-                    bool ok = j < e;
-                    int i2 = 0, d = 0;
-                    if (ok) {
-                        i2 = idx[j];
-                        const ivf_keypoint kp = kps[i2];
-                        if (chk) { if (kp.octave < minL) ok = false; if (maxL >= 0 && kp.octave > maxL) ok = false; }
-                        if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) ok = false;
-                        if (ok) {
-                            const uint4* cd = (const uint4*)(desc + (size_t)i2 * 32);
-                            const uint4 a = cd[0], b2 = cd[1];
-                            d = __popc(a.x ^ qa.x) + __popc(a.y ^ qa.y) + __popc(a.z ^ qa.z) + __popc(a.w ^ qa.w) +
-                                __popc(b2.x ^ qb.x) + __popc(b2.y ^ qb.y) + __popc(b2.z ^ qb.z) + __popc(b2.w ^ qb.w);
-                        }
-                    }
-                    const unsigned long long m = __ballot(ok);
-                    if (ok) {
-                        const int pos = total + __popcll(m & ((1ull << lane) - 1ull));
-                        if (pos < cap) cand[(size_t)q * cap + pos] = make_int2(i2, d);
-                    }
-                    total += __popcll(m);
-                }
-            }
-        }
-    }
-    if (lane == 0) count[q] = total;
-}
-
-void launch_grid_build(const ivf_keypoint* kps, int n, float minX, float minY, float invW, float invH, int* start, int* idx, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(256), 0, s, kps, n, minX, minY, invW, invH, start, idx);
-}
-void launch_grid_window(const ivf_keypoint* kps, const uint8_t* desc, const int* start, const int* idx, float minX, float minY,
-                        float invW, float invH, int nq, const float* qu, const float* qv, const float* qr, const int* qminL,
-                        const int* qmaxL, const uint8_t* qdesc, const uint8_t* qvalid, int cap, int* count, int* cand, hipStream_t s)
-{
-    if (nq <= 0) return;
-    hipLaunchKernelGGL(k_grid_window, dim3((nq + 3) / 4), dim3(256), 0, s, kps, desc, start, idx, minX, minY, invW, invH, nq, qu, qv,
-                       qr, qminL, qmaxL, qdesc, qvalid, cap, count, (int2*)cand);
 }
 
 }  // namespace ivf

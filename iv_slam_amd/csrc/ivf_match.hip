@@ -1,7 +1,8 @@
 // ivf_match.hip -- the per-call half of the C-ABI (include/ivfront.h): every ORBmatcher search, the device-resident ivf_frame, the
 // DBoW2 vocabulary / BoW vectors, the distinctive descriptor and the quality-score update.
 // Each search builds its candidate lists and Hamming distances on the device (CandSource, node_pairs) and then replays the
-// reference's order-dependent greedy logic on the host.  Host side only: the kernels are in ivf_kernels.hip.
+// reference's order-dependent greedy logic on the host.  Its kernels (k_hamming_pairs, k_distinct_median, k_bow_transform, k_grid_build,
+// k_grid_window) are file-local, at the top; the grid they and the batched tracker (ivf_track.hip) share is ivf_grid.h.
 #include <cmath>
 #include <climits>
 #include <cstdio>
@@ -10,39 +11,178 @@
 #include <mutex>
 #include <vector>
 #include <algorithm>
-#include "ivf_device.h"
+#include "ivf_grid.h"
 
 using namespace ivf;
 
-// ---- Frame grid (ORB/src/Frame.cc:415-430, 615-680; 64 x 48, Frame.h:43-44) ----
+// ---- kernels of this file (hand-written for gfx950, wave = 64) ------------------------------------------------------------------
 namespace {
-constexpr int GC = 64, GR = 48;
+
+// DescriptorDistance (ORBmatcher.cc:1700-1716) of index pairs
+__global__ void k_hamming_pairs(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                const int* __restrict__ pairs, int n, int* __restrict__ dist)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4* pa = (const uint4*)(a + (size_t)pairs[2 * i] * 32);
+    const uint4* pb = (const uint4*)(b + (size_t)pairs[2 * i + 1] * 32);
+    dist[i] = hamming256(pa[0], pa[1], pb[0], pb[1]);
+}
+void launch_hamming_pairs(const uint8_t* a, const uint8_t* b, const int* pairs, int n, int* dist, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_hamming_pairs, dim3((n + 255) / 256), dim3(256), 0, s, a, b, pairs, n, dist);
+}
+
+// ---- MapPoint::ComputeDistinctiveDescriptors (ORB/src/MapPoint.cc:281-305): per observed descriptor the median of
+// its Hamming distances to all n (the 0 of the diagonal included) = sorted row [(int)(0.5*(n-1))].  Distances live in
+// 0..256, so the median is read off a 257-bin LDS histogram instead of a sort: the smallest value whose cumulative count
+// exceeds the index.  One workgroup per row.
+__global__ __launch_bounds__(256) void k_distinct_median(const uint8_t* __restrict__ desc, int n, int* __restrict__ median)
+{
+    __shared__ int hist[257 + 7];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    for (int k = tid; k < 264; k += 256) hist[k] = 0;
+    __syncthreads();
+    const uint4* pi = (const uint4*)(desc + (size_t)i * 32);
+    const uint4 a0 = pi[0], a1 = pi[1];
+    for (int j = tid; j < n; j += 256) {
+        const uint4* pj = (const uint4*)(desc + (size_t)j * 32);
+        const int d = j == i ? 0 : hamming256(a0, a1, pj[0], pj[1]);
+        atomicAdd(&hist[d], 1);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int target = (int)(0.5 * (n - 1));
+        int acc = 0, v = 0;
+        for (; v < 257; v++) { acc += hist[v]; if (acc > target) break; }
+        median[i] = v;
+    }
+}
+
+void launch_distinct_median(const uint8_t* desc, int n, int* median, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_distinct_median, dim3(n), dim3(256), 0, s, desc, n, median);
+}
+
+// ---- DBoW2 vocabulary-tree descent (TemplatedVocabulary.h:1217-1259): 16 lanes per descriptor, one child per lane per
+// round, (distance << 16 | position) min-reduction across the 16 lanes = "first minimum in child order"
+__global__ __launch_bounds__(256) void k_bow_transform(const int* __restrict__ childStart, const int* __restrict__ child,
+                                                      const uint8_t* __restrict__ nodeDesc, const uint8_t* __restrict__ desc,
+                                                      int n, int nidLevel, int* __restrict__ leaf, int* __restrict__ nodeAt)
+{
+    const int f = (blockIdx.x * 256 + threadIdx.x) >> 4, sub = threadIdx.x & 15;
+    const bool live = f < n;
+    const uint4* pf = (const uint4*)(desc + (size_t)(live ? f : 0) * 32);
+    const uint4 a0 = pf[0], a1 = pf[1];
+    int node = 0, level = 0, nid = 0;
+    for (;;) {
+        const int c0 = childStart[node], c1 = childStart[node + 1];
+        if (c1 == c0) break;                                              // leaf (uniform within the 16 lanes)
+        ++level;
+        unsigned best = 0xffffffffu;
+        for (int c = c0 + sub; c < c1; c += 16) {
+            const int id = child[c];
+            const uint4* pn = (const uint4*)(nodeDesc + (size_t)id * 32);
+            const unsigned key = ((unsigned)hamming256(a0, a1, pn[0], pn[1]) << 16) | (unsigned)(c - c0);
+            best = min(best, key);
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) best = min(best, (unsigned)__shfl_xor((int)best, o, 16));
+        node = child[c0 + (int)(best & 0xffffu)];
+        if (level == nidLevel) nid = node;
+    }
+    if (live && sub == 0) { leaf[f] = node; nodeAt[f] = nidLevel <= 0 ? 0 : nid; }
+}
+
+void launch_bow_transform(const int* childStart, const int* child, const uint8_t* nodeDesc, const uint8_t* desc, int n, int nidLevel,
+                          int* leaf, int* nodeAt, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_bow_transform, dim3((n * 16 + 255) / 256), dim3(256), 0, s, childStart, child, nodeDesc, desc, n, nidLevel, leaf, nodeAt);
+}
+
+// ---- the device-resident frame grid: ivf_grid.h's grid_build / grid_walk with int indices (what ivf_frame_grid returns) ----
+// k_grid_build: ONE workgroup builds the grid of a frame.  start: [64*48 + 1], idx: [n].
+__global__ __launch_bounds__(256) void k_grid_build(const ivf_keypoint* __restrict__ kps, int n, GridGeom G, int* __restrict__ start,
+                                                   int* __restrict__ idx)
+{
+    __shared__ int cnt[kGC * kGR];
+    __shared__ int part[256];
+    __shared__ int blk[256];
+    grid_build<int>(G, kps, n, start, idx, cnt, part, blk, threadIdx.x);
+}
+void launch_grid_build(const ivf_keypoint* kps, int n, const GridGeom& G, int* start, int* idx, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(256), 0, s, kps, n, G, start, idx);
+}
+
+// k_grid_window: one wave per query.  The candidates that pass the window's filters are appended, ordered and ballot-compacted,
+// as (index, distance) to the query's list (cap entries; count may exceed cap = overflow, the host then re-does that query
+// through the host grid).
+__global__ __launch_bounds__(256) void k_grid_window(const ivf_keypoint* __restrict__ kps, const uint8_t* __restrict__ desc,
+                                                    const int* __restrict__ start, const int* __restrict__ idx, GridGeom G, int nq,
+                                                    const float* __restrict__ qu, const float* __restrict__ qv,
+                                                    const float* __restrict__ qr, const int* __restrict__ qminL,
+                                                    const int* __restrict__ qmaxL, const uint8_t* __restrict__ qdesc,
+                                                    const uint8_t* __restrict__ qvalid, int cap, int* __restrict__ count,
+                                                    int2* __restrict__ cand)
+{
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (q >= nq) return;
+    int total = 0;
+    if (!qvalid || qvalid[q]) {
+        const uint4* qd = (const uint4*)(qdesc + (size_t)q * 32);
+        grid_walk<int>(G, kps, desc, start, idx, qu[q], qv[q], qr[q], qminL[q], qmaxL[q], qd[0], qd[1], lane, [&](bool ok, int i2, int d) {
+            const unsigned long long m = __ballot(ok);
+            if (ok) {
+                const int pos = total + __popcll(m & ((1ull << lane) - 1ull));
+                if (pos < cap) cand[(size_t)q * cap + pos] = make_int2(i2, d);
+            }
+            total += __popcll(m);
+        });
+    }
+    if (lane == 0) count[q] = total;
+}
+void launch_grid_window(const ivf_keypoint* kps, const uint8_t* desc, const int* start, const int* idx, const GridGeom& G, int nq,
+                        const float* qu, const float* qv, const float* qr, const int* qminL, const int* qmaxL, const uint8_t* qdesc,
+                        const uint8_t* qvalid, int cap, int* count, int* cand, hipStream_t s)
+{
+    if (nq <= 0) return;
+    hipLaunchKernelGGL(k_grid_window, dim3((nq + 3) / 4), dim3(256), 0, s, kps, desc, start, idx, G, nq, qu, qv, qr, qminL, qmaxL,
+                       qdesc, qvalid, cap, count, (int2*)cand);
+}
+}  // namespace
+
+// ---- Frame grid on the host (ORB/src/Frame.cc:415-430, 615-680): the CPU fallback of the searches that take host arrays ----
+namespace {
 struct Grid {
     std::vector<int> start, idx; float invW, invH;
     void build(const ivf_keypoint* k, int n, const ivf_bounds& bd)
     {
-        invW = (float)GC / (bd.max_x - bd.min_x); invH = (float)GR / (bd.max_y - bd.min_y);
-        start.assign(GC * GR + 1, 0); idx.assign(std::max(n, 1), 0);
+        invW = (float)kGC / (bd.max_x - bd.min_x); invH = (float)kGR / (bd.max_y - bd.min_y);
+        start.assign(kGC * kGR + 1, 0); idx.assign(std::max(n, 1), 0);
         std::vector<int> cell(std::max(n, 1), -1);
         for (int i = 0; i < n; i++) {
             const int px = (int)roundf((k[i].x - bd.min_x) * invW), py = (int)roundf((k[i].y - bd.min_y) * invH);
-            if (px < 0 || px >= GC || py < 0 || py >= GR) continue;
-            cell[i] = px * GR + py; start[cell[i] + 1]++;
+            if (px < 0 || px >= kGC || py < 0 || py >= kGR) continue;
+            cell[i] = px * kGR + py; start[cell[i] + 1]++;
         }
-        for (int c = 0; c < GC * GR; c++) start[c + 1] += start[c];
-        std::vector<int> fill(GC * GR, 0);
+        for (int c = 0; c < kGC * kGR; c++) start[c + 1] += start[c];
+        std::vector<int> fill(kGC * kGR, 0);
         for (int i = 0; i < n; i++) if (cell[i] >= 0) idx[start[cell[i]] + fill[cell[i]]++] = i;
     }
     template <class F> void query(const ivf_keypoint* k, const ivf_bounds& bd, float x, float y, float r, int minL, int maxL, F f) const
     {
-        const int x0 = std::max(0, (int)floorf((x - bd.min_x - r) * invW)); if (x0 >= GC) return;
-        const int x1 = std::min(GC - 1, (int)ceilf((x - bd.min_x + r) * invW)); if (x1 < 0) return;
-        const int y0 = std::max(0, (int)floorf((y - bd.min_y - r) * invH)); if (y0 >= GR) return;
-        const int y1 = std::min(GR - 1, (int)ceilf((y - bd.min_y + r) * invH)); if (y1 < 0) return;
+        const int x0 = std::max(0, (int)floorf((x - bd.min_x - r) * invW)); if (x0 >= kGC) return;
+        const int x1 = std::min(kGC - 1, (int)ceilf((x - bd.min_x + r) * invW)); if (x1 < 0) return;
+        const int y0 = std::max(0, (int)floorf((y - bd.min_y - r) * invH)); if (y0 >= kGR) return;
+        const int y1 = std::min(kGR - 1, (int)ceilf((y - bd.min_y + r) * invH)); if (y1 < 0) return;
         const bool chk = (minL > 0) || (maxL >= 0);
         for (int ix = x0; ix <= x1; ix++)
             for (int iy = y0; iy <= y1; iy++) {
-                const int c = ix * GR + iy;
+                const int c = ix * kGR + iy;
                 for (int j = start[c]; j < start[c + 1]; j++) {
                     const ivf_keypoint& kp = k[idx[j]];
                     if (chk) { if (kp.octave < minL) continue; if (maxL >= 0 && kp.octave > maxL) continue; }
@@ -272,7 +412,7 @@ inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 struct ivf_frame {
     int device = 0, n = 0;
     ivf_bounds bd{};
-    float invW = 0, invH = 0;
+    GridGeom geom{};                    // of bd (Frame.cc:208-209)
     std::vector<ivf_keypoint> kps;      // host copies for the greedy replay (angle, uRight)
     std::vector<float> uright;
     std::vector<uint8_t> desc;          // host copy for the overflow fallback
@@ -292,7 +432,7 @@ static int frame_alloc(ivf_frame* f, int n)
 {
     const size_t nn = (size_t)std::max(n, 1);
     const size_t oK = 0, oD = oK + up256(nn * sizeof(ivf_keypoint)), oU = oD + up256(nn * 32), oS = oU + up256(nn * sizeof(float)),
-                 oI = oS + up256((GC * GR + 1) * sizeof(int)), total = oI + up256(nn * sizeof(int));
+                 oI = oS + up256((kGC * kGR + 1) * sizeof(int)), total = oI + up256(nn * sizeof(int));
     const int rc = frame_pool_ptr()->acquire(f->device, total, f->mem);
     if (rc) return rc;
     uint8_t* b = f->mem.base;
@@ -350,7 +490,7 @@ int ivf_frame_create(const ivf_keypoint* kps, const uint8_t* desc, const float* 
     HIPCHK(hipSetDevice(device_id));
     ivf_frame* f = new ivf_frame();
     f->device = device_id; f->n = n; f->bd = *bounds;
-    f->invW = (float)GC / (bounds->max_x - bounds->min_x); f->invH = (float)GR / (bounds->max_y - bounds->min_y);   // Frame.cc:208-209
+    f->geom = grid_geom(*bounds);
     f->kps.assign(kps, kps + n); f->uright.assign(uright, uright + n); f->desc.assign(desc, desc + (size_t)n * 32);
     rc = frame_alloc(f, n);
     if (rc) { ivf_frame_destroy(f); return rc; }
@@ -361,7 +501,7 @@ int ivf_frame_create(const ivf_keypoint* kps, const uint8_t* desc, const float* 
             return fail(IVF_E_NO_DEVICE, "frame upload failed");
         }
     }
-    launch_grid_build(f->dKps, n, bounds->min_x, bounds->min_y, f->invW, f->invH, f->dStart, f->dIdx, f->stream);   // AssignFeaturesToGrid
+    launch_grid_build(f->dKps, n, f->geom, f->dStart, f->dIdx, f->stream);   // AssignFeaturesToGrid
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(f->stream) != hipSuccess) {
         ivf_frame_destroy(f);
         return fail(IVF_E_NO_DEVICE, "grid build failed");
@@ -374,7 +514,7 @@ int ivf_frame_grid(const ivf_frame* f, int32_t* cell_start, int32_t* cell_index)
 {
     if (!f || !cell_start || !cell_index) return fail(IVF_E_INVALID, "null argument");
     HIPCHK(hipSetDevice(f->device));
-    HIPCHK(hipMemcpy(cell_start, f->dStart, (GC * GR + 1) * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cell_start, f->dStart, (kGC * kGR + 1) * sizeof(int), hipMemcpyDeviceToHost));
     if (f->n > 0) HIPCHK(hipMemcpy(cell_index, f->dIdx, (size_t)f->n * sizeof(int), hipMemcpyDeviceToHost));
     return IVF_OK;
 }
@@ -409,8 +549,8 @@ static int frame_candidates(ivf_frame* f, int n_q, const float* q_u, const float
     HIPCHK(hipMemcpyAsync(f->dQmax, q_max_level, nq * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(f->dQdesc, q_desc, nq * 32, hipMemcpyHostToDevice, st));
     if (q_valid) HIPCHK(hipMemcpyAsync(f->dQvalid, q_valid, nq, hipMemcpyHostToDevice, st));
-    launch_grid_window(f->dKps, f->dDesc, f->dStart, f->dIdx, f->bd.min_x, f->bd.min_y, f->invW, f->invH, n_q, f->dQu, f->dQv, f->dQr,
-                       f->dQmin, f->dQmax, f->dQdesc, q_valid ? f->dQvalid : nullptr, f->cCap, f->dCount, f->dCand, st);
+    launch_grid_window(f->dKps, f->dDesc, f->dStart, f->dIdx, f->geom, n_q, f->dQu, f->dQv, f->dQr, f->dQmin,
+                       f->dQmax, f->dQdesc, q_valid ? f->dQvalid : nullptr, f->cCap, f->dCount, f->dCand, st);
     HIPCHK(hipGetLastError());
     std::vector<int> count(n_q), raw(nq * f->cCap * 2);
     HIPCHK(hipMemcpyAsync(count.data(), f->dCount, nq * 4, hipMemcpyDeviceToHost, st));
@@ -1153,7 +1293,7 @@ int ivf::frame_from_batch(int device, const BatchImage& src, const ivf_bounds& b
 {
     ivf_frame* f = new ivf_frame();
     f->device = device; f->bd = bounds; f->hostKps = false; f->hostDesc = false;
-    f->invW = (float)GC / (bounds.max_x - bounds.min_x); f->invH = (float)GR / (bounds.max_y - bounds.min_y);
+    f->geom = grid_geom(bounds);
     auto bail = [&](const char* what) { ivf_frame_destroy(f); return fail(IVF_E_NO_DEVICE, "%s failed for a frame from the front end", what); };
     // sized for the batch's capacity: the (pooled) arena is acquired before the keypoint count is known
     if (frame_alloc(f, src.cap) != IVF_OK) { ivf_frame_destroy(f); return IVF_E_NO_DEVICE; }
@@ -1169,7 +1309,7 @@ int ivf::frame_from_batch(int device, const BatchImage& src, const ivf_bounds& b
         if (src.uright) { if (hipMemcpyAsync(f->dUright, src.uright, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, f->stream) != hipSuccess) return bail("device copy"); }
         else if (hipMemsetD32Async((hipDeviceptr_t)f->dUright, (int)0xbf800000, (size_t)n, f->stream) != hipSuccess) return bail("fill");      // -1.0f: no stereo
     }
-    launch_grid_build(f->dKps, n, bounds.min_x, bounds.min_y, f->invW, f->invH, f->dStart, f->dIdx, f->stream);
+    launch_grid_build(f->dKps, n, f->geom, f->dStart, f->dIdx, f->stream);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(f->stream) != hipSuccess) return bail("grid build");
     *out = f;
     return IVF_OK;

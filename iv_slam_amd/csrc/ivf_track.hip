@@ -30,7 +30,9 @@
 //                    frame live in LDS, the lists of the next 16 queries are in registers before they are needed, the first
 //                    minimum is a DPP row_shr / row_bcast reduction of (distance << 6 | list position); histogram in one VGPR
 //                    (lane = bin).  Queries whose window overflowed the list are re-walked in place against the live state.
-#include "ivf_device.h"
+// The grid itself -- grid_build / grid_walk, here with unsigned short indices (nfeatures <= 4096) -- is ivf_grid.h's, shared with the
+// device-resident ivf_frame (ivf_match.hip).
+#include "ivf_grid.h"
 #include <climits>
 #include <cstring>
 #include <vector>
@@ -41,7 +43,6 @@ namespace {
 
 #define DEVINL __device__ __forceinline__
 
-constexpr int kGC = 64, kGR = 48;                 // FRAME_GRID_COLS / ROWS (ORB/include/Frame.h:43-44)
 constexpr int kListCap = 64;                      // candidates listed per query (one per lane of the greedy wave)
 constexpr int kPrefetch = 16;                     // queries whose lists are in registers ahead of the greedy walk
 constexpr int kMaxTrackFeatures = 4096;           // LDS state of k_track_greedy: 20 B per keypoint
@@ -60,114 +61,14 @@ struct TrackParams {                               // uniform kernel arguments
 // a pair / frame table built for another block (a different world size or batch) must not read outside this one: such an entry
 // gets nmatches = -1, assign = -1 and is otherwise skipped
 DEVINL bool rec_ok(const TrackParams& P, int r) { return (unsigned)r < (unsigned)P.nRecords; }
+// the grid geometry of grid_build / grid_walk (ivf_grid.h), by value: the fields keep their place in the kernel arguments
+DEVINL GridGeom geom_of(const TrackParams& P) { return GridGeom{P.minX, P.minY, P.invW, P.invH}; }
 
 // per-query record written by k_track_prepare: projection (u, v), ur = u - bf * invzc, and the packed
 // {octave, minLevel + 1, maxLevel + 1, flags: bit 0 valid, bit 1 blocks}
 struct __attribute__((aligned(16))) Query { float u, v, ur; unsigned bits; };
 DEVINL unsigned pack_bits(int oct, int lo, int hi, int valid, int blocks)
 { return (unsigned)oct | ((unsigned)(lo + 1) << 8) | ((unsigned)(hi + 1) << 16) | ((unsigned)valid << 24) | ((unsigned)blocks << 25); }
-
-DEVINL int hamming256(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1)
-{
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-// minimum over the wave without a trip through the LDS crossbar: row_shr 1/2/4/8 folds each row of 16 lanes into its lane 15,
-// row_bcast15 / row_bcast31 fold the four rows into lane 63
-DEVINL unsigned wave_min_u32_dpp(unsigned v)
-{
-    const int idn = -1;                           // 0xFFFFFFFF: identity of the unsigned minimum
-    unsigned t;
-    t = (unsigned)__builtin_amdgcn_update_dpp(idn, (int)v, 0x111, 0xf, 0xf, false); v = t < v ? t : v;   // row_shr:1
-    t = (unsigned)__builtin_amdgcn_update_dpp(idn, (int)v, 0x112, 0xf, 0xf, false); v = t < v ? t : v;   // row_shr:2
-    t = (unsigned)__builtin_amdgcn_update_dpp(idn, (int)v, 0x114, 0xf, 0xf, false); v = t < v ? t : v;   // row_shr:4
-    t = (unsigned)__builtin_amdgcn_update_dpp(idn, (int)v, 0x118, 0xf, 0xf, false); v = t < v ? t : v;   // row_shr:8
-    t = (unsigned)__builtin_amdgcn_update_dpp(idn, (int)v, 0x142, 0xa, 0xf, false); v = t < v ? t : v;   // row_bcast:15 -> rows 1, 3
-    t = (unsigned)__builtin_amdgcn_update_dpp(idn, (int)v, 0x143, 0xc, 0xf, false); v = t < v ? t : v;   // row_bcast:31 -> rows 2, 3
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-// Frame::GetFeaturesInArea (Frame.cc:615-668) for one query, walked by one wave 64 candidates at a time in the reference's
-// order (grid column ix outer, row iy inner, insertion order inside a bucket -- the buckets of a column are one contiguous run
-// of `idx`).  f(ok, i2, dist) is called by all lanes for every step; ok = the lane holds a candidate that passed the octave
-// and box filters, dist = its Hamming distance to the query descriptor.
-template <class F>
-DEVINL void walk_window(const TrackParams& P, const ivf_keypoint* __restrict__ kps, const uint8_t* __restrict__ desc,
-                        const int* __restrict__ start, const unsigned short* __restrict__ idx, float x, float y, float r,
-                        int minL, int maxL, const uint4 qa, const uint4 qb, int lane, F&& f)
-{
-    const int x0 = max(0, (int)floorf((x - P.minX - r) * P.invW)), x1 = min(kGC - 1, (int)ceilf((x - P.minX + r) * P.invW));
-    const int y0 = max(0, (int)floorf((y - P.minY - r) * P.invH)), y1 = min(kGR - 1, (int)ceilf((y - P.minY + r) * P.invH));
-    if (!(x0 < kGC && x1 >= 0 && y0 < kGR && y1 >= 0)) return;
-    const bool chk = (minL > 0) || (maxL >= 0);
-    for (int ix = x0; ix <= x1; ix++) {
-        const int s = start[ix * kGR + y0], e = start[ix * kGR + y1 + 1];
-        for (int j0 = s; j0 < e; j0 += 64) {
-            const int j = j0 + lane;
-            bool ok = j < e;
-            int i2 = 0, d = 0;
-            if (ok) {
-                i2 = idx[j];
-                const ivf_keypoint kp = kps[i2];
-                if (chk) { if (kp.octave < minL) ok = false; if (maxL >= 0 && kp.octave > maxL) ok = false; }
-                if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) ok = false;
-                if (ok) {
-                    const uint4* cd = (const uint4*)(desc + (size_t)i2 * 32);
-                    d = hamming256(cd[0], cd[1], qa, qb);
-                }
-            }
-            f(ok, i2, d);
-        }
-    }
-}
-
-// Frame::AssignFeaturesToGrid (Frame.cc:415-430) by one 256-thread workgroup: CSR, buckets in ix-major order, keypoints of a
-// bucket in insertion order (rank inside the bucket = same-bucket keypoints in earlier 256-blocks + earlier threads).
-// cnt [kGC * kGR], part [256], blk [256]: workgroup scratch in LDS.
-DEVINL void build_grid(const TrackParams& P, const ivf_keypoint* __restrict__ kc, int nC, int* __restrict__ start,
-                       unsigned short* __restrict__ idx, int* cnt, int* part, int* blk, int tid)
-{
-    for (int c = tid; c < kGC * kGR; c += 256) cnt[c] = 0;
-    __syncthreads();
-    auto cell_of = [&](int i) {
-        const int px = (int)roundf((kc[i].x - P.minX) * P.invW), py = (int)roundf((kc[i].y - P.minY) * P.invH);   // PosInGrid :672-673
-        return (px < 0 || px >= kGC || py < 0 || py >= kGR) ? -1 : px * kGR + py;
-    };
-    for (int i = tid; i < nC; i += 256) { const int c = cell_of(i); if (c >= 0) atomicAdd(&cnt[c], 1); }
-    __syncthreads();
-    constexpr int PER = kGC * kGR / 256;
-    int local[PER], sum = 0;
-#pragma unroll
-    for (int k = 0; k < PER; k++) { local[k] = sum; sum += cnt[tid * PER + k]; }
-    part[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const int v = tid >= off ? part[tid - off] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    const int base = part[tid] - sum;
-#pragma unroll
-    for (int k = 0; k < PER; k++) { start[tid * PER + k] = base + local[k]; cnt[tid * PER + k] = base + local[k]; }
-    if (tid == 255) start[kGC * kGR] = part[255];
-    __syncthreads();
-    for (int i0 = 0; i0 < nC; i0 += 256) {
-        const int i = i0 + tid;
-        const int c = i < nC ? cell_of(i) : -1;
-        blk[tid] = c;
-        __syncthreads();
-        if (c >= 0) {
-            int before = 0;
-            for (int t = 0; t < tid; t++) before += blk[t] == c ? 1 : 0;
-            idx[cnt[c] + before] = (unsigned short)i;
-        }
-        __syncthreads();
-        if (c >= 0) atomicAdd(&cnt[c], 1);
-        __syncthreads();
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // k_track_prepare: one workgroup per frame pair
@@ -192,7 +93,7 @@ __global__ __launch_bounds__(256) void k_track_prepare(TrackParams P, const uint
 
     // ---- Frame::AssignFeaturesToGrid of the current frame (Frame.cc:415-430)
     const ivf_keypoint* kc = rec_kps(recC);
-    build_grid(P, kc, nC, gStart + (size_t)p * (kGC * kGR + 1), gIdx + (size_t)p * P.nf, cnt, part, blk, tid);
+    grid_build(geom_of(P), kc, nC, gStart + (size_t)p * (kGC * kGR + 1), gIdx + (size_t)p * P.nf, cnt, part, blk, tid);
 
     // ---- poses of THIS pair: {LastFrame.mTcw, CurrentFrame.mTcw = mVelocity * mLastFrame.mTcw (Tracking.cc:1311)}, row-major 3x4;
     //      identity when none are given (zero-motion prior)
@@ -292,15 +193,15 @@ __global__ __launch_bounds__(256) void k_track_window(TrackParams P, const uint8
         const uint4* qd = (const uint4*)(rec_desc(recL, P.nf) + (size_t)i * 32);       // pMP->GetDescriptor(): the point's one observation
         const uint4 qa = qd[0], qb = qd[1];
         unsigned* L = lists + ((size_t)p * P.nf + i) * kListCap;
-        walk_window(P, rec_kps(recC), rec_desc(recC, P.nf), gStart + (size_t)p * (kGC * kGR + 1), gIdx + (size_t)p * P.nf,
-                    q.u, q.v, r, lo, hi, qa, qb, lane, [&](bool ok, int i2, int d) {
-                        const unsigned long long m = __ballot(ok);
-                        if (ok) {
-                            const int pos = total + __popcll(m & ((1ull << lane) - 1ull));
-                            if (pos < kListCap) L[pos] = (unsigned)i2 | ((unsigned)d << 16);
-                        }
-                        total += __popcll(m);
-                    });
+        grid_walk(geom_of(P), rec_kps(recC), rec_desc(recC, P.nf), gStart + (size_t)p * (kGC * kGR + 1), gIdx + (size_t)p * P.nf,
+                  q.u, q.v, r, lo, hi, qa, qb, lane, [&](bool ok, int i2, int d) {
+                      const unsigned long long m = __ballot(ok);
+                      if (ok) {
+                          const int pos = total + __popcll(m & ((1ull << lane) - 1ull));
+                          if (pos < kListCap) L[pos] = (unsigned)i2 | ((unsigned)d << 16);
+                      }
+                      total += __popcll(m);
+                  });
     }
     if (lane == 0) count[(size_t)p * P.nf + i] = total;
 }
@@ -422,7 +323,7 @@ __global__ __launch_bounds__(64) void k_track_greedy(TrackParams P, const uint8_
                         if (u2 > 0) { const float er = fabsf(qur - u2); if (er > radius) ok = false; }   // :1451-1457
                     }
                     const unsigned key1 = ok ? ((unsigned)d << 6) | (unsigned)lane : 0xffffffffu;
-                    const unsigned best = wave_min_u32_dpp(key1);                           // first minimum in list order (:1463-1467)
+                    const unsigned best = wave_min_u32(key1);                           // first minimum in list order (:1463-1467)
                     if (best != 0xffffffffu) {
                         bestDist = best >> 6;
                         bestIdx2 = __builtin_amdgcn_readlane(i2, best & 63);
@@ -436,27 +337,27 @@ __global__ __launch_bounds__(64) void k_track_greedy(TrackParams P, const uint8_
                     const uint4 qa = qd[0], qb = qd[1];
                     unsigned long long bestKey = ~0ull;                                    // dist << 32 | ordinal
                     unsigned ordinal = 0;
-                    walk_window(P, kc, rec_desc(recC, P.nf), gStart + (size_t)p * (kGC * kGR + 1), gIdx + (size_t)p * P.nf, qu, qv, radius,
-                                lo, hi, qa, qb, lane, [&](bool ok, int i2, int d) {
-                                    const unsigned long long m = __ballot(ok);
-                                    const unsigned pos = ordinal + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-                                    ordinal += (unsigned)__popcll(m);
-                                    if (ok) {
-                                        const int a = s_assign[i2];
-                                        if (a >= 0 && !(a & kNoBlock)) ok = false;
-                                        const float u2 = s_ur[i2];
-                                        if (u2 > 0) { const float er = fabsf(qur - u2); if (er > radius) ok = false; }
-                                    }
-                                    if (ok) {
-                                        const unsigned long long key2 = ((unsigned long long)(unsigned)d << 32) | (unsigned long long)pos;
-                                        if (key2 < bestKey) { bestKey = key2; bestIdx2 = i2; }
-                                    }
-                                });
+                    grid_walk(geom_of(P), kc, rec_desc(recC, P.nf), gStart + (size_t)p * (kGC * kGR + 1), gIdx + (size_t)p * P.nf, qu, qv, radius,
+                              lo, hi, qa, qb, lane, [&](bool ok, int i2, int d) {
+                                  const unsigned long long m = __ballot(ok);
+                                  const unsigned pos = ordinal + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+                                  ordinal += (unsigned)__popcll(m);
+                                  if (ok) {
+                                      const int a = s_assign[i2];
+                                      if (a >= 0 && !(a & kNoBlock)) ok = false;
+                                      const float u2 = s_ur[i2];
+                                      if (u2 > 0) { const float er = fabsf(qur - u2); if (er > radius) ok = false; }
+                                  }
+                                  if (ok) {
+                                      const unsigned long long key2 = ((unsigned long long)(unsigned)d << 32) | (unsigned long long)pos;
+                                      if (key2 < bestKey) { bestKey = key2; bestIdx2 = i2; }
+                                  }
+                              });
                     // lanes hold their own best (key, i2): reduce to the smallest key
                     unsigned hiK = (unsigned)(bestKey >> 32), loK = (unsigned)bestKey;
-                    const unsigned minHi = wave_min_u32_dpp(hiK);
+                    const unsigned minHi = wave_min_u32(hiK);
                     const unsigned loC = hiK == minHi ? loK : 0xffffffffu;
-                    const unsigned minLo = wave_min_u32_dpp(loC);
+                    const unsigned minLo = wave_min_u32(loC);
                     const unsigned long long who = __ballot(hiK == minHi && loK == minLo && bestKey != ~0ull);
                     if (who) { bestDist = (int)minHi; bestIdx2 = __builtin_amdgcn_readlane(bestIdx2, __ffsll((long long)who) - 1); }
                     else bestIdx2 = -1;
@@ -489,14 +390,7 @@ __global__ __launch_bounds__(64) void k_track_greedy(TrackParams P, const uint8_
                 key[m] = ok ? ((unsigned)d << 6) | (unsigned)pos : 0xffffffffu;
             }
 #pragma unroll
-            for (int m = 0; m < 4; m++) {             // minimum of each row of 16 lanes, in its lane 15
-                unsigned v = key[m], t;
-                t = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false); v = t < v ? t : v;
-                t = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false); v = t < v ? t : v;
-                t = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false); v = t < v ? t : v;
-                t = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false); v = t < v ? t : v;
-                key[m] = v;
-            }
+            for (int m = 0; m < 4; m++) key[m] = wave_row_min_u32(key[m]);   // minimum of each row of 16 lanes, in its lane 15
             // lane k < 16 collects query k's result (row k & 3 of pass k >> 2)
             const int src = 16 * (lane & 3) + 15, mSel = (lane >> 2) & 3;
             unsigned kq[4];
@@ -670,7 +564,7 @@ __global__ __launch_bounds__(256) void k_local_prepare(TrackParams P, const uint
     if (!rec_ok(P, ri) || offsets[f + 1] < offsets[f] || offsets[f] < 0) return;
     const uint8_t* recC = records + (size_t)ri * P.recBytes;
     const int nC = rec_count(recC, P.nf);
-    build_grid(P, rec_kps(recC), nC, gStart + (size_t)f * (kGC * kGR + 1), gIdx + (size_t)f * P.nf, cnt, part, blk, tid);
+    grid_build(geom_of(P), rec_kps(recC), nC, gStart + (size_t)f * (kGC * kGR + 1), gIdx + (size_t)f * P.nf, cnt, part, blk, tid);
 
     float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0}, Ow[3];
     if (poses) {
@@ -745,16 +639,16 @@ __global__ __launch_bounds__(256) void k_local_window(TrackParams P, const uint8
         const float* urC = rec_uright(recC, P.nf);
         const ivf_keypoint* kc = rec_kps(recC);
         unsigned* L = lists + ((size_t)f * maxM + m) * kListCap;
-        walk_window(P, kc, rec_desc(recC, P.nf), gStart + (size_t)f * (kGC * kGR + 1), gIdx + (size_t)f * P.nf,
-                    q.u, q.v, r, lv - 1, lv, qa, qb, lane, [&](bool ok, int i2, int d) {
-                        if (ok) { const float u2 = urC[i2]; if (u2 > 0) { const float er = fabsf(q.ur - u2); if (er > r) ok = false; } }   // :91-96
-                        const unsigned long long mk = __ballot(ok);
-                        if (ok) {
-                            const int pos = total + __popcll(mk & ((1ull << lane) - 1ull));
-                            if (pos < kListCap) L[pos] = (unsigned)i2 | ((unsigned)kc[i2].octave << 12) | ((unsigned)d << 16);
-                        }
-                        total += __popcll(mk);
-                    });
+        grid_walk(geom_of(P), kc, rec_desc(recC, P.nf), gStart + (size_t)f * (kGC * kGR + 1), gIdx + (size_t)f * P.nf,
+                  q.u, q.v, r, lv - 1, lv, qa, qb, lane, [&](bool ok, int i2, int d) {
+                      if (ok) { const float u2 = urC[i2]; if (u2 > 0) { const float er = fabsf(q.ur - u2); if (er > r) ok = false; } }   // :91-96
+                      const unsigned long long mk = __ballot(ok);
+                      if (ok) {
+                          const int pos = total + __popcll(mk & ((1ull << lane) - 1ull));
+                          if (pos < kListCap) L[pos] = (unsigned)i2 | ((unsigned)kc[i2].octave << 12) | ((unsigned)d << 16);
+                      }
+                      total += __popcll(mk);
+                  });
     }
     if (lane == 0) count[(size_t)f * maxM + m] = total;
 }
@@ -833,11 +727,11 @@ __global__ __launch_bounds__(64) void k_local_greedy(TrackParams P, const uint8_
                 const unsigned e = ent[k];
                 const bool ok = lane < cnt && !blocked((int)(e & 0xfff));
                 const unsigned key = ok ? ((e >> 16) << 12) | (unsigned)lane : 0xffffffffu;
-                kb = wave_min_u32_dpp(key);
+                kb = wave_min_u32(key);
                 if (kb != 0xffffffffu) {
                     const int bl = (int)(kb & 63);
                     eb = (unsigned)__builtin_amdgcn_readlane((int)e, bl);
-                    ks = wave_min_u32_dpp(lane == bl ? 0xffffffffu : key);
+                    ks = wave_min_u32(lane == bl ? 0xffffffffu : key);
                     if (ks != 0xffffffffu) es = (unsigned)__builtin_amdgcn_readlane((int)e, (int)(ks & 63));
                 }
             } else {
@@ -850,28 +744,28 @@ __global__ __launch_bounds__(64) void k_local_greedy(TrackParams P, const uint8_
                 const float* urC = rec_uright(recC, P.nf);
                 const ivf_keypoint* kc = rec_kps(recC);
                 unsigned ordinal = 0;
-                walk_window(P, kc, rec_desc(recC, P.nf), gStart + (size_t)f * (kGC * kGR + 1), gIdx + (size_t)f * P.nf, q.u, q.v, r,
-                            lv - 1, lv, qa, qb, lane, [&](bool ok, int i2, int d) {
-                                if (ok) { const float u2 = urC[i2]; if (u2 > 0) { const float er = fabsf(q.ur - u2); if (er > r) ok = false; } }
-                                const unsigned long long mk = __ballot(ok);
-                                const unsigned pos = ordinal + (unsigned)__popcll(mk & ((1ull << lane) - 1ull));
-                                ordinal += (unsigned)__popcll(mk);
-                                if (ok && blocked(i2)) ok = false;
-                                const unsigned e = ok ? ((unsigned)i2 | ((unsigned)kc[i2].octave << 12) | ((unsigned)d << 16)) : 0u;
-                                const unsigned key = ok ? ((unsigned)d << 12) | pos : 0xffffffffu;
-                                const unsigned k1 = wave_min_u32_dpp(key);
-                                if (k1 == 0xffffffffu) return;
-                                const unsigned long long w1 = __ballot(key == k1);
-                                const int l1 = __ffsll((long long)w1) - 1;
-                                const unsigned e1 = (unsigned)__builtin_amdgcn_readlane((int)e, l1);
-                                const unsigned k2 = wave_min_u32_dpp(lane == l1 ? 0xffffffffu : key);
-                                unsigned e2 = 0;
-                                if (k2 != 0xffffffffu) {
-                                    const unsigned long long w2 = __ballot(key == k2 && lane != l1);
-                                    e2 = (unsigned)__builtin_amdgcn_readlane((int)e, __ffsll((long long)w2) - 1);
-                                }
-                                merge_top2(kb, eb, ks, es, k1, e1, k2, e2);
-                            });
+                grid_walk(geom_of(P), kc, rec_desc(recC, P.nf), gStart + (size_t)f * (kGC * kGR + 1), gIdx + (size_t)f * P.nf, q.u, q.v, r,
+                          lv - 1, lv, qa, qb, lane, [&](bool ok, int i2, int d) {
+                              if (ok) { const float u2 = urC[i2]; if (u2 > 0) { const float er = fabsf(q.ur - u2); if (er > r) ok = false; } }
+                              const unsigned long long mk = __ballot(ok);
+                              const unsigned pos = ordinal + (unsigned)__popcll(mk & ((1ull << lane) - 1ull));
+                              ordinal += (unsigned)__popcll(mk);
+                              if (ok && blocked(i2)) ok = false;
+                              const unsigned e = ok ? ((unsigned)i2 | ((unsigned)kc[i2].octave << 12) | ((unsigned)d << 16)) : 0u;
+                              const unsigned key = ok ? ((unsigned)d << 12) | pos : 0xffffffffu;
+                              const unsigned k1 = wave_min_u32(key);
+                              if (k1 == 0xffffffffu) return;
+                              const unsigned long long w1 = __ballot(key == k1);
+                              const int l1 = __ffsll((long long)w1) - 1;
+                              const unsigned e1 = (unsigned)__builtin_amdgcn_readlane((int)e, l1);
+                              const unsigned k2 = wave_min_u32(lane == l1 ? 0xffffffffu : key);
+                              unsigned e2 = 0;
+                              if (k2 != 0xffffffffu) {
+                                  const unsigned long long w2 = __ballot(key == k2 && lane != l1);
+                                  e2 = (unsigned)__builtin_amdgcn_readlane((int)e, __ffsll((long long)w2) - 1);
+                              }
+                              merge_top2(kb, eb, ks, es, k1, e1, k2, e2);
+                          });
             }
             if (kb == 0xffffffffu) continue;
             const int bestDist = (int)(kb >> 12), bestIdx = (int)(eb & 0xfff), bestLevel = (int)((eb >> 12) & 15);
@@ -941,6 +835,7 @@ int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n
     if (n_items < 0 || n_items > t->cfg.max_pairs) return fail(IVF_E_INVALID, "%d frames / pairs outside [0,%d]", n_items, t->cfg.max_pairs);
     HIPCHK(hipSetDevice(t->cfg.device_id));
     if (t->ran) HIPCHK(hipStreamWaitEvent(st, t->evDone, 0));                          // the handle runs one call at a time
+    if (!v) return IVF_OK;                                                            // this file's own entry points read t->P themselves
     const TrackParams& P = t->P;
     v->nf = P.nf; v->nlevels = P.nlevels; v->maxPairs = t->cfg.max_pairs; v->recBytes = P.recBytes;
     v->fx = P.fx; v->fy = P.fy; v->cx = P.cx; v->cy = P.cy; v->invfx = P.invfx; v->invfy = P.invfy; v->bf = P.bf;
@@ -996,8 +891,8 @@ int ivf_tracker_create(const ivf_track_config* cfg, ivf_tracker** out)
     for (int l = 0; l < kMaxLevels; l++) P.scale[l] = l < cfg->nlevels ? cfg->scale_factors[l] : 1.0f;
     P.fx = cfg->fx; P.fy = cfg->fy; P.cx = cfg->cx; P.cy = cfg->cy; P.invfx = 1.0f / cfg->fx; P.invfy = 1.0f / cfg->fy;   // Frame.cc:203-204
     P.bf = cfg->bf; P.b = cfg->b;
-    P.minX = cfg->bounds.min_x; P.minY = cfg->bounds.min_y; P.maxX = cfg->bounds.max_x; P.maxY = cfg->bounds.max_y;
-    P.invW = (float)kGC / (P.maxX - P.minX); P.invH = (float)kGR / (P.maxY - P.minY);                                    // Frame.cc:208-209
+    const GridGeom G = grid_geom(cfg->bounds);
+    P.minX = G.minX; P.minY = G.minY; P.maxX = cfg->bounds.max_x; P.maxY = cfg->bounds.max_y; P.invW = G.invW; P.invH = G.invH;
     P.thDepth = cfg->th_depth; P.checkOri = cfg->check_orientation ? 1 : 0; P.defaultBlocks = cfg->points_block ? 1 : 0;
     P.recBytes = ivf_track_record_bytes(cfg->nfeatures);
     P.logScale = cfg->nlevels > 1 ? logf(cfg->scale_factors[1]) : 1.0f;             // mfLogScaleFactor = log(mfScaleFactor) (Frame.cc:106): logf
@@ -1027,20 +922,17 @@ int ivf_tracker_run(ivf_tracker* t, const uint8_t* d_records, size_t record_byte
                     int32_t* d_assign, int32_t* d_nmatches, void* hip_stream)
 {
     if (!t || !d_records || !d_pairs || !d_assign || !d_nmatches) return fail(IVF_E_INVALID, "null argument");
-    if (record_bytes != t->P.recBytes) return fail(IVF_E_INVALID, "record_bytes %zu: records of %d features are %zu bytes", record_bytes, t->P.nf, t->P.recBytes);
     if (((size_t)d_records & 15) != 0) return fail(IVF_E_INVALID, "the record block must be 16-byte aligned");
-    if (n_records < 1) return fail(IVF_E_INVALID, "n_records must be >= 1");
     if (n_pairs == 0) return IVF_OK;
-    if (n_pairs < 0 || n_pairs > t->cfg.max_pairs) return fail(IVF_E_INVALID, "n_pairs %d outside [0,%d]", n_pairs, t->cfg.max_pairs);
-    HIPCHK(hipSetDevice(t->cfg.device_id));
     if ((d_point_quality == nullptr) != (d_key_quality == nullptr)) return fail(IVF_E_INVALID, "d_point_quality and d_key_quality come together");
     hipStream_t st = (hipStream_t)hip_stream;
+    // the per-pair grids, query tables and candidate lists are scratch of the HANDLE: a run enqueued on another stream than the
+    // previous one queues behind it (use one tracker per stream to let runs overlap)
+    const int rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st, nullptr);
+    if (rc != IVF_OK) return rc;
     TrackParams P = t->P;
     P.nRecords = n_records;
     const int2* pairs = (const int2*)d_pairs;
-    // the per-pair grids, query tables and candidate lists are scratch of the HANDLE: a run enqueued on another stream than the
-    // previous one queues behind it (use one tracker per stream to let runs overlap)
-    if (t->ran) HIPCHK(hipStreamWaitEvent(st, t->evDone, 0));
     hipLaunchKernelGGL(k_track_prepare, dim3(n_pairs), dim3(256), 0, st, P, d_records, pairs, d_poses, d_point_flags, t->dStart, t->dIdx, t->dQ, t->dRetry);
     const dim3 wg((P.nf + 3) / 4, n_pairs);
     for (int pass = 0; pass < (t->cfg.retry_below > 0 ? 2 : 1); pass++) {
@@ -1049,10 +941,7 @@ int ivf_tracker_run(ivf_tracker* t, const uint8_t* d_records, size_t record_byte
         hipLaunchKernelGGL(k_track_greedy, dim3(n_pairs), dim3(64), t->ldsBytes, st, P, d_records, pairs, t->dStart, t->dIdx, t->dQ, th, t->dRetry, pass,
                            t->cfg.retry_below, t->dCount, t->dLists, d_point_quality, d_key_quality, d_assign, d_nmatches);
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(t->evDone, st));
-    t->ran = true;
-    return IVF_OK;
+    return tracker_end(t, st);
 }
 
 int ivf_tracker_search_local(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_frames, int n_frames,
@@ -1061,17 +950,14 @@ int ivf_tracker_search_local(ivf_tracker* t, const uint8_t* d_records, size_t re
                              int32_t* d_assign, int32_t* d_nmatches, void* hip_stream)
 {
     if (!t || !d_records || !d_frames || !d_points || !d_point_offsets || !d_assign || !d_nmatches) return fail(IVF_E_INVALID, "null argument");
-    if (record_bytes != t->P.recBytes) return fail(IVF_E_INVALID, "record_bytes %zu: records of %d features are %zu bytes", record_bytes, t->P.nf, t->P.recBytes);
     if (((size_t)d_records & 15) != 0 || ((size_t)d_points & 15) != 0) return fail(IVF_E_INVALID, "the record block and the point array must be 16-byte aligned");
-    if (n_records < 1) return fail(IVF_E_INVALID, "n_records must be >= 1");
     if (n_frames == 0) return IVF_OK;
-    if (n_frames < 0 || n_frames > t->cfg.max_pairs) return fail(IVF_E_INVALID, "n_frames %d outside [0,%d]", n_frames, t->cfg.max_pairs);
     if (max_points_per_frame < 1 || max_points_per_frame >= kLocalNoBlock) return fail(IVF_E_INVALID, "max_points_per_frame %d out of range", max_points_per_frame);
     if (!(th > 0) || !(nn_ratio > 0)) return fail(IVF_E_INVALID, "th and nn_ratio must be positive");
     if ((d_point_quality == nullptr) != (d_key_quality == nullptr)) return fail(IVF_E_INVALID, "d_point_quality and d_key_quality come together");
-    HIPCHK(hipSetDevice(t->cfg.device_id));
     hipStream_t st = (hipStream_t)hip_stream;
-    if (t->ran) HIPCHK(hipStreamWaitEvent(st, t->evDone, 0));                          // the handle's scratch belongs to one call at a time
+    const int rc = tracker_begin(t, true, record_bytes, n_records, n_frames, st, nullptr);
+    if (rc != IVF_OK) return rc;
     if (max_points_per_frame > t->localCap) {
         // grow the scratch: the previous call (if any) must be done with the old buffers before they are freed
         if (t->ran) HIPCHK(hipEventSynchronize(t->evDone));
@@ -1098,10 +984,7 @@ int ivf_tracker_search_local(ivf_tracker* t, const uint8_t* d_records, size_t re
     hipLaunchKernelGGL(k_local_greedy, dim3(n_frames), dim3(64), (size_t)P.nf * 4, st, P, d_records, d_frames, d_points, d_point_offsets, M,
                        t->dStart, t->dIdx, t->dLQ, t->dLRad, d_occupied, nn_ratio, t->dLCount, t->dLLists, d_point_quality, d_key_quality,
                        d_assign, d_nmatches);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(t->evDone, st));
-    t->ran = true;
-    return IVF_OK;
+    return tracker_end(t, st);
 }
 
 }  // extern "C"

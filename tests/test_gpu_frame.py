@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from iv_slam_amd import synth
+from iv_slam_amd import KP_DTYPE, synth
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,6 +63,37 @@ def test_grid_built_on_device(iv):
     f = iv.DeviceFrame(kps[:0], desc[:0], uright[:0], bounds)
     st, ix = f.grid()
     assert not st.any() and len(ix) == 0
+
+
+def _big_grid_case(n=70000, seed=21):
+    """n synthetic keypoints inside (0, 0, 1242, 375), 52 of them outside the bounds (as are those that round to column 64 / row 48)
+    and 600 in ONE grid cell, spread over the whole index range: that bucket spans several 256-blocks and holds several average buckets' worth of rank"""
+    bounds = (0.0, 0.0, 1242.0, 375.0)
+    rng = np.random.default_rng(seed)
+    kps = np.zeros(n, KP_DTYPE)
+    kps["x"] = rng.uniform(0.0, 1242.0, n); kps["y"] = rng.uniform(0.0, 375.0, n)
+    kps["size"] = 31.0; kps["octave"] = rng.integers(0, 8, n)
+    one = np.linspace(0, n - 1, 600).astype(np.int64)                                # first and last keypoint included
+    kps["x"][one] = 20 * (1242.0 / 64) + rng.uniform(-3.0, 3.0, 600)                 # cell (20, 10): 19.4 x 7.8 px around its centre
+    kps["y"][one] = 10 * (375.0 / 48) + rng.uniform(-2.0, 2.0, 600)
+    out = rng.choice(np.setdiff1d(np.arange(n), one), 52, replace=False)
+    kps["x"][out[:13]] = rng.uniform(-60.0, -15.0, 13); kps["x"][out[13:26]] = rng.uniform(1255.0, 1300.0, 13)
+    kps["y"][out[26:39]] = rng.uniform(-40.0, -6.0, 13); kps["y"][out[39:]] = rng.uniform(381.0, 420.0, 13)
+    desc = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    return kps, desc, np.full(n, -1.0, np.float32), bounds, one, out
+
+
+def test_grid_of_70000_keypoints_keeps_int_indices(iv):
+    """The grid's index type is a template parameter (int here, unsigned short in the tracker): 70 000 is the smallest round size
+    above 65 535, where an int instantiation narrowed to 16 bits wraps.  No extractor: synthetic keypoints, one workgroup."""
+    kps, desc, uright, bounds, one, out = _big_grid_case()
+    es, ei = _np_grid(kps, bounds)
+    c = 20 * 48 + 10
+    assert np.isin(one, ei[es[c]:es[c + 1]]).all() and es[-1] <= len(kps) - len(out) and ei.max() == len(kps) - 1   # the input is as described
+    f = iv.DeviceFrame(kps, desc, uright, bounds)
+    st, ix = f.grid()
+    assert len(ix) == len(kps)                                                       # cell_index has n slots; the grid fills the first start[-1]
+    assert np.array_equal(st, es) and np.array_equal(ix[:es[-1]], ei)
 
 
 def test_search_by_projection_on_resident_frame(iv):
