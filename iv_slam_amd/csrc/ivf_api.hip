@@ -85,6 +85,10 @@ int make_tables(const ivf_extractor_params& p, Tables& t)
     return IVF_OK;
 }
 
+// One set of input planes, as the caller holds it: image i of the set at p + i * imageStride, rows rowStride bytes apart.
+// code 0 = grey, 1 / 2 (| 4) = B,G,R / R,G,B interleaved (IVF_COLOR_*: k_ingest_color converts)
+struct ImageSrc { const uint8_t* p; size_t imageStride; int rowStride; int code; };
+
 // ---- one batch context: geometry + device buffers for a fixed (params, image size, capacity) ----
 struct Context {
     int device = 0, maxImg = 0, nSides = 1;
@@ -94,6 +98,7 @@ struct Context {
     Config* dc = nullptr;
     ResizeCoef* dTab = nullptr;           // packed cv::resize coefficients, all levels
     Buffers b{};
+    std::vector<void*> owned;           // every device allocation of the context (alloc): release() frees these
     uint8_t* dStage = nullptr;          // single-image host API staging (image + cost)
     uint8_t* hStage = nullptr;          // ... and its pinned host twin (+ room for the keypoints / descriptors coming back)
     size_t stageBytes = 0;
@@ -107,17 +112,23 @@ struct Context {
     hipEvent_t evFork = nullptr, evJoin = nullptr;
     long long nRuns = 0;
     int markOwn = -1, markSide = -1;    // progress words of this context's stream / of the stream its blur is lent (experiment builds: IVF_MARK)
-    hipStream_t lastStream = nullptr;
 
     int build(const Tables& t, int w, int h, int maxImages, int sides, int dev, bool withStereo, const int* variant = nullptr);
     int set_variant(const int* variant);
     void release();
-    int run(const uint8_t* s0, const uint8_t* s1, const uint8_t* cost, size_t imageStride, int rowStride,
-            size_t costStride, int costRowStride, int nImg, const uint8_t* hUseCost, hipStream_t st,
-            hipEvent_t inputsConsumed = nullptr, hipStream_t sideStream = nullptr);
-    // r06: per-side source override of the NEXT run (ivf_frontend_run_color): code 0 = grey with its own strides, 1 / 2 (| 4) = B,G,R / R,G,B interleaved
-    // (k_ingest_color).  Consumed by run().
-    struct SideSrc { const uint8_t* src = nullptr; size_t imageStride = 0; int rowStride = 0; int code = 0; } sideSrc[2];
+    // one hipMalloc the context owns from here on; zero: cleared (blocking) as well
+    template <class T> hipError_t alloc(T*& p, size_t bytes, bool zero = false)
+    {
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) return e;
+        owned.push_back(p);
+        return zero ? hipMemset(p, 0, bytes) : hipSuccess;
+    }
+    int ensure_qpyr(hipStream_t st);
+    // side[sd]: the images of side sd (one side: side[0]); cost: the cost maps, or null.  perSide: one ingest launch per side even where
+    // one launch could serve both (grey sides that share their strides) -- ivf_frontend_run_color, which has always ingested side by side
+    int run(const ImageSrc (&side)[2], const ImageSrc* cost, int nImg, const uint8_t* dUseCostSrc, hipStream_t st,
+            hipEvent_t inputsConsumed = nullptr, hipStream_t sideStream = nullptr, bool perSide = false);
     int check_status(int which = 0);
 };
 
@@ -224,62 +235,54 @@ int Context::build(const Tables& t, int w, int h, int maxImages, int sides, int 
     if (tab.empty()) tab.push_back(0);
 
     HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc(&dc, sizeof(Config)));
+    HIPCHK(alloc(dc, sizeof(Config)));
     HIPCHK(hipMemcpy(dc, &hc, sizeof(Config), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&dTab, tab.size() * sizeof(ResizeCoef)));
+    HIPCHK(alloc(dTab, tab.size() * sizeof(ResizeCoef)));
     HIPCHK(hipMemcpy(dTab, tab.data(), tab.size() * sizeof(ResizeCoef), hipMemcpyHostToDevice));
     const size_t nI = (size_t)maxImg, nf = (size_t)c.nfeatures, blob = (size_t)c.pyrBytes * nI;
-    HIPCHK(hipMalloc(&b.pyr, blob + 256));          // + slack: k_stereo_match / k_describe read whole dwords that may end a few bytes past a plane's last row
-    HIPCHK(hipMalloc(&b.blur, blob + 256));
+    HIPCHK(alloc(b.pyr, blob + 256));               // + slack: k_stereo_match / k_describe read whole dwords that may end a few bytes past a plane's last row
+    HIPCHK(alloc(b.blur, blob + 256));
     HIPCHK(hipMemset(b.pyr, 0, blob));
-    if (introspection) { HIPCHK(hipMalloc(&b.qpyr, blob)); HIPCHK(hipMemset(b.qpyr, 0, blob)); }
-    HIPCHK(hipMalloc(&b.tileList, nI * std::max(c.nTiles, 1) * (size_t)kTileCap * sizeof(unsigned)));
-    HIPCHK(hipMalloc(&b.tileCnt, nI * std::max(c.nTiles, 1) * sizeof(int)));
-    HIPCHK(hipMalloc(&b.cellCnt, nI * c.nCellsTotal * 2 * sizeof(int)));
-    HIPCHK(hipMalloc(&b.cellInfo, nI * c.nCellsTotal * sizeof(int4)));
-    HIPCHK(hipMalloc(&b.lvlTotal, nI * kMaxLevels * sizeof(int)));
-    HIPCHK(hipMalloc(&b.lvl, nI * c.candTotal * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&b.slotPos, nI * nf * sizeof(unsigned)));
-    HIPCHK(hipMalloc(&b.slotResp, nI * nf * sizeof(float)));
-    HIPCHK(hipMalloc(&b.lvlCount, nI * kMaxLevels * sizeof(int)));
-    HIPCHK(hipMemset(b.lvlCount, 0, nI * kMaxLevels * sizeof(int)));
-    HIPCHK(hipMalloc(&b.useCost, (nI + 3) & ~(size_t)3));                // whole dwords: the kernels read the flags with scalar dword loads
-    HIPCHK(hipMemset(b.useCost, 0, (nI + 3) & ~(size_t)3));
-    HIPCHK(hipMalloc(&b.kps, nI * nf * sizeof(ivf_keypoint)));
-    HIPCHK(hipMalloc(&b.desc, nI * nf * 32));
-    HIPCHK(hipMalloc(&b.count, nI * sizeof(int)));
-    HIPCHK(hipMemset(b.count, 0, nI * sizeof(int)));
-    HIPCHK(hipMalloc(&b.quality, nI * nf * sizeof(float)));
+    if (introspection) HIPCHK(alloc(b.qpyr, blob, true));
+    HIPCHK(alloc(b.tileList, nI * std::max(c.nTiles, 1) * (size_t)kTileCap * sizeof(unsigned)));
+    HIPCHK(alloc(b.tileCnt, nI * std::max(c.nTiles, 1) * sizeof(int)));
+    HIPCHK(alloc(b.cellCnt, nI * c.nCellsTotal * 2 * sizeof(int)));
+    HIPCHK(alloc(b.cellInfo, nI * c.nCellsTotal * sizeof(int4)));
+    HIPCHK(alloc(b.lvlTotal, nI * kMaxLevels * sizeof(int)));
+    HIPCHK(alloc(b.lvl, nI * c.candTotal * sizeof(unsigned long long)));
+    HIPCHK(alloc(b.slotPos, nI * nf * sizeof(unsigned)));
+    HIPCHK(alloc(b.slotResp, nI * nf * sizeof(float)));
+    HIPCHK(alloc(b.lvlCount, nI * kMaxLevels * sizeof(int), true));
+    HIPCHK(alloc(b.useCost, (nI + 3) & ~(size_t)3, true));               // whole dwords: the kernels read the flags with scalar dword loads
+    HIPCHK(alloc(b.kps, nI * nf * sizeof(ivf_keypoint)));
+    HIPCHK(alloc(b.desc, nI * nf * 32));
+    HIPCHK(alloc(b.count, nI * sizeof(int), true));
+    HIPCHK(alloc(b.quality, nI * nf * sizeof(float)));
     if (withStereo) {
         const size_t nP = std::max<size_t>(nI / 2, 1);
-        HIPCHK(hipMalloc(&b.uright, nP * nf * sizeof(float)));
-        HIPCHK(hipMalloc(&b.depth, nP * nf * sizeof(float)));
-        HIPCHK(hipMalloc(&b.sad, nP * nf * sizeof(int)));
-        HIPCHK(hipMalloc(&b.rowCnt, nP * (size_t)h * sizeof(int)));
-        HIPCHK(hipMalloc(&b.rowList, nP * (size_t)h * kRowCap * sizeof(unsigned short)));
+        HIPCHK(alloc(b.uright, nP * nf * sizeof(float)));
+        HIPCHK(alloc(b.depth, nP * nf * sizeof(float)));
+        HIPCHK(alloc(b.sad, nP * nf * sizeof(int)));
+        HIPCHK(alloc(b.rowCnt, nP * (size_t)h * sizeof(int)));
+        HIPCHK(alloc(b.rowList, nP * (size_t)h * kRowCap * sizeof(unsigned short)));
     }
-    HIPCHK(hipMalloc(&b.status, 4 * sizeof(int)));
-    HIPCHK(hipMemset(b.status, 0, 4 * sizeof(int)));
+    HIPCHK(alloc(b.status, 4 * sizeof(int), true));
     b.hugeCount = b.status + 1;
-    HIPCHK(hipMalloc(&b.tierList, 2 * nI * (size_t)c.nCellsTotal * sizeof(int)));
+    HIPCHK(alloc(b.tierList, 2 * nI * (size_t)c.nCellsTotal * sizeof(int)));
     if (c.maxCandCap > 4096) {          // kCellCapBig: cells of this geometry can outgrow the LDS selection paths
-        HIPCHK(hipMalloc(&b.hugeList, (size_t)kHugeListCap * sizeof(int)));
-        HIPCHK(hipMalloc(&b.hugeScratch, (size_t)kHugeSlots * 6 * c.maxCandCap * sizeof(unsigned)));
+        HIPCHK(alloc(b.hugeList, (size_t)kHugeListCap * sizeof(int)));
+        HIPCHK(alloc(b.hugeScratch, (size_t)kHugeSlots * 6 * c.maxCandCap * sizeof(unsigned)));
     }
     for (int i = 0; i < kEvRing; i++) { HIPCHK(hipEventCreate(&evFast0[i])); HIPCHK(hipEventCreate(&evFast1[i])); }
-    {
-        HIPCHK(hipEventCreateWithFlags(&evFork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&evJoin, hipEventDisableTiming));
-    }
+    HIPCHK(hipEventCreateWithFlags(&evFork, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&evJoin, hipEventDisableTiming));
     return IVF_OK;
 }
 
 void Context::release()
 {
     (void)hipSetDevice(device);
-    void* ptrs[] = {dc, dTab, b.pyr, b.qpyr, b.blur, b.tileList, b.tileCnt, b.cellCnt, b.cellInfo, b.lvlTotal, b.lvl, b.slotPos, b.slotResp, b.lvlCount,
-                    b.useCost, b.kps, b.desc, b.count, b.quality, b.uright, b.depth, b.sad, b.rowCnt, b.rowList, b.status, b.hugeList, b.hugeScratch, b.tierList, dStage};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    for (void* p : owned) (void)hipFree(p);
     if (hStage) (void)hipHostFree(hStage);
     for (int i = 0; i < kEvRing; i++) {
         if (evFast0[i]) (void)hipEventDestroy(evFast0[i]);
@@ -290,39 +293,42 @@ void Context::release()
     *this = Context();
 }
 
+// The cost blob of an extractor that ignores the map (enableIntrospection = 0): mvKeyQualScore still reads level 0 of a cost image that comes
+// with the frame (Frame.cc:130-143).  Allocated by the first call that needs it; cleared in order on `st`, or blocking when st is null.
+int Context::ensure_qpyr(hipStream_t st)
+{
+    if (b.qpyr) return IVF_OK;
+    const size_t blob = (size_t)hc.pyrBytes * maxImg;
+    HIPCHK(alloc(b.qpyr, blob));
+    if (st) HIPCHK(hipMemsetAsync(b.qpyr, 0, blob, st));
+    else HIPCHK(hipMemset(b.qpyr, 0, blob));
+    return IVF_OK;
+}
+
 // Enqueue ORBextractor::operator() for nImg images (ORB/src/ORBextractor.cc:1224-1296)
-int Context::run(const uint8_t* s0, const uint8_t* s1, const uint8_t* cost, size_t imageStride, int rowStride,
-                 size_t costStride, int costRowStride, int nImg, const uint8_t* dUseCostSrc, hipStream_t st,
-                 hipEvent_t inputsConsumed, hipStream_t sideStream)
+int Context::run(const ImageSrc (&side)[2], const ImageSrc* cost, int nImg, const uint8_t* dUseCostSrc, hipStream_t st,
+                 hipEvent_t inputsConsumed, hipStream_t sideStream, bool perSide)
 {
     if (nImg < 1 || nImg > maxImg) return fail(IVF_E_INVALID, "batch of %d images outside [1,%d]", nImg, maxImg);
     HIPCHK(hipSetDevice(device));
-    lastStream = st;
     const bool useQ = introspection && cost != nullptr;
     if (needsCost && !useQ)
         return fail(IVF_E_GEOMETRY, "cell rows leave a pyramid level: this geometry is defined only with a cost map (stale hY, ORBextractor.cc:935-999)");
-    if (cost && !b.qpyr) {
-        // a cost image with an extractor that ignores it (enableIntrospection = 0): mvKeyQualScore still reads it
-        // (Frame.cc:130-143), so its level 0 is ingested.  One-time allocation, on the first such call.
-        const size_t blob = (size_t)hc.pyrBytes * maxImg;
-        HIPCHK(hipMalloc(&b.qpyr, blob));
-        HIPCHK(hipMemsetAsync(b.qpyr, 0, blob, st));
-    }
+    if (const int rc = cost ? ensure_qpyr(st) : IVF_OK) return rc;
     if (cost) HIPCHK(hipMemcpyAsync(b.useCost, dUseCostSrc, nImg, hipMemcpyDeviceToDevice, st));
     else HIPCHK(hipMemsetAsync(b.useCost, 0, nImg, st));
-    if (sideSrc[0].src || sideSrc[1].src) {
+    const ImageSrc &s0 = side[0], &s1 = side[nSides - 1];
+    if (!perSide && !(s0.code & 3) && !(s1.code & 3) && s0.imageStride == s1.imageStride && s0.rowStride == s1.rowStride)
+        launch_ingest(hc, dc, s0.p, s1.p, s0.imageStride, s0.rowStride, nImg, nSides, b.pyr, nullptr, st);
+    else
         for (int sd = 0; sd < nSides; sd++) {
-            const SideSrc& q = sideSrc[sd];
-            if (q.src && (q.code & 3)) launch_ingest_color(hc, dc, q.src, q.imageStride, q.rowStride, q.code, nImg, nSides, sd, b.pyr, st);
-            else if (q.src) launch_ingest(hc, dc, b, q.src, q.src, q.imageStride, q.rowStride, nImg, nSides, b.pyr, st, 1 << sd);
-            else launch_ingest(hc, dc, b, s0, s1, imageStride, rowStride, nImg, nSides, b.pyr, st, 1 << sd);
+            const ImageSrc& q = side[sd];
+            if (q.code & 3) launch_ingest_color(hc, dc, q.p, q.imageStride, q.rowStride, q.code, nImg, nSides, sd, b.pyr, st);
+            else launch_ingest(hc, dc, q.p, q.p, q.imageStride, q.rowStride, nImg, nSides, b.pyr, nullptr, st, 1 << sd);
         }
-        sideSrc[0] = SideSrc(); sideSrc[1] = SideSrc();
-    } else
-    launch_ingest(hc, dc, b, s0, s1, imageStride, rowStride, nImg, nSides, b.pyr, st);
     // r06: a cost map that already sits in the level-0 cost plane (ivf_frontend_cost_plane: the FCN wrote it there) needs no copy
-    const bool costInPlace = cost && b.qpyr && cost == b.qpyr + hc.lv[0].off && costStride == (size_t)nSides * hc.pyrBytes && costRowStride == hc.lv[0].pitch;
-    if (cost && !costInPlace) launch_ingest(hc, dc, b, cost, cost, costStride, costRowStride, nImg, nSides, b.qpyr, st);
+    const bool costInPlace = cost && cost->p == b.qpyr + hc.lv[0].off && cost->imageStride == (size_t)nSides * hc.pyrBytes && cost->rowStride == hc.lv[0].pitch;
+    if (cost && !costInPlace) launch_ingest(hc, dc, cost->p, cost->p, cost->imageStride, cost->rowStride, nImg, nSides, b.qpyr, b.useCost, st);
     if (inputsConsumed) HIPCHK(hipEventRecord(inputsConsumed, st));   // caller buffers are free from here on
     IVF_MARK(st, markOwn, 1, nRuns);
     launch_pyramid(hc, dc, dTab, b.pyr, useQ ? b.qpyr : nullptr, b.useCost, nImg, st);   // + ComputeQualityImagePyramid :1325-1357
@@ -334,27 +340,25 @@ int Context::run(const uint8_t* s0, const uint8_t* s1, const uint8_t* cost, size
     launch_fast(hc, dc, b, nImg, st);
     HIPCHK(hipEventRecord(evFast1[slot], st));
     IVF_MARK(st, markOwn, 3, nRuns);
-    const long long thisRun = nRuns;
+    const long long thisRun = nRuns++;
     (void)thisRun;
-    nRuns++;
     static const bool sideBlur = getenv("IVF_NO_SIDE_BLUR") == nullptr;
-    hipStream_t side = sideStream;
-    if (sideBlur && side && side != st && nImg > 2) {       // not for single frames: there the two event hand-overs cost more than the overlap gives (extraction 0.35 -> 0.63 ms)
+    if (sideBlur && sideStream && sideStream != st && nImg > 2) {       // not for single frames: there the two event hand-overs cost more than the overlap gives (extraction 0.35 -> 0.63 ms)
         // fork: the blur only needs the pyramid (in order behind it on st); the next run's blur cannot overtake this run's descriptors,
         // because its fork event is recorded on st behind them
         HIPCHK(hipEventRecord(evFork, st));
-        HIPCHK(hipStreamWaitEvent(side, evFork, 0));
-        IVF_MARK(side, markSide, 1, thisRun);
-        launch_blur(hc, dc, b, nImg, side, false);
-        IVF_MARK(side, markSide, 2, thisRun);
+        HIPCHK(hipStreamWaitEvent(sideStream, evFork, 0));
+        IVF_MARK(sideStream, markSide, 1, thisRun);
+        launch_blur(hc, dc, b, nImg, sideStream, false);
+        IVF_MARK(sideStream, markSide, 2, thisRun);
         // whatever fails from here on, the owning stream joins the side stream's work before this call returns: an un-joined blur
         // would still be writing b.blur when the context is reused or released
-        const hipError_t eRec = hipEventRecord(evJoin, side);
+        const hipError_t eRec = hipEventRecord(evJoin, sideStream);
         if (eRec == hipSuccess) launch_select(hc, dc, b, nImg, st);
         IVF_MARK(st, markOwn, 4, thisRun);
         const hipError_t eWait = eRec == hipSuccess ? hipStreamWaitEvent(st, evJoin, 0) : eRec;
         if (eWait != hipSuccess) {
-            (void)hipStreamSynchronize(side);
+            (void)hipStreamSynchronize(sideStream);
             return fail(IVF_E_NO_DEVICE, "joining the side-stream blur failed: %s", hipGetErrorString(eWait));
         }
         IVF_MARK(st, markOwn, 5, thisRun);
@@ -364,7 +368,7 @@ int Context::run(const uint8_t* s0, const uint8_t* s1, const uint8_t* cost, size
         launch_blur(hc, dc, b, nImg, st, true);
         IVF_MARK(st, markOwn, 5, thisRun);
     }
-    launch_describe(hc, dc, b, nullptr, 0, 0, nImg, nSides, st);
+    launch_describe(hc, dc, b, nImg, st);
     IVF_MARK(st, markOwn, 6, thisRun);
     HIPCHK(hipGetLastError());
     return IVF_OK;
@@ -495,17 +499,41 @@ struct ivf_frontend {
     hipStream_t stream[kPipe] = {};
     hipEvent_t evIn[kPipe] = {}, evConsumed[kPipe] = {}, evDone[kPipe] = {};
     uint8_t* dFlags = nullptr;          // useCost flags when a cost batch is given: [L,R,L,R,...]
-    int lastPairs = 0;
     int pairsOf[kPipe] = {};            // batch size of the run each context holds
     long long runs = 0;
     // Frame::UndistortKeyPoints inside the batch (ivf_frontend_set_camera): mvKeysUn of the left frames, one buffer per context
     bool camOn = false;                 // an undistorting camera is set: runs from now on fill kpsUn of their context
     ivf::UndistortCam cam{};
     ivf_keypoint* kpsUn[kPipe] = {};    // addressed like Buffers::kps ([2 * max_pairs][nfeatures], the left frame of pair p at 2 * p: the odd frames are
-                                        // never written), so that every consumer of b.kps -- k_pack_gather -- runs unchanged; allocated by the first undistorting camera
+                                        // never written), so that every consumer of b.kps -- k_pack_gather -- runs unchanged; allocated by the first undistorting camera, owned by ctx[k]
     bool unOf[kPipe] = {};              // the run each context holds was made with a camera
     int last() const { return (int)((runs + kPipe - 1) % kPipe); }      // context of the most recent run
 };
+
+// context *k of the batch `age` runs back (0 = the last run; a batch is held until kPipe - 1 further runs were enqueued)
+static int held_batch(const ivf_frontend* fe, int age, int* k)
+{
+    if (age < 0 || age >= kPipe || fe->runs <= age) return fail(IVF_E_STATE, "no batch of age %d is held", age);
+    *k = (int)((fe->runs - 1 - age) % kPipe);
+    return IVF_OK;
+}
+
+// Image (pair, side) of the batch context k holds: images are interleaved [L0,R0,L1,R1,...], the stereo results are per pair and belong
+// to the left image.  kps is what a Frame reads, mvKeysUn (Frame.cc:424): kpsUn for the left image of a run made with a camera, else mvKeys.
+static BatchImage batch_image(const ivf_frontend* fe, int k, int pair, int side)
+{
+    const Buffers& b = fe->ctx[k].b;
+    const size_t nf = fe->ctx[k].hc.nfeatures, img = (size_t)pair * 2 + side;
+    BatchImage im;
+    im.mvKeys = b.kps + img * nf;
+    im.kps = (side == 0 && fe->unOf[k]) ? fe->kpsUn[k] + img * nf : im.mvKeys;
+    im.desc = b.desc + img * nf * 32;
+    im.uright = side == 0 ? b.uright + (size_t)pair * nf : nullptr;
+    im.depth = side == 0 ? b.depth + (size_t)pair * nf : nullptr;
+    im.quality = b.quality + img * nf;
+    im.count = b.count + img; im.cap = (int)nf; im.done = fe->evDone[k];
+    return im;
+}
 
 extern "C" {
 
@@ -597,7 +625,7 @@ int ivf_extract(ivf_extractor* e, const uint8_t* image, int width, int height, i
         if (rc) { e->ctx.release(); return rc; }
         // staging is part of the context: the handle only counts as built once all of it exists (release() frees what does)
         e->ctx.stageBytes = ((size_t)width * height * 2 + 15) & ~(size_t)15;       // keypoints / counters behind it stay 16-byte aligned
-        if (hipMalloc(&e->ctx.dStage, e->ctx.stageBytes) != hipSuccess ||
+        if (e->ctx.alloc(e->ctx.dStage, e->ctx.stageBytes) != hipSuccess ||
             hipHostMalloc((void**)&e->ctx.hStage, e->ctx.stageBytes + (size_t)e->t.p.nfeatures * (sizeof(ivf_keypoint) + 32) + 64, hipHostMallocDefault) != hipSuccess ||
             (!e->dOne && (hipMalloc(&e->dOne, 1) != hipSuccess || hipMemset(e->dOne, 1, 1) != hipSuccess)) ||
             (!e->st && hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking) != hipSuccess)) {
@@ -624,7 +652,8 @@ int ivf_extract(ivf_extractor* e, const uint8_t* image, int width, int height, i
     // that failed half-way must not still be in flight then (the stream is non-blocking: the NULL stream does not order it)
     struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{e->st};
     HIPCHK(hipMemcpyAsync(dImg, hImg, useCost ? 2 * px : px, hipMemcpyHostToDevice, e->st));
-    rc = c.run(dImg, dImg, useCost ? dCost : nullptr, px, width, px, width, 1, e->dOne, e->st);
+    const ImageSrc img{dImg, px, width, 0}, costSrc{dCost, px, width, 0};
+    rc = c.run({img, img}, useCost ? &costSrc : nullptr, 1, e->dOne, e->st);
     if (rc) return rc;
     // counts are not known before the kernels finish: fetch the count and the full-capacity result arrays in one go (56 KB at N = 1000)
     HIPCHK(hipMemcpyAsync(hN, c.b.count, sizeof(int), hipMemcpyDeviceToHost, e->st));
@@ -917,7 +946,6 @@ void ivf_frontend_destroy(ivf_frontend* fe)
         if (fe->evDone[k]) (void)hipEventSynchronize(fe->evDone[k]);      // never recorded = complete
     if (fe->dFlags) (void)hipFree(fe->dFlags);
     for (int k = 0; k < kPipe; k++) {
-        if (fe->kpsUn[k]) (void)hipFree(fe->kpsUn[k]);
         fe->ctx[k].release();
         // fe->stream[k] belongs to the process-wide pool: never destroyed
         if (fe->evIn[k]) (void)hipEventDestroy(fe->evIn[k]);
@@ -927,8 +955,38 @@ void ivf_frontend_destroy(ivf_frontend* fe)
     delete fe;
 }
 
-static int frontend_run_common(ivf_frontend* fe, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_cost,
-                               size_t image_stride, int row_stride, int n_pairs, void* hip_stream, const Context::SideSrc* sides);
+// One batch on the next context: side[0 / 1] the left / right images, cost the cost maps or null (Context::run)
+static int frontend_run(ivf_frontend* fe, const ImageSrc (&side)[2], const ImageSrc* cost, int n_pairs, void* hip_stream, bool perSide)
+{
+    hipStream_t caller = (hipStream_t)hip_stream;
+    const int k = (int)(fe->runs % kPipe);
+    Context& c = fe->ctx[k];
+    hipStream_t st = fe->stream[k];
+    HIPCHK(hipSetDevice(fe->cfg.device_id));
+    // order: everything the caller enqueued so far (it produced the inputs) -> this batch
+    IVF_MARK_HOST(6, (fe->runs << 8) | 1);
+    HIPCHK(hipEventRecord(fe->evIn[k], caller));
+    HIPCHK(hipStreamWaitEvent(st, fe->evIn[k], 0));
+    // the blur of this batch is lent the internal stream of the NEXT context: whatever older batch that stream still holds does not
+    // depend on this one, and the next batch queues behind the blur
+    int rc = c.run(side, cost, 2 * n_pairs, fe->dFlags, st, fe->evConsumed[k], fe->stream[(k + 1) % kPipe], perSide);
+    if (rc) return rc;
+    launch_stereo(c.hc, c.dc, c.b, n_pairs, fe->cfg.bf, fe->cfg.b, st);
+    IVF_MARK(st, c.markOwn, 7, c.nRuns - 1);
+    // Frame::UndistortKeyPoints (Frame.cc:145, :696-726): the left frames only (images are interleaved L,R: every second frame of b.kps)
+    if (fe->camOn)
+        launch_undistort_keys(fe->cam, false, c.b.kps, (size_t)2 * c.hc.nfeatures, c.b.count, 2, n_pairs, c.hc.nfeatures, fe->kpsUn[k],
+                              (size_t)2 * c.hc.nfeatures, st);
+    fe->unOf[k] = fe->camOn;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(fe->evDone[k], st));
+    // the caller's stream may overwrite its input buffers once they have been ingested
+    HIPCHK(hipStreamWaitEvent(caller, fe->evConsumed[k], 0));
+    fe->pairsOf[k] = n_pairs;
+    IVF_MARK_HOST(6, (fe->runs << 8) | 2);
+    fe->runs++;
+    return IVF_OK;
+}
 
 int ivf_frontend_run(ivf_frontend* fe, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_cost,
                      size_t image_stride, int row_stride, int n_pairs, void* hip_stream)
@@ -937,7 +995,9 @@ int ivf_frontend_run(ivf_frontend* fe, const uint8_t* d_left, const uint8_t* d_r
     if (n_pairs < 1 || n_pairs > fe->cfg.max_pairs) return fail(IVF_E_INVALID, "n_pairs %d outside [1,%d]", n_pairs, fe->cfg.max_pairs);
     if (row_stride < fe->cfg.width || image_stride < (size_t)row_stride * (fe->cfg.height - 1) + fe->cfg.width)
         return fail(IVF_E_INVALID, "strides too small for %dx%d", fe->cfg.width, fe->cfg.height);
-    return frontend_run_common(fe, d_left, d_right, d_cost, image_stride, row_stride, n_pairs, hip_stream, nullptr);
+    const ImageSrc cost{d_cost, image_stride, row_stride, 0};
+    return frontend_run(fe, {{d_left, image_stride, row_stride, 0}, {d_right, image_stride, row_stride, 0}}, d_cost ? &cost : nullptr, n_pairs,
+                        hip_stream, false);
 }
 
 int ivf_frontend_cost_plane(ivf_frontend* fe, uint8_t** d_plane, size_t* image_stride, int* row_stride, void* hip_stream)
@@ -946,11 +1006,7 @@ int ivf_frontend_cost_plane(ivf_frontend* fe, uint8_t** d_plane, size_t* image_s
     const int k = (int)(fe->runs % kPipe);
     Context& c = fe->ctx[k];
     HIPCHK(hipSetDevice(fe->cfg.device_id));
-    if (!c.b.qpyr) {            // extractors that ignore the map (enableIntrospection = 0) allocate the plane on first use
-        const size_t blob = (size_t)c.hc.pyrBytes * c.maxImg;
-        HIPCHK(hipMalloc(&c.b.qpyr, blob));
-        HIPCHK(hipMemset(c.b.qpyr, 0, blob));
-    }
+    if (const int rc = c.ensure_qpyr(nullptr)) return rc;
     // the context's previous batch (three runs ago) read this plane: the caller's stream may write it once that batch is done
     if (fe->runs >= kPipe) HIPCHK(hipStreamWaitEvent((hipStream_t)hip_stream, fe->evDone[k], 0));
     *d_plane = c.b.qpyr + c.hc.lv[0].off;
@@ -965,57 +1021,19 @@ int ivf_frontend_run_color(ivf_frontend* fe, const uint8_t* d_left, int left_cod
 {
     if (!fe || !d_left || !d_right) return fail(IVF_E_INVALID, "null argument");
     if (n_pairs < 1 || n_pairs > fe->cfg.max_pairs) return fail(IVF_E_INVALID, "n_pairs %d outside [1,%d]", n_pairs, fe->cfg.max_pairs);
-    Context::SideSrc sides[2];
-    const uint8_t* ptr[2] = {d_left, d_right}; const int code[2] = {left_code, right_code};
-    const size_t ist[2] = {left_image_stride, right_image_stride}; const int rst[2] = {left_row_stride, right_row_stride};
+    const ImageSrc side[2] = {{d_left, left_image_stride, left_row_stride, left_code}, {d_right, right_image_stride, right_row_stride, right_code}};
     for (int sd = 0; sd < 2; sd++) {
-        if (code[sd] < 0 || (code[sd] & 3) == 3 || code[sd] > 7 || (!(code[sd] & 3) && code[sd]))
-            return fail(IVF_E_INVALID, "side %d: colour code %d is not 0 (grey), 1 (bytes B,G,R) or 2 (bytes R,G,B), the last two optionally + 4 (OpenCV <= 3 coefficients)", sd, code[sd]);
-        const int ch = (code[sd] & 3) ? 3 : 1;
-        if (rst[sd] < ch * fe->cfg.width || ist[sd] < (size_t)rst[sd] * (fe->cfg.height - 1) + (size_t)ch * fe->cfg.width)
+        const ImageSrc& q = side[sd];
+        if (q.code < 0 || (q.code & 3) == 3 || q.code > 7 || (!(q.code & 3) && q.code))
+            return fail(IVF_E_INVALID, "side %d: colour code %d is not 0 (grey), 1 (bytes B,G,R) or 2 (bytes R,G,B), the last two optionally + 4 (OpenCV <= 3 coefficients)", sd, q.code);
+        const int ch = (q.code & 3) ? 3 : 1;
+        if (q.rowStride < ch * fe->cfg.width || q.imageStride < (size_t)q.rowStride * (fe->cfg.height - 1) + (size_t)ch * fe->cfg.width)
             return fail(IVF_E_INVALID, "side %d: strides too small for %dx%d x %d channel(s)", sd, fe->cfg.width, fe->cfg.height, ch);
-        sides[sd].src = ptr[sd]; sides[sd].imageStride = ist[sd]; sides[sd].rowStride = rst[sd]; sides[sd].code = code[sd];
     }
     if (d_cost && (cost_row_stride < fe->cfg.width || cost_image_stride < (size_t)cost_row_stride * (fe->cfg.height - 1) + fe->cfg.width))
         return fail(IVF_E_INVALID, "cost strides too small for %dx%d", fe->cfg.width, fe->cfg.height);
-    return frontend_run_common(fe, d_left, d_right, d_cost, cost_image_stride, cost_row_stride, n_pairs, hip_stream, sides);
-}
-
-// sides != nullptr: the images come from sides[0 / 1] (own strides, grey or colour); image_stride / row_stride then describe the cost maps only
-static int frontend_run_common(ivf_frontend* fe, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_cost,
-                               size_t image_stride, int row_stride, int n_pairs, void* hip_stream, const Context::SideSrc* sides)
-{
-    hipStream_t caller = (hipStream_t)hip_stream;
-    const int k = (int)(fe->runs % kPipe);
-    Context& c = fe->ctx[k];
-    if (sides) { c.sideSrc[0] = sides[0]; c.sideSrc[1] = sides[1]; }
-    hipStream_t st = fe->stream[k];
-    HIPCHK(hipSetDevice(fe->cfg.device_id));
-    // order: everything the caller enqueued so far (it produced the inputs) -> this batch
-    IVF_MARK_HOST(6, (fe->runs << 8) | 1);
-    HIPCHK(hipEventRecord(fe->evIn[k], caller));
-    HIPCHK(hipStreamWaitEvent(st, fe->evIn[k], 0));
-    // the blur of this batch is lent the internal stream of the NEXT context: whatever older batch that stream still holds does not
-    // depend on this one, and the next batch queues behind the blur
-    int rc = c.run(d_left, d_right, d_cost, image_stride, row_stride, image_stride, row_stride, 2 * n_pairs,
-                   fe->dFlags, st, fe->evConsumed[k], fe->stream[(k + 1) % kPipe]);
-    if (rc) return rc;
-    launch_stereo(c.hc, c.dc, c.b, n_pairs, fe->cfg.bf, fe->cfg.b, st);
-    IVF_MARK(st, c.markOwn, 7, c.nRuns - 1);
-    // Frame::UndistortKeyPoints (Frame.cc:145, :696-726): the left frames only (images are interleaved L,R: every second frame of b.kps)
-    if (fe->camOn)
-        launch_undistort_keys(fe->cam, false, c.b.kps, (size_t)2 * c.hc.nfeatures, c.b.count, 2, n_pairs, c.hc.nfeatures, fe->kpsUn[k],
-                              (size_t)2 * c.hc.nfeatures, st);
-    fe->unOf[k] = fe->camOn;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(fe->evDone[k], st));
-    // the caller's stream may overwrite its input buffers once they have been ingested
-    HIPCHK(hipStreamWaitEvent(caller, fe->evConsumed[k], 0));
-    fe->lastPairs = n_pairs;
-    fe->pairsOf[k] = n_pairs;
-    IVF_MARK_HOST(6, (fe->runs << 8) | 2);
-    fe->runs++;
-    return IVF_OK;
+    const ImageSrc cost{d_cost, cost_image_stride, cost_row_stride, 0};
+    return frontend_run(fe, side, d_cost ? &cost : nullptr, n_pairs, hip_stream, true);
 }
 
 int ivf_frontend_sync(ivf_frontend* fe)
@@ -1054,43 +1072,46 @@ int ivf_frontend_device_results(const ivf_frontend* fe, int side, const ivf_keyp
                                 const float** d_quality, int* cap)
 {
     if (!fe || side < 0 || side > 1) return fail(IVF_E_INVALID, "bad argument");
-    const Buffers& b = fe->ctx[fe->last()].b;
-    const size_t nf = fe->ctx[0].hc.nfeatures;
-    // images are interleaved [L0,R0,L1,R1,...]: element stride between pairs is 2*cap
-    if (d_kps) *d_kps = b.kps + side * nf;
-    if (d_desc) *d_desc = b.desc + side * nf * 32;
-    if (d_count) *d_count = b.count + side;
-    if (d_uright) *d_uright = side == 0 ? b.uright : nullptr;
-    if (d_depth) *d_depth = side == 0 ? b.depth : nullptr;
-    if (d_quality) *d_quality = b.quality + side * nf;
-    if (cap) *cap = (int)nf;
+    // base of the side: pair p lies p * 2 * cap elements (counts: 2 p) further on, the stereo results p * cap
+    const BatchImage im = batch_image(fe, fe->last(), 0, side);
+    if (d_kps) *d_kps = im.mvKeys;
+    if (d_desc) *d_desc = im.desc;
+    if (d_count) *d_count = im.count;
+    if (d_uright) *d_uright = im.uright;
+    if (d_depth) *d_depth = im.depth;
+    if (d_quality) *d_quality = im.quality;
+    if (cap) *cap = im.cap;
+    return IVF_OK;
+}
+
+// one image of a held batch to the host; undistorted: its mvKeysUn instead of mvKeys (the same unless the run had a camera)
+static int fetch_image(ivf_frontend* fe, int age, int pair, int side, bool undistorted, ivf_keypoint* kps, uint8_t* desc, int cap, int* n_out,
+                       float* uright, float* depth, float* quality)
+{
+    if (!fe || !n_out || side < 0 || side > 1) return fail(IVF_E_INVALID, "bad argument");
+    int k = 0, rc = held_batch(fe, age, &k);
+    if (rc) return rc;
+    if (pair < 0 || pair >= fe->pairsOf[k]) return fail(IVF_E_INVALID, "pair %d outside the batch of %d", pair, fe->pairsOf[k]);
+    rc = ivf_frontend_sync(fe);
+    if (rc) return rc;
+    const BatchImage im = batch_image(fe, k, pair, side);
+    int n = 0;
+    HIPCHK(hipMemcpy(&n, im.count, sizeof(int), hipMemcpyDeviceToHost));
+    *n_out = n;
+    if (n > cap) return fail(IVF_E_CAPACITY, "%d keypoints exceed caller capacity %d", n, cap);
+    if (n == 0) return IVF_OK;
+    if (kps) HIPCHK(hipMemcpy(kps, undistorted ? im.kps : im.mvKeys, (size_t)n * sizeof(ivf_keypoint), hipMemcpyDeviceToHost));
+    if (desc) HIPCHK(hipMemcpy(desc, im.desc, (size_t)n * 32, hipMemcpyDeviceToHost));
+    if (quality) HIPCHK(hipMemcpy(quality, im.quality, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (uright && im.uright) HIPCHK(hipMemcpy(uright, im.uright, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (depth && im.depth) HIPCHK(hipMemcpy(depth, im.depth, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return IVF_OK;
 }
 
 int ivf_frontend_fetch_of(ivf_frontend* fe, int age, int pair, int side, ivf_keypoint* kps, uint8_t* desc, int cap, int* n_out,
                           float* uright, float* depth, float* quality)
 {
-    if (!fe || !n_out || side < 0 || side > 1) return fail(IVF_E_INVALID, "bad argument");
-    if (age < 0 || age >= kPipe || fe->runs <= age) return fail(IVF_E_STATE, "no batch of age %d is held", age);
-    const int k = (int)((fe->runs - 1 - age) % kPipe);
-    if (pair < 0 || pair >= fe->pairsOf[k]) return fail(IVF_E_INVALID, "pair %d outside the batch of %d", pair, fe->pairsOf[k]);
-    int rc = ivf_frontend_sync(fe);
-    if (rc) return rc;
-    const Buffers& b = fe->ctx[k].b;
-    const size_t nf = fe->ctx[0].hc.nfeatures, img = (size_t)pair * 2 + side;
-    int n = 0;
-    HIPCHK(hipMemcpy(&n, b.count + img, sizeof(int), hipMemcpyDeviceToHost));
-    *n_out = n;
-    if (n > cap) return fail(IVF_E_CAPACITY, "%d keypoints exceed caller capacity %d", n, cap);
-    if (n == 0) return IVF_OK;
-    if (kps) HIPCHK(hipMemcpy(kps, b.kps + img * nf, (size_t)n * sizeof(ivf_keypoint), hipMemcpyDeviceToHost));
-    if (desc) HIPCHK(hipMemcpy(desc, b.desc + img * nf * 32, (size_t)n * 32, hipMemcpyDeviceToHost));
-    if (quality) HIPCHK(hipMemcpy(quality, b.quality + img * nf, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    if (side == 0) {
-        if (uright) HIPCHK(hipMemcpy(uright, b.uright + (size_t)pair * nf, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-        if (depth) HIPCHK(hipMemcpy(depth, b.depth + (size_t)pair * nf, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    return IVF_OK;
+    return fetch_image(fe, age, pair, side, false, kps, desc, cap, n_out, uright, depth, quality);
 }
 
 int ivf_frontend_fetch(ivf_frontend* fe, int pair, int side, ivf_keypoint* kps, uint8_t* desc, int cap, int* n_out,
@@ -1109,7 +1130,7 @@ int ivf_frontend_set_camera(ivf_frontend* fe, const ivf_camera* cam)
     HIPCHK(hipSetDevice(fe->cfg.device_id));
     const size_t bytes = (size_t)2 * fe->cfg.max_pairs * fe->ctx[0].hc.nfeatures * sizeof(ivf_keypoint);
     for (int k = 0; k < kPipe; k++)
-        if (!fe->kpsUn[k]) HIPCHK(hipMalloc(&fe->kpsUn[k], bytes));
+        if (!fe->kpsUn[k]) HIPCHK(fe->ctx[k].alloc(fe->kpsUn[k], bytes));
     fe->cam = ivf::undistort_cam(*cam);       // passed to the kernel by value: batches already enqueued keep the camera they ran with
     fe->camOn = true;
     return IVF_OK;
@@ -1118,29 +1139,16 @@ int ivf_frontend_set_camera(ivf_frontend* fe, const ivf_camera* cam)
 int ivf_frontend_undistorted(const ivf_frontend* fe, int age, const ivf_keypoint** d_kps_un)
 {
     if (!fe || !d_kps_un) return fail(IVF_E_INVALID, "null argument");
-    if (age < 0 || age >= kPipe || fe->runs <= age) return fail(IVF_E_STATE, "no batch of age %d is held", age);
-    const int k = (int)((fe->runs - 1 - age) % kPipe);
+    int k = 0;
+    if (const int rc = held_batch(fe, age, &k)) return rc;
     if (!fe->unOf[k]) return fail(IVF_E_STATE, "the batch of age %d ran without an undistorting camera: mvKeysUn == mvKeys", age);
-    *d_kps_un = fe->kpsUn[k];
+    *d_kps_un = batch_image(fe, k, 0, 0).kps;
     return IVF_OK;
 }
 
 int ivf_frontend_fetch_undistorted(ivf_frontend* fe, int age, int pair, ivf_keypoint* kps_un, int cap, int* n_out)
 {
-    if (!fe || !n_out) return fail(IVF_E_INVALID, "bad argument");
-    if (age < 0 || age >= kPipe || fe->runs <= age) return fail(IVF_E_STATE, "no batch of age %d is held", age);
-    const int k = (int)((fe->runs - 1 - age) % kPipe);
-    if (!fe->unOf[k]) return ivf_frontend_fetch_of(fe, age, pair, 0, kps_un, nullptr, cap, n_out, nullptr, nullptr, nullptr);
-    if (pair < 0 || pair >= fe->pairsOf[k]) return fail(IVF_E_INVALID, "pair %d outside the batch of %d", pair, fe->pairsOf[k]);
-    int rc = ivf_frontend_sync(fe);
-    if (rc) return rc;
-    const size_t nf = fe->ctx[0].hc.nfeatures;
-    int n = 0;
-    HIPCHK(hipMemcpy(&n, fe->ctx[k].b.count + (size_t)pair * 2, sizeof(int), hipMemcpyDeviceToHost));
-    *n_out = n;
-    if (n > cap) return fail(IVF_E_CAPACITY, "%d keypoints exceed caller capacity %d", n, cap);
-    if (n > 0 && kps_un) HIPCHK(hipMemcpy(kps_un, fe->kpsUn[k] + (size_t)2 * pair * nf, (size_t)n * sizeof(ivf_keypoint), hipMemcpyDeviceToHost));
-    return IVF_OK;
+    return fetch_image(fe, age, pair, 0, true, kps_un, nullptr, cap, n_out, nullptr, nullptr, nullptr);
 }
 
 float ivf_frontend_last_fast_ms(ivf_frontend* fe)
@@ -1179,8 +1187,8 @@ int ivf_frontend_pack_gather_block_of(ivf_frontend* fe, int age, uint8_t* d_bloc
     *record_bytes = rec;
     if (!d_block) return IVF_OK;
     if (age < 0 || age >= kPipe) return fail(IVF_E_INVALID, "age %d outside [0,%d): results stay valid for %d further runs", age, kPipe, kPipe - 1);
-    if (fe->runs <= age) return fail(IVF_E_STATE, "no batch of age %d has run", age);
-    const int k = (int)((fe->runs - 1 - age) % kPipe);
+    int k = 0;
+    if (const int rc = held_batch(fe, age, &k)) return rc;
     const int np = fe->pairsOf[k];
     if (block_bytes < rec * np) return fail(IVF_E_CAPACITY, "gather block needs %zu bytes", rec * np);
     if (((size_t)d_block & 15) != 0) return fail(IVF_E_INVALID, "gather block must be 16-byte aligned");
@@ -1188,15 +1196,16 @@ int ivf_frontend_pack_gather_block_of(ivf_frontend* fe, int age, uint8_t* d_bloc
     hipStream_t st = (hipStream_t)hip_stream;
     if (hip_stream == IVF_STREAM_OF_BATCH) st = fe->stream[k];        // in order behind the batch itself: nothing to wait for
     else HIPCHK(hipStreamWaitEvent(st, fe->evDone[k], 0));            // the batch ran on an internal stream
-    launch_pack_gather(fe->ctx[k].b, fe->unOf[k] ? fe->kpsUn[k] : nullptr, (int)nf, np, d_block, rec, st);
+    launch_pack_gather(fe->ctx[k].b, batch_image(fe, k, 0, 0).kps, (int)nf, np, d_block, rec, st);
     HIPCHK(hipGetLastError());
     return IVF_OK;
 }
 
 void* ivf_frontend_batch_stream(ivf_frontend* fe, int age)
 {
-    if (!fe || age < 0 || age >= kPipe || fe->runs <= age) return nullptr;
-    return (void*)fe->stream[(fe->runs - 1 - age) % kPipe];
+    int k = 0;
+    if (!fe || held_batch(fe, age, &k)) return nullptr;
+    return (void*)fe->stream[k];
 }
 
 // A resident frame straight from a batch (the frame itself: ivf::frame_from_batch, ivf_match.hip).  `age` as in
@@ -1207,19 +1216,11 @@ int ivf_frame_create_from_frontend(ivf_frontend* fe, int age, int pair, int side
     *out = nullptr;
     if (!fe || !bounds || side < 0 || side > 1) return fail(IVF_E_INVALID, "bad argument");
     if (!(bounds->max_x > bounds->min_x) || !(bounds->max_y > bounds->min_y)) return fail(IVF_E_INVALID, "empty image bounds");
-    if (age < 0 || age >= kPipe || fe->runs <= age) return fail(IVF_E_STATE, "no batch of age %d is held", age);
-    const int k = (int)((fe->runs - 1 - age) % kPipe);
+    int k = 0;
+    if (const int rc = held_batch(fe, age, &k)) return rc;
     if (pair < 0 || pair >= fe->pairsOf[k]) return fail(IVF_E_INVALID, "pair %d outside the batch of %d", pair, fe->pairsOf[k]);
     HIPCHK(hipSetDevice(fe->cfg.device_id));
-    const Buffers& b = fe->ctx[k].b;
-    const size_t nf = fe->ctx[k].hc.nfeatures, img = (size_t)pair * 2 + side;
-    BatchImage src;
-    // Frame::AssignFeaturesToGrid reads mvKeysUn (Frame.cc:424): the left frame of a run made with a camera
-    src.kps = (side == 0 && fe->unOf[k]) ? fe->kpsUn[k] + img * nf : b.kps + img * nf;
-    src.desc = b.desc + img * nf * 32;
-    src.uright = side == 0 ? b.uright + (size_t)pair * nf : nullptr;
-    src.count = b.count + img; src.cap = (int)nf; src.done = fe->evDone[k];
-    return frame_from_batch(fe->cfg.device_id, src, *bounds, out);
+    return frame_from_batch(fe->cfg.device_id, batch_image(fe, k, pair, side), *bounds, out);
 }
 
 int ivf_frontend_pack_gather_block(ivf_frontend* fe, uint8_t* d_block, size_t block_bytes, size_t* record_bytes, void* hip_stream)

@@ -177,15 +177,15 @@ int thread_scratch(int device, size_t need, uint8_t** out);
 int thread_pinned(size_t need, uint8_t** out);
 int have_device(int dev);
 
-// One image of a front-end batch, as ivf_frame_create_from_frontend (ivf_api.hip) resolves it, and the frame made of it (ivf_match.hip,
-// which alone knows struct ivf_frame): `count` keypoints of at most `cap` are valid once `done` has passed; uright == nullptr: no stereo
-struct BatchImage { const ivf_keypoint* kps; const uint8_t* desc; const float* uright; const int* count; int cap; hipEvent_t done; };
+// One image of a front-end batch, as batch_image (ivf_api.hip) resolves it, and the frame made of it (ivf_match.hip, which alone knows struct ivf_frame):
+// `count` keypoints of at most `cap` are valid once `done` has passed; kps = mvKeysUn (mvKeys unless the run had a camera); uright == depth == nullptr: no stereo
+struct BatchImage { const ivf_keypoint *kps, *mvKeys; const uint8_t* desc; const float *uright, *depth, *quality; const int* count; int cap; hipEvent_t done; };
 int frame_from_batch(int device, const BatchImage& src, const ivf_bounds& bounds, ivf_frame** out);
 
 // launchers (ivf_kernels.hip)
 void launch_stereo_args(const Config& hc, const Config* dc, const StereoArgs& A, int nPairs, hipStream_t s);
-void launch_ingest(const Config& hc, const Config* dc, const Buffers& b, const uint8_t* src0, const uint8_t* src1,
-                   size_t imageStride, int rowStride, int nImg, int nSides, uint8_t* dstBlob, hipStream_t s, int sideMask = 3);
+void launch_ingest(const Config& hc, const Config* dc, const uint8_t* src0, const uint8_t* src1, size_t imageStride, int rowStride,
+                   int nImg, int nSides, uint8_t* dstBlob, const uint8_t* onlyFlagged, hipStream_t s, int sideMask = 3);
 void launch_ingest_color(const Config& hc, const Config* dc, const uint8_t* src, size_t imageStride, int rowStride, int code, int nImg, int nSides, int side,
                          uint8_t* dstBlob, hipStream_t s);
 void launch_pyramid(const Config& hc, const Config* dc, const ResizeCoef* dTab, uint8_t* blob, uint8_t* qblob, const uint8_t* useCost,
@@ -193,8 +193,7 @@ void launch_pyramid(const Config& hc, const Config* dc, const ResizeCoef* dTab, 
 void launch_fast(const Config& hc, const Config* dc, const Buffers& b, int nImg, hipStream_t s);
 void launch_blur(const Config& hc, const Config* dc, const Buffers& b, int nImg, hipStream_t s, bool skipEmptyLevels);
 void launch_select(const Config& hc, const Config* dc, const Buffers& b, int nImg, hipStream_t s);
-void launch_describe(const Config& hc, const Config* dc, const Buffers& b, const uint8_t* cost0, size_t costStride,
-                     int costPitch, int nImg, int nSides, hipStream_t s);
+void launch_describe(const Config& hc, const Config* dc, const Buffers& b, int nImg, hipStream_t s);
 void launch_stereo(const Config& hc, const Config* dc, const Buffers& b, int nPairs, float bf, float bb, hipStream_t s);
 void launch_test_retain_best(const float* dResp, int n, int nPoints, int* dOrder, hipStream_t s);
 // kpsUn != nullptr: the records carry these keypoints (mvKeysUn of the left frames, addressed like b.kps: pair p at 2 * p * nf) instead of b.kps

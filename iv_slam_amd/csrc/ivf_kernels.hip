@@ -2254,15 +2254,14 @@ void launch_test_retain_best(const float* dResp, int n, int nPoints, int* dOrder
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-// dstBlob == b.qpyr: the cost images; only the planes something reads are written (useCost bit 0: the cost pyramid gates the
+// onlyFlagged = the useCost flags for the cost images: only the planes something reads are written (bit 0: the cost pyramid gates the
 // extraction, bit 1: mvKeyQualScore samples level 0)
-void launch_ingest(const Config& hc, const Config* dc, const Buffers& b, const uint8_t* src0, const uint8_t* src1,
-                   size_t imageStride, int rowStride, int nImg, int nSides, uint8_t* dstBlob, hipStream_t s, int sideMask)
+void launch_ingest(const Config& hc, const Config* dc, const uint8_t* src0, const uint8_t* src1, size_t imageStride, int rowStride,
+                   int nImg, int nSides, uint8_t* dstBlob, const uint8_t* onlyFlagged, hipStream_t s, int sideMask)
 {
     const LevelGeom& G = hc.lv[0];
     dim3 grid((G.h + kIngestRows - 1) / kIngestRows, nImg);
-    hipLaunchKernelGGL(k_ingest, grid, dim3(256), 0, s, dc, src0, src1, imageStride, rowStride, nSides, dstBlob,
-                       dstBlob == b.qpyr && b.qpyr ? b.useCost : (const uint8_t*)nullptr, sideMask);
+    hipLaunchKernelGGL(k_ingest, grid, dim3(256), 0, s, dc, src0, src1, imageStride, rowStride, nSides, dstBlob, onlyFlagged, sideMask);
 }
 // side `side` of every pair (nImg / nSides images) from 3-channel interleaved images: level 0 = cvtColor(..., GRAY)
 void launch_ingest_color(const Config& hc, const Config* dc, const uint8_t* src, size_t imageStride, int rowStride, int code, int nImg, int nSides, int side,
@@ -2339,8 +2338,7 @@ void launch_select(const Config& hc, const Config* dc, const Buffers& b, int nIm
     hipLaunchKernelGGL(k_level_select, dim3(hc.nlevels, nImg), dim3(256), (size_t)lcap * 12, s, dc, b.lvlTotal, b.lvl, b.slotPos, b.slotResp,
                        b.lvlCount, lcap);
 }
-void launch_describe(const Config& hc, const Config* dc, const Buffers& b, const uint8_t*, size_t, int, int nImg, int,
-                     hipStream_t s)
+void launch_describe(const Config& hc, const Config* dc, const Buffers& b, int nImg, hipStream_t s)
 {
     hipLaunchKernelGGL(k_describe, dim3((nImg + 7) / 8 * 8 * ((hc.nfeatures + kDescKP - 1) / kDescKP)), dim3(256), 0, s, dc, b.pyr, b.blur, b.qpyr,
                        b.useCost, b.slotPos, b.slotResp, b.lvlCount, b.kps, b.desc, b.count, b.quality, nImg);

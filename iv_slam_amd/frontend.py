@@ -30,6 +30,7 @@ class StereoFrontend:
 
     def __del__(self):
         if getattr(self, "_h", None):
+            self._plane_views = None            # views over library memory: gone before the memory is
             self._lib.ivf_frontend_destroy(self._h)
             self._h = None
 
@@ -77,7 +78,8 @@ class StereoFrontend:
         """The pitched level-0 cost plane of the batch context the NEXT run uses, as a torch u8 view [n, height, width] (rows / images padded): a producer on
         the device (IntrospectionFCN.forward_device(..., cost_u8=view)) writes the maps there and run_color(..., cost=view) skips their ingest.
         `stream_ptr` waits until that context's previous batch is done with the plane."""
-        import torch
+        if not 1 <= n <= self.max_pairs:
+            raise ValueError("cost_plane(%d): the plane holds 1..%d pairs (max_pairs)" % (n, self.max_pairs))
         p = C.c_void_p(); ist = C.c_size_t(); rst = C.c_int()
         check(self._lib.ivf_frontend_cost_plane(self._h, C.byref(p), C.byref(ist), C.byref(rst), stream_ptr))
         key = (p.value, n)
