@@ -426,7 +426,12 @@ int  ivf_tracker_search_local(ivf_tracker* t, const uint8_t* d_records, size_t r
  * per frame, double arithmetic where the reference uses it; the sums over edges are taken in a fixed order (bit-identical re-runs).
  * d_xw [n_frames][nfeatures][3] = pMP->GetWorldPos() of the point keypoint i holds; d_has_point [n_frames][nfeatures] = mvpMapPoints[i]
  * != NULL (keypoints past the record's count are ignored); d_quality [n_frames][nfeatures] or NULL (= 1.0f) = the qual_score of
- * :315-320; n_rounds = FLAGS_optimizer_pose_opt_iter_count (default 4), 1..4.
+ * :315-320; n_rounds = FLAGS_optimizer_pose_opt_iter_count (default 4), 1..4.  The scores are expected in [0, 1].  They are not
+ * clamped: a negative one gives its edge a negative weight once chi2 exceeds delta^2, H + lambda I stops being positive, solves fail
+ * as g2o's would, and the call returns whatever pose and flags the reference's arithmetic gives on that input (in the tested case the
+ * input pose and 0 inliers).  Non-finite arithmetic (a NaN, a point at z = 0 in the camera frame) cannot hang the call, every loop
+ * has a compile-time bound, but its result is unspecified beyond that: the one tested case, a z = 0.0f point at the identity pose,
+ * returns the pose unchanged with no outlier flagged.
  * d_poses [n_frames][12] in: pFrame->mTcw (row-major 3x4), out: the pose SetPose receives; d_outlier [n_frames][nfeatures] = mvbOutlier
  * (0 where there is no point); d_ninliers [n_frames] = the return value (0 with fewer than 3 correspondences: pose unchanged; -1 for a
  * record index outside [0, n_records): pose unchanged); d_chi2 [n_frames][nfeatures] (nullable) = mvChi2 as logging == true records it

@@ -42,7 +42,8 @@ def make_tracker(iv, nf, max_pairs, cam=None):
 
 
 def run_optimize(iv, frames, nf, n_rounds, max_pairs, bad=(), with_quality=None, tracker=None):
-    """frames: list of scene dicts -> dict of device results as numpy; slots in `bad` get a record index outside the block"""
+    """frames: list of scene dicts -> dict of device results as numpy; slots in `bad` get a record index outside the block; a frame with
+    has_tail = 1 gets has_point = 1 and a point 10 m ahead on every slot past its record's count"""
     import torch
     from iv_slam_amd import dist as ivd
     dev = torch.device("cuda:0")
@@ -55,6 +56,8 @@ def run_optimize(iv, frames, nf, n_rounds, max_pairs, bad=(), with_quality=None,
         xw[k, :f["n"]] = f["xw"]; has[k, :f["n"]] = f["has"]; poses[k] = f["pose_in"]
         if f["quality"] is not None:
             q[k, :f["n"]] = f["quality"]
+        if f.get("has_tail"):
+            has[k, f["n"]:] = 1; xw[k, f["n"]:] = (0.0, 0.0, 10.0)
     use_q = with_quality if with_quality is not None else any(f["quality"] is not None for f in frames)
     d = dict(frames=torch.tensor(idx, dtype=torch.int32, device=dev), xw=torch.from_numpy(xw).to(dev), has=torch.from_numpy(has).to(dev),
              q=torch.from_numpy(q).to(dev) if use_q else None, poses=torch.from_numpy(poses).to(dev),
@@ -78,6 +81,7 @@ def check_frame(name, k, fr, ref, got, floor_rot, floor_trans, borderline):
     diff = np.nonzero(got["outlier"][k, :n] != ref["outlier"][:n])[0]
     assert set(int(i) for i in diff) <= set(borderline), "%s frame %d: mvbOutlier differs at %r" % (name, k, diff[:8])
     assert not got["outlier"][k, n:].any() and not got["outlier"][k, :n][fr["has"] == 0].any()
+    assert not got["chi2"][k, n:].any(), "chi2 logged on a slot past the record's count"
     assert abs(int(got["ninl"][k]) - ref["ninliers"]) <= len(borderline) and (len(diff) > 0 or got["ninl"][k] == ref["ninliers"])
     if ref["chi2"] is not None:
         c = got["chi2"][k, :n]
@@ -100,7 +104,9 @@ def check_frame(name, k, fr, ref, got, floor_rot, floor_trans, borderline):
 @pytest.mark.parametrize("name", sorted(SCENARIOS))
 def test_scenario_against_the_restatement(iv, name):
     """edge counts 0 / 2 / 3 / 9 / 10 / 63 / 64 / 65 / 257 / 1000 of 4096, mono / stereo / mixed, n_rounds 1..4, n_frames 1 / 3 /
-    max_pairs, every quality mode, one bad record index; and a second run is bit-identical to the first"""
+    max_pairs, every quality mode, one bad record index; rotations of 119..180 degrees and exact axis permutations (every case of
+    Quaterniond(Matrix3d), the sign flip of normalizeRotation), points behind the camera, negative quality (failed solves, the pose
+    stays), has_point set past the record's count; and a second run is bit-identical to the first"""
     sc = SCENARIOS[name]
     g = NOISE[name]
     assert sum(len(v) for v in g["borderline"].values()) <= 0.01 * g["n_edges"]
@@ -126,6 +132,109 @@ def test_quality_of_one_is_no_quality_and_rounds_are_checked(iv):
             run_optimize(iv, sc["frames"], 64, r, 1)
     with pytest.raises(iv.IvfError):
         run_optimize(iv, sc["frames"] * 2, 64, 4, 1)                       # n_frames > max_pairs
+
+
+def test_conversion_only_is_the_restatement_to_the_bit(iv):
+    """the scenario in which nothing is optimised (quality 0, one round): the device pose is Converter::toCvMat(Converter::toSE3Quat(input)),
+    a few dozen double operations with no sum over edges in them, so it equals the restatement's bit for bit -- each hand-written case of
+    Quaterniond(Matrix3d) compared directly, not through a Levenberg-Marquardt that would repair a wrong start.  sqrt and the divisions
+    are correctly rounded in double on both sides and nothing is fused (-ffp-contract=off)."""
+    sc = SCENARIOS["conversion_only"]
+    refs = reference("conversion_only")
+    got = run_optimize(iv, sc["frames"], sc["nf"], sc["n_rounds"], sc["max_pairs"])
+    for k, fr in enumerate(sc["frames"]):
+        q, t = PR.se3_from_pose(fr["pose_in"])
+        assert refs[k]["pose"].tobytes() == PR.pose_from_se3(q, t).tobytes()
+        assert got["pose"][k].tobytes() == refs[k]["pose"].tobytes(), (k, got["pose"][k], refs[k]["pose"])
+        assert np.array_equal(got["outlier"][k], refs[k]["outlier"]) and got["ninl"][k] == refs[k]["ninliers"]
+        assert got["chi2"][k].tobytes() == refs[k]["chi2"].tobytes(), k
+
+
+def zero_depth_frame():
+    """a scene moved into its camera's frame (input pose = identity, world points = their camera coordinates narrowed to float), 40 edges,
+    one of them with z = 0.0f: the identity quaternion maps a point to itself exactly, so P[2] is exactly 0"""
+    fr = S.make_frame(901, 64, 40, "mixed", 1.0, 0, prior=(0, 0))
+    T = fr["pose_gt"].reshape(3, 4)
+    fr["xw"] = (fr["xw"].astype(np.float64) @ T[:, :3].T + T[:, 3]).astype(F)
+    fr["pose_in"] = np.eye(4, dtype=F)[:3].reshape(12).copy()
+    fr["pose_gt"] = fr["pose_in"].astype(np.float64)
+    k = int(np.nonzero(fr["has"])[0][17])
+    fr["xw"][k, 2] = F(0.0)
+    return fr, k
+
+
+def test_zero_depth_point_is_contained(iv):
+    """the kernel's claim "NaN input cannot spin the kernel", once: frame A holds a point with z = 0.0f exactly at the identity input pose.
+    Its invz is infinite, its Huber weight 0, every entry of H is 0 * inf = NaN, the solve returns NaN, every trial pose and every chi2 at it
+    is NaN; NaN compares false everywhere (levenberg.cpp:134, :149, :151, :155; Optimizer.cc:432, :469), so no trial is accepted, no edge is
+    an outlier and the estimate never moves.  Expected, from the restatement: the pose has the input's bits, no outliers, ninliers == nE,
+    chi2 NaN where the restatement's is.  Frame B, an ordinary frame in the same launch, agrees with its restatement as ever; a second
+    run is bit-identical.  Not a scenario: spread_and_borderline marks every edge of a frame with non-finite chi2 borderline."""
+    A, kz = zero_depth_frame()
+    sc = SCENARIOS["quality_None"]
+    B = sc["frames"][0]
+    with np.errstate(all="ignore"):
+        refA = S.reference(A, 4)
+    ne = int(A["has"].sum())
+    assert ne == 40 and A["xw"][kz, 2] == 0 and A["has"][kz] == 1
+    assert refA["pose"].tobytes() == A["pose_in"].tobytes() and not refA["outlier"].any() and refA["ninliers"] == ne
+    assert np.isnan(refA["chi2"][kz]) and not np.isnan(refA["chi2"][A["has"] == 0]).any()
+    got = run_optimize(iv, [A, B], 64, 4, 2)
+    print("zero depth: device inliers %d, NaN chi2 on %d edges (restatement %d), pose %r" %
+          (got["ninl"][0], int(np.isnan(got["chi2"][0]).sum()), int(np.isnan(refA["chi2"]).sum()), got["pose"][0]))
+    assert got["pose"][0].tobytes() == A["pose_in"].tobytes()
+    assert not got["outlier"][0].any() and got["ninl"][0] == ne
+    assert np.array_equal(np.isnan(got["chi2"][0]), np.isnan(refA["chi2"]))
+    assert np.isnan(refA["chi2"][A["has"] != 0]).all() and not got["chi2"][0][A["has"] == 0].any()      # all 40 edges; 0 where there is no point
+    g = NOISE["quality_None"]
+    check_frame("zero depth, frame B", 1, B, reference("quality_None")[0], got, g["floor_rot"], g["floor_trans"], g["borderline"].get("0", []))
+    again = run_optimize(iv, [A, B], 64, 4, 2)
+    for key in ("pose", "outlier", "ninl", "chi2"):
+        assert got[key].tobytes() == again[key].tobytes(), key
+
+
+def test_points_from_pairs_edges(iv):
+    """ivf_tracker_points_from_pairs on its own, nf = 70 (not a multiple of the block), poses = NULL (identity): a last-record index outside
+    the block, assign = -1 / exactly the last record's count / past it / past nf, last keypoints with depth -1 and 0.  The last records hold
+    keypoints with depth on every slot, also past their count.  Bit-exact against projection_oracle.unproject_stereo with T = I; has == 0
+    and xw == 0 everywhere else."""
+    import torch
+    import projection_oracle as PO
+    from iv_slam_amd import dist as ivd
+    nf = 70
+    dev = torch.device("cuda:0")
+    counts = [60, 70, 33]
+    recs = []
+    for k in range(3):
+        fr = S.make_frame(910 + k, nf, nf, "stereo")
+        recs.append(dict(kps=fr["kps"], desc=fr["desc"], uright=fr["uright"], depth=fr["depth"].copy()))
+    recs[0]["depth"][[5, 6]] = (-1.0, 0.0); recs[1]["depth"][[0, 69]] = (0.0, -1.0)
+    raw = ivd.pack_records(recs, nf)
+    for k, c in enumerate(counts):
+        raw[k, :4] = np.array([c], np.int32).view(np.uint8)                       # the slots from the count on keep their keypoints and depth
+    pairs = [(0, 1), (5, 2), (1, 0)]                                             # (last, current); record 5 does not exist
+    rng = np.random.default_rng(4)
+    assign = rng.integers(-1, nf + 3, (3, nf)).astype(np.int32)
+    assign[0, :8] = (-1, 60, 61, 69, 70, 1 << 30, 5, 6); assign[0, 69] = 59
+    assign[2, :6] = (0, 69, 70, -1, -(1 << 31), 68)
+    tr = make_tracker(iv, nf, 3)
+    xw = torch.full((3, nf, 3), 7.0, dtype=torch.float32, device=dev); has = torch.full((3, nf), 7, dtype=torch.uint8, device=dev)
+    tr.points_from_pairs(torch.from_numpy(raw.reshape(-1)).to(dev), torch.tensor(pairs, dtype=torch.int32, device=dev), torch.from_numpy(assign).to(dev),
+                         xw, has, poses=None)
+    torch.cuda.synchronize()
+    xw = xw.cpu().numpy(); has = has.cpu().numpy()
+    exw = np.zeros((3, nf, 3), F); ehas = np.zeros((3, nf), np.uint8)
+    for p, (a, b) in enumerate(pairs):
+        if not 0 <= a < 3:
+            continue
+        last = dict(kps=recs[a]["kps"], depth=recs[a]["depth"], T=np.eye(4, dtype=F), **{k: S.CAM[k] for k in ("fx", "fy", "cx", "cy")})
+        for i in range(nf):
+            j = int(assign[p, i])
+            if 0 <= j < counts[a] and last["depth"][j] > 0:
+                exw[p, i] = PO.unproject_stereo(last, j); ehas[p, i] = 1
+    assert ehas[0].sum() > 20 and ehas[2].sum() > 20 and not ehas[1].any() and ehas[0, 69] == 1 and not ehas[0, :8].any() and ehas[2, :6].tolist() == [0, 0, 0, 0, 0, 1]
+    assert has.tobytes() == ehas.tobytes()
+    assert xw.tobytes() == exw.tobytes()
 
 
 def test_points_from_local_is_exact(iv):
