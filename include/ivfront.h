@@ -204,7 +204,10 @@ int  ivf_update_quality_scores(const int32_t* assign, int n, float* kp_quality, 
 /* ---- testing hook ----
  * Runs the device's cv::KeyPointsFilter::retainBest core (the wave-cooperative replay of libstdc++ std::nth_element
  * used by the keypoint selection kernels) on caller-supplied non-negative responses: order_out[i] = index of the
- * element that ends at position i after nth_element(begin, begin+n_points-1, end, response-greater).  1 <= n <= 4096. */
+ * element that ends at position i after nth_element(begin, begin+n_points-1, end, response-greater).  1 <= n <= 65536.
+ * Up to 4096 elements the lists live in LDS, as in the kernels' common tiers.  Above, they live in the calling thread's device
+ * scratch and both global-memory forms run on copies of the same keys: the wave-cooperative replay (order_out) and the
+ * one-thread sequential replay; IVF_E_STATE if their orders differ anywhere. */
 int  ivf_test_retain_best(const float* responses, int n, int n_points, int32_t* order_out, int device_id);
 
 /* ---- batched device-resident stereo front end (throughput path; one per GPU) ----

@@ -1,6 +1,6 @@
 // ivf_api.hip -- C-ABI of libivfront.so (include/ivfront.h), extraction side: the per-call extractor, stereo match and undistortion,
 // the batched front end, the error state and the per-thread scratch pools.  The matcher searches, ivf_frame and the BoW calls are in
-// ivf_match.hip.  Host side only; all image / descriptor compute is in ivf_kernels.hip.  No CPU fallback exists.
+// ivf_match.hip.  Host side only; all image / descriptor compute is in ivf_kernels.hip and ivf_select.hip.  No CPU fallback exists.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -247,7 +247,7 @@ int Context::build(const Tables& t, int w, int h, int maxImages, int sides, int 
     HIPCHK(alloc(b.tileList, nI * std::max(c.nTiles, 1) * (size_t)kTileCap * sizeof(unsigned)));
     HIPCHK(alloc(b.tileCnt, nI * std::max(c.nTiles, 1) * sizeof(int)));
     HIPCHK(alloc(b.cellCnt, nI * c.nCellsTotal * 2 * sizeof(int)));
-    HIPCHK(alloc(b.cellInfo, nI * c.nCellsTotal * sizeof(int4)));
+    HIPCHK(alloc(b.cellInfo, nI * c.nCellsTotal * sizeof(CellInfo)));
     HIPCHK(alloc(b.lvlTotal, nI * kMaxLevels * sizeof(int)));
     HIPCHK(alloc(b.lvl, nI * c.candTotal * sizeof(unsigned long long)));
     HIPCHK(alloc(b.slotPos, nI * nf * sizeof(unsigned)));
@@ -271,7 +271,7 @@ int Context::build(const Tables& t, int w, int h, int maxImages, int sides, int 
     HIPCHK(alloc(b.tierList, 2 * nI * (size_t)c.nCellsTotal * sizeof(int)));
     if (c.maxCandCap > 4096) {          // kCellCapBig: cells of this geometry can outgrow the LDS selection paths
         HIPCHK(alloc(b.hugeList, (size_t)kHugeListCap * sizeof(int)));
-        HIPCHK(alloc(b.hugeScratch, (size_t)kHugeSlots * 6 * c.maxCandCap * sizeof(unsigned)));
+        HIPCHK(alloc(b.hugeScratch, (size_t)kHugeSlots * 4 * c.maxCandCap * sizeof(unsigned)));
     }
     for (int i = 0; i < kEvRing; i++) { HIPCHK(hipEventCreate(&evFast0[i])); HIPCHK(hipEventCreate(&evFast1[i])); }
     HIPCHK(hipEventCreateWithFlags(&evFork, hipEventDisableTiming));
@@ -839,18 +839,27 @@ int ivf_undistort_keypoints_device(const ivf_camera* cam, const ivf_keypoint* d_
 // testing hook (see include/ivfront.h)
 int ivf_test_retain_best(const float* responses, int n, int n_points, int32_t* order_out, int device_id)
 {
-    if (!responses || !order_out || n < 1 || n > 4096 || n_points < 0) return fail(IVF_E_INVALID, "bad argument (1 <= n <= 4096)");
+    if (!responses || !order_out || n < 1 || n > 65536 || n_points < 0) return fail(IVF_E_INVALID, "bad argument (1 <= n <= 65536)");
     int rc = have_device(device_id);
     if (rc) return rc;
     HIPCHK(hipSetDevice(device_id));
+    // responses, order, and above 4096 elements the flag and the global lists of k_test_retain_best: u64[2 * n] + u32[2 * n]
+    const bool global = n > 4096;
+    const size_t szR = ((size_t)n * 4 + 255) & ~(size_t)255;
     uint8_t* scb = nullptr;
-    rc = thread_scratch(device_id, (size_t)n * 8 + 256, &scb);
+    rc = thread_scratch(device_id, 2 * szR + (global ? 256 + (size_t)n * 24 : 0), &scb);
     if (rc) return rc;
-    float* dR = (float*)scb; int* dO = (int*)(scb + (((size_t)n * 4 + 255) & ~(size_t)255));
+    float* dR = (float*)scb; int* dO = (int*)(scb + szR);
+    int* dDiffer = global ? (int*)(scb + 2 * szR) : nullptr;
+    unsigned long long* dLists = global ? (unsigned long long*)(scb + 2 * szR + 256) : nullptr;
     HIPCHK(hipMemcpyAsync(dR, responses, (size_t)n * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    launch_test_retain_best(dR, n, n_points, dO, nullptr);
+    if (global) HIPCHK(hipMemsetAsync(dDiffer, 0, sizeof(int), nullptr));
+    launch_test_retain_best(dR, n, n_points, dO, dLists, dDiffer, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(order_out, dO, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    int differ = 0;
+    if (global) HIPCHK(hipMemcpy(&differ, dDiffer, sizeof(int), hipMemcpyDeviceToHost));
+    if (differ) return fail(IVF_E_STATE, "the wave-cooperative and the one-thread replay of nth_element disagree (n %d, n_points %d)", n, n_points);
     return IVF_OK;
 }
 

@@ -108,6 +108,9 @@ constexpr int kRowCap = 96;              // right keypoints listed per image row
 constexpr int kHugeSlots = 8;            // workgroups (= global scratch slots) of k_cell_select_huge
 constexpr int kHugeListCap = 4096;       // cells with > 4096 survivors listed per launch
 
+// per cell, from k_quota (k_cell_qsum parks the cell's cost-window sum in nTotal until then)
+struct CellInfo { int nTotal, nRetain, prefix, useMin; };
+
 struct Buffers {            // device pointers of one batch context
     uint8_t* pyr;           // [nImg][pyrBytes]  un-blurred pyramid (level 0 = ingested input)
     uint8_t* qpyr;          // [nImg][pyrBytes]  cost-map pyramid (introspection) or nullptr
@@ -116,7 +119,7 @@ struct Buffers {            // device pointers of one batch context
     int* tileCnt;           // [nImg][nTiles] survivors per tile
     int* cellCnt;           // [nImg][nCellsTotal][2] survivors per cell: {score >= minTh, score >= iniTh}
     unsigned long long* lvl;    // [nImg][candTotal] per level: kept keys (respbits<<32 | y<<16 | x) of all cells, (i,j) order
-    int4* cellInfo;         // [nImg][nCellsTotal] {nTotal, nRetain, prefix, useMin} from k_quota
+    CellInfo* cellInfo;     // [nImg][nCellsTotal]
     int* lvlTotal;          // [nImg][kMaxLevels] length of each level list before the level-wide retainBest
     unsigned int* slotPos;  // [nImg][nfeatures] (y<<16|x) level coords
     float* slotResp;        // [nImg][nfeatures]
@@ -135,7 +138,7 @@ struct Buffers {            // device pointers of one batch context
     int* hugeCount;         // [3] cells with more than 4096 survivors in this launch (k_quota -> k_cell_select_huge); [1], [2]: lengths of the tier lists
     int* tierList;          // [2][nImg * nCellsTotal] cells with 257..1024 / 1025..4096 survivors: img * nCellsTotal + cell (k_quota -> k_cell_select_list)
     int* hugeList;          // [kHugeListCap] img * nCellsTotal + cell
-    unsigned* hugeScratch;  // [kHugeSlots][6 * maxCandCap] dwords, or nullptr when no cell can exceed 4096 maxima
+    unsigned* hugeScratch;  // [kHugeSlots][4 * maxCandCap] dwords, or nullptr when no cell can exceed 4096 maxima
 };
 
 // arguments of the stereo matcher kernels: left/right data may live in one batch context
@@ -192,12 +195,13 @@ void launch_pyramid(const Config& hc, const Config* dc, const ResizeCoef* dTab, 
                     int nImg, hipStream_t s);
 void launch_fast(const Config& hc, const Config* dc, const Buffers& b, int nImg, hipStream_t s);
 void launch_blur(const Config& hc, const Config* dc, const Buffers& b, int nImg, hipStream_t s, bool skipEmptyLevels);
-void launch_select(const Config& hc, const Config* dc, const Buffers& b, int nImg, hipStream_t s);
 void launch_describe(const Config& hc, const Config* dc, const Buffers& b, int nImg, hipStream_t s);
 void launch_stereo(const Config& hc, const Config* dc, const Buffers& b, int nPairs, float bf, float bb, hipStream_t s);
-void launch_test_retain_best(const float* dResp, int n, int nPoints, int* dOrder, hipStream_t s);
 // kpsUn != nullptr: the records carry these keypoints (mvKeysUn of the left frames, addressed like b.kps: pair p at 2 * p * nf) instead of b.kps
 void launch_pack_gather(const Buffers& b, const ivf_keypoint* kpsUn, int nf, int nPairs, uint8_t* block, size_t recBytes, hipStream_t s);
+// launchers (ivf_select.hip); dLists, dDiffer: see k_test_retain_best
+void launch_select(const Config& hc, const Config* dc, const Buffers& b, int nImg, hipStream_t s);
+void launch_test_retain_best(const float* dResp, int n, int nPoints, int* dOrder, unsigned long long* dLists, int* dDiffer, hipStream_t s);
 // k_undistort_keys (ivf_rectify.hip): frame f reads kps + f * kpStride and count[f * cntStride], writes out + f * outStride (elements)
 void launch_undistort_keys(const UndistortCam& cam, bool passThrough, const ivf_keypoint* kps, size_t kpStride, const int* count, int cntStride,
                            int nFrames, int cap, ivf_keypoint* out, size_t outStride, hipStream_t s);
@@ -207,6 +211,33 @@ __device__ __forceinline__ const ivf_keypoint* rec_kps(const uint8_t* r) { retur
 __device__ __forceinline__ const uint8_t* rec_desc(const uint8_t* r, int nf) { return r + 16 + (size_t)nf * 24; }
 __device__ __forceinline__ const float* rec_uright(const uint8_t* r, int nf) { return (const float*)(r + 16 + (size_t)nf * 56); }
 __device__ __forceinline__ const float* rec_depth(const uint8_t* r, int nf) { return (const float*)(r + 16 + (size_t)nf * 60); }
+// The per-image flag byte through the scalar cache: gfx950 has no scalar byte load, so a plain `useCost [img]` is a vector load with an `s_waitcnt vmcnt(0)` in
+// front of every scalar load that follows it at the head of a workgroup.  The flag array is allocated in whole dwords (Context::build).
+__device__ __forceinline__ unsigned use_cost_of(const uint8_t* __restrict__ useCost, int img)
+{
+    const unsigned w = ((const unsigned*)useCost)[img >> 2];
+    return (w >> (8 * (img & 3))) & 0xffu;
+}
+
+// sum over the wave without the LDS crossbar (r04; was six ds_bpermute round trips): row_shr 1/2/4/8 fold each row of 16 lanes into
+// its lane 15, row_bcast15 / row_bcast31 fold the four rows into lane 63, which every lane then reads
+__device__ __forceinline__ int wave_sum_i32(int v)
+{
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
+    return __builtin_amdgcn_readlane(v, 63);
+}
+// LDS operations of one wave execute in order: a wavefront-scope fence (compiler ordering) is all that one lane needs to
+// read what another lane of the same wave wrote
+__device__ __forceinline__ void wave_sync_lds()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
 // cv::gemm on CV_32F operands: double accumulation of (double)a * (double)b, + (double)c, one narrowing
 __device__ __forceinline__ void mul_add(const float* R, const float* p, const float* t, float* out)
 {

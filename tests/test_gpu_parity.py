@@ -541,7 +541,7 @@ def test_committed_golden_fixtures(iv):
 
 
 def test_device_retain_best_matches_libstdcxx(iv):
-    """The wave-cooperative introselect on the device against the REAL libstdc++ nth_element (oracle/stl_pin.cpp):
+    """The introselect replays on the device against the REAL libstdc++ nth_element (oracle/stl_pin.cpp):
     tie-heavy random inputs, sorted/reversed runs, and organ-pipe inputs that hit the depth-limit heap-select."""
     import ctypes as C
     from iv_slam_amd import _lib
@@ -573,6 +573,23 @@ def test_device_retain_best_matches_libstdcxx(iv):
         base = np.concatenate([np.arange(0, n, 2), np.arange(1, n, 2)[::-1]]).astype(np.float32)
         for k in (1, 2, n // 3, n // 2, n - 1):
             check(base, k)
+    # above 4096 elements the hook keeps the lists in global memory and runs both forms that do so in the kernels: the
+    # wave-cooperative replay with the workgroup fence (the order it returns) and the one-thread replay (it fails if the two differ)
+    for i in range(20):
+        n = int(rng.integers(4097, 9001))
+        mode = i % 4
+        resp = rng.integers(7, 7 + int(rng.integers(1, 80)), n).astype(np.float32)
+        if mode == 1:
+            resp *= rng.choice(np.array([0.25, 0.5, 1.0], np.float32), n)
+        elif mode == 2:
+            resp = np.sort(resp)[::-1].copy() if rng.integers(0, 2) else np.sort(resp)
+        elif mode == 3:
+            resp[:] = 42.0
+        check(resp, int(rng.integers(0, n + 2)))
+    n = 8192
+    base = np.concatenate([np.arange(0, n, 2), np.arange(1, n, 2)[::-1]]).astype(np.float32)
+    for k in (1, 2, n // 3, n // 2, n - 1):
+        check(base, k)
 
 
 def test_jackal_shape_4000_features(iv):
@@ -737,6 +754,29 @@ def test_huge_cells_take_the_global_fallback(iv):
     ok2, od2 = o(img2, cap=2000)
     assert_kps_equal(gk2, ok2, "after huge")
     assert np.array_equal(gd2, od2)
+
+
+def test_cell_selection_storage_and_sort_combinations(iv):
+    """cell_select_one's four combinations of list storage and sort, on one small geometry: 640x600 at N = 50 has a 1x1 cell grid
+    on levels 0-3 (levels 4-7 are invalid); the level-0 cell is 568 rows tall (> kSelRows: bitonic sort), levels 1-3 are 468, 385
+    and 315 rows (counting sort).  The noise image leaves 15,702 / 23,226 / 14,335 / 8,148 survivors per level (all above 4,096:
+    global scratch), the synthetic one 2,391 / 1,603 / 1,328 / 1,029 (LDS tiers 1-2).  Noise, synthetic, noise again on one
+    handle: no work list or flag carries over."""
+    noise = (np.random.default_rng(19).integers(0, 4, size=(600, 640)) * 60 + 20).astype(np.uint8)
+    scene = synth.make_left(640, 600, seed=3, idx=0)
+    g = iv.ORBextractor(50, 1.2, 8, 20, 7)
+    o = O.Extractor(50, 1.2, 8, 20, 7)
+    want = {}
+    for name, img in (("noise", noise), ("scene", scene)):
+        ok, od = o(img, cap=200)
+        assert len(ok) == 34 and o.level_counts() == [11, 9, 8, 6, 0, 0, 0, 0]
+        want[name] = (ok, od, o.level_counts())
+    for name, img in (("noise", noise), ("scene", scene), ("noise", noise)):
+        gk, gd = g(img)
+        ok, od, counts = want[name]
+        assert g.level_counts() == counts
+        assert_kps_equal(gk, ok, "640x600 N=50 " + name)
+        assert np.array_equal(gd, od)
 
 
 def test_quality_scores_without_extractor_introspection(iv):
