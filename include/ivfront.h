@@ -601,6 +601,36 @@ int  ivf_bow_transform(const ivf_vocabulary* v, const uint8_t* desc, int n, int 
 int  ivf_bow_vectors(const int32_t* word_id, const int32_t* node_id, const double* weight, int n,
                      int32_t* bow_word, double* bow_value, int bow_cap, int* bow_n,
                      int32_t* fv_node, int32_t* fv_start, int32_t* fv_idx, int fv_cap, int* fv_n);
+/* Tracking::TrackReferenceKeyFrame's matcher part (ORB/src/Tracking.cc:1159-1176) for n_pairs (reference keyframe, current frame) pairs
+ * of gather records, on the device from end to end: the fallback of a frame that ivf_tracker_run could not track (no velocity, or fewer
+ * than 20 matches after the retry, Tracking.cc:556-577).  Frame::ComputeBoW (Tracking.cc:1168) is reduced to what the search reads:
+ * mFeatVec of both records of every pair, i.e. the node at level L - levelsup of every keypoint (TemplatedVocabulary.h:1217-1259; a
+ * keypoint whose word has weight 0 enters no node, :1157), node ids ascending, features ascending inside a node; mBowVec is not
+ * computed.  Then ORBmatcher(nn_ratio, check_orientation).SearchByBoW(mpReferenceKF, mCurrentFrame, vpMapPointMatches)
+ * (ORB/src/ORBmatcher.cc:165-294; the reference calls it with 0.7, true) and, when the quality arrays are given,
+ * UpdateQualityScores(mCurrentFrame) (Tracking.cc:1174-1176).  Results are those of ivf_bow_transform + ivf_bow_vectors +
+ * ivf_search_by_bow on the same data, bit for bit.
+ * d_pairs [n_pairs][2] = (keyframe record, current record); d_select [n_pairs] (nullable): 0 leaves the pair out (d_assign = -1,
+ * d_nmatches = -2) -- a mask a device-side comparison of ivf_tracker_run's d_nmatches produces without a sync; a record index outside
+ * [0, n_records) gives -1 / -1.  d_point_flags [n_records][nfeatures] (nullable), bit 0 = the keypoint holds a live map point
+ * (vpMapPointsKF[i] && !isBad(), :197-203); NULL: every keyframe keypoint with a stereo depth holds one (ivf_tracker_run's default
+ * with th_depth <= 0).  Given flags decide alone: a keyframe's map points need no stereo depth, their positions come from
+ * ivf_tracker_points_from_keyframe's d_kf_xw.  d_point_quality [n_pairs][nfeatures] (indexed by keyframe keypoint) and d_key_quality
+ * [n_pairs][nfeatures] (by frame keypoint): both or neither, in/out.
+ * d_assign [n_pairs][nfeatures]: the keyframe keypoint whose map point frame keypoint i receives, or -1; d_nmatches [n_pairs] = the
+ * return value (the caller applies the < 15 rule of Tracking.cc:1172).  IVF_E_INVALID: a vocabulary on another device than the
+ * tracker, levelsup < 0, n_pairs > max_pairs.  Asynchronous on hip_stream; the feature vectors live in scratch the handle allocated at
+ * ivf_tracker_create, so the call obeys the handle's one-call-at-a-time rule like the other searches. */
+int  ivf_tracker_search_by_bow(ivf_tracker* t, const ivf_vocabulary* voc, int levelsup,
+                               const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_pairs, int n_pairs,
+                               const int32_t* d_select, const uint8_t* d_point_flags, float nn_ratio, int check_orientation,
+                               float* d_point_quality, float* d_key_quality, int32_t* d_assign, int32_t* d_nmatches, void* hip_stream);
+/* The third feeder of ivf_tracker_optimize_pose, after ivf_tracker_search_by_bow on the same d_pairs (Tracking.cc:1173: mvpMapPoints =
+ * vpMapPointMatches): d_xw[p][i] = d_kf_xw[keyframe record of pair p][d_assign[p][i]], d_has_point[p][i] = 1; 0 (and xw = 0) where
+ * d_assign is -1 or the keyframe record index is outside [0, n_records).  d_kf_xw [n_records][nfeatures][3] = GetWorldPos() of the map
+ * point each keypoint of each record holds.  The frames to optimise are the pairs' current records.  Asynchronous on hip_stream. */
+int  ivf_tracker_points_from_keyframe(ivf_tracker* t, const int32_t* d_pairs, int n_pairs, int n_records, const float* d_kf_xw,
+                                      const int32_t* d_assign, float* d_xw, uint8_t* d_has_point, void* hip_stream);
 /* MapPoint::ComputeDistinctiveDescriptors (ORB/src/MapPoint.cc:247-312): desc = the n observed descriptors (rows of
  * vDescriptors, in mObservations order); *best_index = the row to copy into mDescriptor, *best_median (nullable) its median. */
 int  ivf_distinctive_descriptor(const uint8_t* desc, int n, int* best_index, int* best_median, int device_id);

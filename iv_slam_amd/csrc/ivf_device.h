@@ -238,6 +238,34 @@ __device__ __forceinline__ void wave_sync_lds()
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
+// The rotation-consistency filter of the batched searches, the one device text of it (k_track_greedy, k_bow_search): a match falls into
+// one of 30 bins by the angle between its two keypoints (ORBmatcher.cc:244-251, :1476-1484), ComputeThreeMaxima (:1654-1695) keeps up to
+// three bins, every match of another bin is taken back.
+struct RotKeep {
+    int ind1, ind2, ind3;
+    __device__ __forceinline__ bool keeps(int bin) const { return bin == ind1 || bin == ind2 || bin == ind3; }
+};
+__device__ __forceinline__ int rot_bin(float rot)
+{
+    const float factor = 1.0f / 30.0f;                         // 1.0f / HISTO_LENGTH
+    if (rot < 0.0f) rot += 360.0f;
+    int bin = (int)roundf(rot * factor);
+    if (bin == 30) bin = 0;
+    return bin;
+}
+__device__ __forceinline__ RotKeep rot_three_maxima(const int* hist)       // hist [30]: rotHist[b].size()
+{
+    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    for (int b = 0; b < 30; b++) {
+        const int s = hist[b];
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = b; }
+        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = b; }
+        else if (s > max3) { max3 = s; ind3 = b; }
+    }
+    if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
+    return RotKeep{ind1, ind2, ind3};
+}
 // cv::gemm on CV_32F operands: double accumulation of (double)a * (double)b, + (double)c, one narrowing
 __device__ __forceinline__ void mul_add(const float* R, const float* p, const float* t, float* out)
 {
@@ -257,7 +285,7 @@ __device__ __forceinline__ void neg_rt_mul(const float* R, const float* t, float
 // tracker entry point shares, hipSetDevice and the wait for the handle's previous call; tracker_end: the event the next call waits for;
 // v may be null (ivf_track.hip's own entry points)
 struct TrackerView {
-    int nf, nlevels, maxPairs;
+    int nf, nlevels, maxPairs, device;
     size_t recBytes;
     float fx, fy, cx, cy, invfx, invfy, bf;
     float scale[kMaxLevels];

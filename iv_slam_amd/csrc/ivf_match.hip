@@ -11,7 +11,7 @@
 #include <mutex>
 #include <vector>
 #include <algorithm>
-#include "ivf_grid.h"
+#include "ivf_bow.h"
 
 using namespace ivf;
 
@@ -66,8 +66,7 @@ void launch_distinct_median(const uint8_t* desc, int n, int* median, hipStream_t
     hipLaunchKernelGGL(k_distinct_median, dim3(n), dim3(256), 0, s, desc, n, median);
 }
 
-// ---- DBoW2 vocabulary-tree descent (TemplatedVocabulary.h:1217-1259): 16 lanes per descriptor, one child per lane per
-// round, (distance << 16 | position) min-reduction across the 16 lanes = "first minimum in child order"
+// ---- DBoW2 vocabulary-tree descent (TemplatedVocabulary.h:1217-1259): 16 lanes per descriptor, bow_descend (ivf_bow.h)
 __global__ __launch_bounds__(256) void k_bow_transform(const int* __restrict__ childStart, const int* __restrict__ child,
                                                       const uint8_t* __restrict__ nodeDesc, const uint8_t* __restrict__ desc,
                                                       int n, int nidLevel, int* __restrict__ leaf, int* __restrict__ nodeAt)
@@ -76,23 +75,8 @@ __global__ __launch_bounds__(256) void k_bow_transform(const int* __restrict__ c
     const bool live = f < n;
     const uint4* pf = (const uint4*)(desc + (size_t)(live ? f : 0) * 32);
     const uint4 a0 = pf[0], a1 = pf[1];
-    int node = 0, level = 0, nid = 0;
-    for (;;) {
-        const int c0 = childStart[node], c1 = childStart[node + 1];
-        if (c1 == c0) break;                                              // leaf (uniform within the 16 lanes)
-        ++level;
-        unsigned best = 0xffffffffu;
-        for (int c = c0 + sub; c < c1; c += 16) {
-            const int id = child[c];
-            const uint4* pn = (const uint4*)(nodeDesc + (size_t)id * 32);
-            const unsigned key = ((unsigned)hamming256(a0, a1, pn[0], pn[1]) << 16) | (unsigned)(c - c0);
-            best = min(best, key);
-        }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) best = min(best, (unsigned)__shfl_xor((int)best, o, 16));
-        node = child[c0 + (int)(best & 0xffffu)];
-        if (level == nidLevel) nid = node;
-    }
+    int node, nid;
+    bow_descend(childStart, child, nodeDesc, a0, a1, sub, nidLevel, node, nid);
     if (live && sub == 0) { leaf[f] = node; nodeAt[f] = nidLevel <= 0 ? 0 : nid; }
 }
 
@@ -1132,6 +1116,7 @@ int ivf_search_for_triangulation(const ivf_keypoint* kps1, const uint8_t* desc1,
 struct ivf_vocabulary {
     int device = 0, nNodes = 0, depth = 0, maxChildren = 0;
     int *dChildStart = nullptr, *dChild = nullptr; uint8_t* dDesc = nullptr;
+    uint8_t* dLive = nullptr;             // [nNodes] weight > 0: what the batched matcher (ivf_track_bow.hip) needs of the weights
     std::vector<int> word; std::vector<double> weight; std::vector<int> childStart;
 };
 
@@ -1170,10 +1155,16 @@ int ivf_vocabulary_create(int n_nodes, const int32_t* child_start, const int32_t
     v->word.assign(node_word, node_word + n_nodes); v->weight.assign(node_weight, node_weight + n_nodes);
     v->childStart.assign(child_start, child_start + n_nodes + 1);
     if (hipMalloc(&v->dChildStart, (size_t)(n_nodes + 1) * sizeof(int)) != hipSuccess || hipMalloc(&v->dChild, (size_t)std::max(nChild, 1) * sizeof(int)) != hipSuccess ||
-        hipMalloc(&v->dDesc, (size_t)n_nodes * 32) != hipSuccess) { ivf_vocabulary_destroy(v); return fail(IVF_E_NO_DEVICE, "hipMalloc failed for the vocabulary"); }
+        hipMalloc(&v->dDesc, (size_t)n_nodes * 32) != hipSuccess || hipMalloc(&v->dLive, (size_t)n_nodes) != hipSuccess) {
+        ivf_vocabulary_destroy(v);
+        return fail(IVF_E_NO_DEVICE, "hipMalloc failed for the vocabulary");
+    }
+    std::vector<uint8_t> live(n_nodes);
+    for (int i = 0; i < n_nodes; i++) live[i] = node_weight[i] > 0 ? 1 : 0;
     if (hipMemcpy(v->dChildStart, child_start, (size_t)(n_nodes + 1) * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(v->dChild, child, (size_t)nChild * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(v->dDesc, node_desc, (size_t)n_nodes * 32, hipMemcpyHostToDevice) != hipSuccess) {
+        hipMemcpy(v->dDesc, node_desc, (size_t)n_nodes * 32, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v->dLive, live.data(), (size_t)n_nodes, hipMemcpyHostToDevice) != hipSuccess) {
         ivf_vocabulary_destroy(v);
         return fail(IVF_E_NO_DEVICE, "vocabulary upload failed");
     }
@@ -1188,6 +1179,7 @@ void ivf_vocabulary_destroy(ivf_vocabulary* v)
     if (v->dChildStart) (void)hipFree(v->dChildStart);
     if (v->dChild) (void)hipFree(v->dChild);
     if (v->dDesc) (void)hipFree(v->dDesc);
+    if (v->dLive) (void)hipFree(v->dLive);
     delete v;
 }
 
@@ -1285,6 +1277,13 @@ int ivf_update_quality_scores(const int32_t* assign, int n, float* kp_quality, f
 }
 
 }  // extern "C"
+
+int ivf::vocabulary_view(const ivf_vocabulary* v, VocabularyView* out)
+{
+    if (!v || !out) return fail(IVF_E_INVALID, "null vocabulary");
+    *out = VocabularyView{v->device, v->nNodes, v->depth, v->dChildStart, v->dChild, v->dDesc, v->dLive};
+    return IVF_OK;
+}
 
 // The frame half of ivf_frame_create_from_frontend (ivf_api.hip resolves the batch image): keypoints, descriptors and uRight go
 // device -> device on the frame's own stream, the 64x48 grid is built on the device; nothing but the 4-byte keypoint count

@@ -515,6 +515,25 @@ __global__ __launch_bounds__(256) void k_points_from_local(int nf, const ivf_loc
     hasPoint[o] = hp;
 }
 
+// xw[p][i] = GetWorldPos() of the map point that keyframe keypoint assign[p][i] holds (Tracking.cc:1173: mvpMapPoints = vpMapPointMatches)
+__global__ __launch_bounds__(256) void k_points_from_keyframe(int nf, int nRecords, const int2* __restrict__ pairs, const float* __restrict__ kfXw,
+                                                             const int* __restrict__ assign, float* __restrict__ xw, uint8_t* __restrict__ hasPoint)
+{
+    const int p = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nf) return;
+    const size_t o = (size_t)p * nf + i;
+    const int kf = pairs[p].x, a = assign[o];
+    float out[3] = {0.0f, 0.0f, 0.0f};
+    uint8_t hp = 0;
+    if ((unsigned)kf < (unsigned)nRecords && a >= 0 && a < nf) {
+        const float* pos = kfXw + ((size_t)kf * nf + a) * 3;
+        out[0] = pos[0]; out[1] = pos[1]; out[2] = pos[2];
+        hp = 1;
+    }
+    xw[3 * o] = out[0]; xw[3 * o + 1] = out[1]; xw[3 * o + 2] = out[2];
+    hasPoint[o] = hp;
+}
+
 PoseParams pose_params(const TrackerView& v, int n_records)
 {
     PoseParams P;
@@ -573,6 +592,21 @@ int ivf_tracker_points_from_local(ivf_tracker* t, const ivf_local_point* d_point
     const int rc = tracker_begin(t, false, 0, 0, n_frames, st, &v);
     if (rc != IVF_OK) return rc;
     hipLaunchKernelGGL(k_points_from_local, dim3((v.nf + 255) / 256, n_frames), dim3(256), 0, st, v.nf, d_points, d_point_offsets, d_assign, d_xw, d_has_point);
+    return tracker_end(t, st);
+}
+
+int ivf_tracker_points_from_keyframe(ivf_tracker* t, const int32_t* d_pairs, int n_pairs, int n_records, const float* d_kf_xw,
+                                     const int32_t* d_assign, float* d_xw, uint8_t* d_has_point, void* hip_stream)
+{
+    if (!t || !d_pairs || !d_kf_xw || !d_assign || !d_xw || !d_has_point) return fail(IVF_E_INVALID, "null argument");
+    if (n_records < 1) return fail(IVF_E_INVALID, "n_records must be >= 1");
+    if (n_pairs == 0) return IVF_OK;
+    hipStream_t st = (hipStream_t)hip_stream;
+    TrackerView v;
+    const int rc = tracker_begin(t, false, 0, 0, n_pairs, st, &v);
+    if (rc != IVF_OK) return rc;
+    hipLaunchKernelGGL(k_points_from_keyframe, dim3((v.nf + 255) / 256, n_pairs), dim3(256), 0, st, v.nf, n_records, (const int2*)d_pairs, d_kf_xw,
+                       d_assign, d_xw, d_has_point);
     return tracker_end(t, st);
 }
 

@@ -32,7 +32,7 @@
 //                    (lane = bin).  Queries whose window overflowed the list are re-walked in place against the live state.
 // The grid itself -- grid_build / grid_walk, here with unsigned short indices (nfeatures <= 4096) -- is ivf_grid.h's, shared with the
 // device-resident ivf_frame (ivf_match.hip).
-#include "ivf_grid.h"
+#include "ivf_bow.h"
 #include <climits>
 #include <cstring>
 #include <vector>
@@ -248,7 +248,6 @@ __global__ __launch_bounds__(64) void k_track_greedy(TrackParams P, const uint8_
     const Query* Q = queries + (size_t)p * P.nf;
     const int* C = count + (size_t)p * P.nf;
     const unsigned* Lp = lists + (size_t)p * P.nf * kListCap;
-    const float factor = 1.0f / 30.0f;                         // 1.0f / HISTO_LENGTH (:1380)
 
     // r04: a group of 16 queries is evaluated SPECULATIVELY against the live state -- four queries per pass, one per DPP row of 16 lanes
     // (a window holds a handful of candidates: radius 7 px x the octave's scale) -- and the longest PREFIX of the group in which no two
@@ -425,12 +424,7 @@ __global__ __launch_bounds__(64) void k_track_greedy(TrackParams P, const uint8_
         {
             const bool mt = fb >= 0;
             int bin = 0;
-            if (P.checkOri && mt) {
-                float rot = cur.myAng - s_ang[fb];
-                if (rot < 0.0f) rot += 360.0f;
-                bin = (int)roundf(rot * factor);
-                if (bin == 30) bin = 0;
-            }
+            if (P.checkOri && mt) bin = rot_bin(cur.myAng - s_ang[fb]);
             const unsigned long long mm = __ballot(mt);
             if (mt) s_match[nMatch + __popcll(mm & ((1ull << lane) - 1ull))] = (unsigned)fb | ((unsigned)bin << 16);
             if (P.checkOri && mt) atomicAdd(&s_hist[bin], 1);
@@ -457,15 +451,7 @@ __global__ __launch_bounds__(64) void k_track_greedy(TrackParams P, const uint8_
 #endif
     // ---- rotation consistency: ComputeThreeMaxima (:1654-1695) over the 30 bins, matches of every other bin are taken back
     if (P.checkOri) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int b = 0; b < 30; b++) {
-            const int s = s_hist[b];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = b; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = b; }
-            else if (s > max3) { max3 = s; ind3 = b; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
+        const RotKeep keep = rot_three_maxima(s_hist);
         __builtin_amdgcn_wave_barrier();
         int removed = 0;
         for (int m0 = 0; m0 < nMatch; m0 += 64) {
@@ -474,7 +460,7 @@ __global__ __launch_bounds__(64) void k_track_greedy(TrackParams P, const uint8_
             if (m < nMatch) {
                 const unsigned e = s_match[m];
                 const int bin = (int)(e >> 16);
-                rm = bin != ind1 && bin != ind2 && bin != ind3;
+                rm = !keep.keeps(bin);
                 if (rm) s_assign[e & 0xffff] = -1;                                      // :1504
             }
             removed += __popcll(__ballot(rm));
@@ -820,6 +806,7 @@ struct ivf_tracker {
     unsigned* dLists = nullptr;
     // scratch of ivf_tracker_search_local, sized at its first call / grown on demand: [max_pairs][localCap] queries, radii, counts, lists
     Query* dLQ = nullptr; float* dLRad = nullptr; int* dLCount = nullptr; unsigned* dLLists = nullptr; int localCap = 0;
+    TrackerBowScratch bow{nullptr, nullptr, nullptr, nullptr, nullptr};   // ivf_tracker_search_by_bow (ivf_track_bow.hip): [2 * max_pairs] slots
     size_t ldsBytes = 0;
     hipEvent_t evDone = nullptr;          // end of the previous run: the scratch above belongs to ONE run at a time
     bool ran = false;
@@ -837,11 +824,12 @@ int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n
     if (t->ran) HIPCHK(hipStreamWaitEvent(st, t->evDone, 0));                          // the handle runs one call at a time
     if (!v) return IVF_OK;                                                            // this file's own entry points read t->P themselves
     const TrackParams& P = t->P;
-    v->nf = P.nf; v->nlevels = P.nlevels; v->maxPairs = t->cfg.max_pairs; v->recBytes = P.recBytes;
+    v->nf = P.nf; v->nlevels = P.nlevels; v->maxPairs = t->cfg.max_pairs; v->device = t->cfg.device_id; v->recBytes = P.recBytes;
     v->fx = P.fx; v->fy = P.fy; v->cx = P.cx; v->cy = P.cy; v->invfx = P.invfx; v->invfy = P.invfy; v->bf = P.bf;
     for (int l = 0; l < kMaxLevels; l++) v->scale[l] = P.scale[l];
     return IVF_OK;
 }
+TrackerBowScratch tracker_bow_scratch(ivf_tracker* t) { return t->bow; }
 int tracker_end(ivf_tracker* t, hipStream_t st)
 {
     HIPCHK(hipGetLastError());
@@ -862,7 +850,8 @@ void ivf_tracker_destroy(ivf_tracker* t)
 {
     if (!t) return;
     (void)hipSetDevice(t->cfg.device_id);
-    void* ptrs[] = {t->dStart, t->dCount, t->dRetry, t->dIdx, t->dQ, t->dLists, t->dLQ, t->dLRad, t->dLCount, t->dLLists};
+    void* ptrs[] = {t->dStart, t->dCount, t->dRetry, t->dIdx, t->dQ, t->dLists, t->dLQ, t->dLRad, t->dLCount, t->dLLists,
+                    t->bow.nodeKey, t->bow.fvNode, t->bow.fvStart, t->bow.fvIdx, t->bow.fvN};
     for (void* q : ptrs) if (q) (void)hipFree(q);
     if (t->evDone) (void)hipEventDestroy(t->evDone);
     delete t;
@@ -900,7 +889,10 @@ int ivf_tracker_create(const ivf_track_config* cfg, ivf_tracker** out)
     t->ldsBytes = nf * 20;
     if (hipMalloc(&t->dStart, np * (kGC * kGR + 1) * sizeof(int)) != hipSuccess || hipMalloc(&t->dIdx, np * nf * sizeof(unsigned short)) != hipSuccess ||
         hipMalloc(&t->dQ, np * nf * sizeof(Query)) != hipSuccess || hipMalloc(&t->dCount, np * nf * sizeof(int)) != hipSuccess ||
-        hipMalloc(&t->dLists, np * nf * kListCap * sizeof(unsigned)) != hipSuccess || hipMalloc(&t->dRetry, np * sizeof(int)) != hipSuccess) {
+        hipMalloc(&t->dLists, np * nf * kListCap * sizeof(unsigned)) != hipSuccess || hipMalloc(&t->dRetry, np * sizeof(int)) != hipSuccess ||
+        hipMalloc(&t->bow.nodeKey, 2 * np * nf * sizeof(int)) != hipSuccess || hipMalloc(&t->bow.fvNode, 2 * np * nf * sizeof(int)) != hipSuccess ||
+        hipMalloc(&t->bow.fvStart, 2 * np * (nf + 1) * sizeof(int)) != hipSuccess || hipMalloc(&t->bow.fvIdx, 2 * np * nf * sizeof(int)) != hipSuccess ||
+        hipMalloc(&t->bow.fvN, 2 * np * sizeof(int)) != hipSuccess) {
         ivf_tracker_destroy(t);
         return fail(IVF_E_NO_DEVICE, "device allocation failed for a tracker of %d pairs x %d features", cfg->max_pairs, cfg->nfeatures);
     }

@@ -1,0 +1,301 @@
+// ivf_track_bow.hip -- batched, device-resident matcher part of Tracking::TrackReferenceKeyFrame (ORB/src/Tracking.cc:1154-1250), the
+// fallback of a frame that ivf_tracker_run could not track: for every (reference keyframe, current frame) pair of gather records
+//   * Frame::ComputeBoW (Tracking.cc:1168, ORB/src/Frame.cc:683-694) reduced to what the search reads of it: mFeatVec, the node at level
+//     L - levelsup of every keypoint's descriptor (TemplatedVocabulary.h:1217-1259), features of a node in ascending order
+//     (FeatureVector.cpp:31-45); mBowVec is not computed;
+//   * ORBmatcher(nn_ratio, check_orientation).SearchByBoW(mpReferenceKF, mCurrentFrame, vpMapPointMatches) (ORB/src/ORBmatcher.cc:165-294);
+//   * ORBmatcher::UpdateQualityScores(mCurrentFrame) (Tracking.cc:1174-1176, ORBmatcher.cc:1108-1121) when the quality arrays are given.
+// Nothing crosses PCIe and nothing is replayed on the host.  The search parallelises exactly: a FeatureVector holds every feature in
+// exactly one node, and the loop's only serial dependence -- `if(vpMapPointMatches[realIdxF]) continue;` (:215) -- links keyframe
+// features of the SAME node only.  Nodes are independent (whichever wave takes whichever node, in whatever order, the result is the
+// same); inside a node one wave walks the keyframe features in list order with the frame's features in its lanes.  The rotation
+// histogram needs the bin counts and the members of each bin, not the push order.
+//
+// Kernels (gfx950, wave = 64; no workgroup waits for another, every loop is bounded by nfeatures or by the node count):
+//   k_bow_nodes    16 lanes per keypoint of every record slot (2 * pair + side): bow_descend (ivf_bow.h), the per-call transform's descent
+//   k_bow_featvec  one workgroup per slot: bitonic sort of the unique 64-bit keys (node id << 32 | feature index) in LDS, run starts by a
+//                  block scan -> the CSR feature vector in the handle's scratch
+//   k_bow_search   one workgroup per pair: node merge (binary search of every keyframe node in the frame's list: only equal ids match,
+//                  the lower_bound walk of :186-270), the common nodes handed to the four waves one at a time, the greedy walk,
+//                  the rotation filter (rot_bin / rot_three_maxima, ivf_device.h), the quality epilogue
+#include "ivf_bow.h"
+
+using namespace ivf;
+
+namespace {
+
+#define DEVINL __device__ __forceinline__
+
+struct BowParams {
+    int nf, nRecords, nidLevel, checkOri;
+    size_t recBytes;
+    float nnRatio;
+};
+DEVINL bool rec_ok(const BowParams& P, int r) { return (unsigned)r < (unsigned)P.nRecords; }
+// a pair takes part when the mask selects it and both record indices lie inside the block
+DEVINL bool pair_live(const BowParams& P, const int2 pr, const int* __restrict__ select, int p)
+{
+    return (!select || select[p] != 0) && rec_ok(P, pr.x) && rec_ok(P, pr.y);
+}
+
+__global__ __launch_bounds__(256) void k_bow_nodes(BowParams P, VocabularyView V, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
+                                                  const int* __restrict__ select, int* __restrict__ nodeKey)
+{
+    const int s = blockIdx.y, p = s >> 1, tid = threadIdx.x;
+    const int2 pr = pairs[p];
+    if (!pair_live(P, pr, select, p)) return;
+    const uint8_t* rec = records + (size_t)((s & 1) ? pr.y : pr.x) * P.recBytes;
+    const int n = rec_count(rec, P.nf);
+    if ((int)blockIdx.x * 16 >= n) return;
+    const int f = blockIdx.x * 16 + (tid >> 4), sub = tid & 15;
+    const bool live = f < n;
+    const uint4* pf = (const uint4*)(rec_desc(rec, P.nf) + (size_t)(live ? f : 0) * 32);
+    const uint4 a0 = pf[0], a1 = pf[1];
+    int leaf, nid;
+    bow_descend(V.childStart, V.child, V.nodeDesc, a0, a1, sub, P.nidLevel, leaf, nid);
+    // a stopped word (weight 0) adds neither to mBowVec nor to mFeatVec (TemplatedVocabulary.h:1157)
+    if (live && sub == 0) nodeKey[(size_t)s * P.nf + f] = V.wordLive[leaf] ? (P.nidLevel <= 0 ? 0 : nid) : -1;
+}
+
+__global__ __launch_bounds__(256) void k_bow_featvec(BowParams P, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
+                                                    const int* __restrict__ select, TrackerBowScratch B)
+{
+    extern __shared__ unsigned long long s_key[];             // [npad]: node id << 32 | feature index, ~0 = padding / stopped word
+    __shared__ int part[256];
+    __shared__ int s_m;
+    const int s = blockIdx.x, p = s >> 1, tid = threadIdx.x;
+    const int2 pr = pairs[p];
+    if (!pair_live(P, pr, select, p)) return;
+    const uint8_t* rec = records + (size_t)((s & 1) ? pr.y : pr.x) * P.recBytes;
+    const int n = rec_count(rec, P.nf);
+    unsigned npad = 256;
+    while ((int)npad < n) npad <<= 1;                         // <= the power of two the launch sized the LDS for (n <= nf)
+    if (tid == 0) s_m = 0;
+    __syncthreads();
+    const int* keyIn = B.nodeKey + (size_t)s * P.nf;
+    int mine = 0;
+    for (unsigned i = tid; i < npad; i += 256) {
+        unsigned long long key = ~0ull;
+        if ((int)i < n) { const int k = keyIn[i]; if (k >= 0) { key = ((unsigned long long)(unsigned)k << 32) | i; mine++; } }
+        s_key[i] = key;
+    }
+    atomicAdd(&s_m, mine);
+    __syncthreads();
+    // the keys are unique: sorting them is the stable sort of the node ids, i.e. std::map order with addFeature's push order inside a node
+    for (unsigned k = 2; k <= npad; k <<= 1)
+        for (unsigned j = k >> 1; j > 0; j >>= 1) {
+            for (unsigned t = tid; t < npad / 2; t += 256) {
+                const unsigned i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const unsigned long long a = s_key[i], b = s_key[l];
+                if ((a > b) == ((i & k) == 0)) { s_key[i] = b; s_key[l] = a; }
+            }
+            __syncthreads();
+        }
+    const int m = s_m;                                        // features in the vector: the first m sorted keys
+    const int per = (int)(npad >> 8), j0 = tid * per;
+    auto starts = [&](int j) { return j < m && (j == 0 || (unsigned)(s_key[j - 1] >> 32) != (unsigned)(s_key[j] >> 32)); };
+    int cnt = 0;
+    for (int j = j0; j < j0 + per; j++) cnt += starts(j) ? 1 : 0;
+    part[tid] = cnt;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int v = tid >= off ? part[tid - off] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int k = part[tid] - cnt;
+    int* nodeOut = B.fvNode + (size_t)s * P.nf;
+    int* startOut = B.fvStart + (size_t)s * (P.nf + 1);
+    int* idxOut = B.fvIdx + (size_t)s * P.nf;
+    for (int j = j0; j < j0 + per; j++) {
+        if (j >= m) break;
+        const unsigned long long key = s_key[j];
+        idxOut[j] = (int)(unsigned)key;
+        if (starts(j)) { nodeOut[k] = (int)(unsigned)(key >> 32); startOut[k] = j; k++; }
+    }
+    if (tid == 0) { const int total = part[255]; startOut[total] = m; B.fvN[s] = total; }
+}
+
+DEVINL uint4 readlane4(const uint4 v, int k)
+{
+    return make_uint4((unsigned)__builtin_amdgcn_readlane((int)v.x, k), (unsigned)__builtin_amdgcn_readlane((int)v.y, k),
+                      (unsigned)__builtin_amdgcn_readlane((int)v.z, k), (unsigned)__builtin_amdgcn_readlane((int)v.w, k));
+}
+
+__global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
+                                                   const int* __restrict__ select, const uint8_t* __restrict__ pointFlags, TrackerBowScratch B,
+                                                   float* __restrict__ pointQuality, float* __restrict__ keyQuality,
+                                                   int* __restrict__ assignOut, int* __restrict__ nmatchesOut)
+{
+    extern __shared__ int s_mem[];
+    int* s_assign = s_mem;                                    // [nf] vpMapPointMatches as keyframe keypoint | bin << 16, or -1
+    int* s_common = s_mem + P.nf;                             // [nf] nodes on both sides: position in the keyframe's list | the frame's << 12
+    __shared__ int s_hist[32];                                // rotHist[b].size()
+    __shared__ int s_nCommon, s_next, s_nm;
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    int* out = assignOut + (size_t)p * P.nf;
+    const int2 pr = pairs[p];
+    if (!pair_live(P, pr, select, p)) {
+        for (int i = tid; i < P.nf; i += 256) out[i] = -1;
+        if (tid == 0) nmatchesOut[p] = (select && select[p] == 0) ? -2 : -1;
+        return;
+    }
+    const uint8_t* recK = records + (size_t)pr.x * P.recBytes;
+    const uint8_t* recF = records + (size_t)pr.y * P.recBytes;
+    const int nF = rec_count(recF, P.nf);
+    const size_t sK = 2 * (size_t)p, sF = sK + 1;
+    const int* nodeK = B.fvNode + sK * P.nf; const int* nodeF = B.fvNode + sF * P.nf;
+    const int* startK = B.fvStart + sK * (P.nf + 1); const int* startF = B.fvStart + sF * (P.nf + 1);
+    const int* idxK = B.fvIdx + sK * P.nf; const int* idxF = B.fvIdx + sF * P.nf;
+    const int nnK = B.fvN[sK], nnF = B.fvN[sF];
+    for (int i = tid; i < nF; i += 256) s_assign[i] = -1;
+    if (tid < 32) s_hist[tid] = 0;
+    if (tid == 0) { s_nCommon = 0; s_next = 0; s_nm = 0; }
+    __syncthreads();
+    // ---- node merge (:186-270): a keyframe node takes part when the frame's ascending list holds the same id
+    for (int a = tid; a < nnK; a += 256) {
+        const int id = nodeK[a];
+        int lo = 0, hi = nnF;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (nodeF[mid] < id) lo = mid + 1; else hi = mid; }
+        if (lo < nnF && nodeF[lo] == id) s_common[atomicAdd(&s_nCommon, 1)] = a | (lo << 12);
+    }
+    __syncthreads();
+    const int nCommon = s_nCommon;
+    const ivf_keypoint* kK = rec_kps(recK);
+    const ivf_keypoint* kF = rec_kps(recF);
+    const uint8_t* dK = rec_desc(recK, P.nf);
+    const uint8_t* dF = rec_desc(recF, P.nf);
+    const float* zK = rec_depth(recK, P.nf);
+    const uint8_t* fl = pointFlags ? pointFlags + (size_t)pr.x * P.nf : nullptr;
+    int nmWave = 0;
+    for (;;) {
+        int c = 0;
+        if (lane == 0) c = atomicAdd(&s_next, 1);
+        c = __builtin_amdgcn_readfirstlane(c);
+        if (c >= nCommon) break;
+        const int e = s_common[c], a = e & 0xfff, b = e >> 12;
+        const int ks = startK[a], ke = startK[a + 1], fs = startF[b], nFn = startF[b + 1] - fs;      // both runs hold at least one feature
+        // the frame's first 64 features of the node stay in registers for every keyframe feature of the node; all loads of a lane are
+        // unconditional, at an index clamped into the run, and requested before the first reduction reads them
+        const int iF0 = idxF[fs + min(lane, nFn - 1)];
+        const uint4* pf0 = (const uint4*)(dF + (size_t)iF0 * 32);
+        const uint4 fa0 = pf0[0], fb0 = pf0[1];
+        const float ang0 = kF[iF0].angle;
+        for (int k0 = ks; k0 < ke; k0 += 64) {
+            // 64 keyframe features at once: index, map point, descriptor and angle of feature k0 + lane, broadcast from its lane in turn
+            const int i1L = idxK[min(k0 + lane, ke - 1)];
+            const bool pointL = fl ? (fl[i1L] & 1) != 0 : zK[i1L] > 0;
+            const uint4* pk = (const uint4*)(dK + (size_t)i1L * 32);
+            const uint4 kaL = pk[0], kbL = pk[1];
+            const float angL = kK[i1L].angle;
+            unsigned long long todo = __ballot(k0 + lane < ke && pointL);                          // :199-203
+            while (todo) {
+                const int k = __ffsll((long long)todo) - 1;
+                todo &= todo - 1;
+                const uint4 qa = readlane4(kaL, k), qb = readlane4(kbL, k);
+                const int i1 = __builtin_amdgcn_readlane(i1L, k);
+                const float angK = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, angL), k));
+                // per lane over its strides: the smallest (distance, list position) and the smallest distance among its others
+                unsigned bestKey = 0xffffffffu; int second = 256, bestI = 0; float bestAng = 0.0f;
+                for (int q = 0; q < nFn; q += 64) {
+                    int iF = iF0; uint4 fa = fa0, fb = fb0; float ang = ang0;
+                    if (q) {
+                        iF = idxF[fs + min(q + lane, nFn - 1)];
+                        const uint4* pf = (const uint4*)(dF + (size_t)iF * 32);
+                        fa = pf[0]; fb = pf[1]; ang = kF[iF].angle;
+                    }
+                    const bool free_ = q + lane < nFn && s_assign[iF] < 0;                         // :215
+                    const unsigned d = (unsigned)hamming256(qa, qb, fa, fb);
+                    const unsigned key = free_ ? (d << 12) | (unsigned)(q + lane) : 0xffffffffu;
+                    if (key < bestKey) { second = min(second, (int)min(bestKey >> 12, 256u)); bestKey = key; bestI = iF; bestAng = ang; }
+                    else second = min(second, (int)min(key >> 12, 256u));
+                }
+                // :222-231: bestDist1 = the first minimum in list order (strict <), bestDist2 = the smallest distance of all the others
+                const unsigned best = wave_min_u32(bestKey);
+                if (best == 0xffffffffu) continue;                                                  // every candidate taken
+                const int who = __ffsll((long long)__ballot(bestKey == best)) - 1;
+                const int bestDist1 = (int)(best >> 12);
+                const int bestDist2 = (int)wave_min_u32(lane == who ? (unsigned)second : min(bestKey >> 12, 256u));
+                if (bestDist1 <= 50 && (float)bestDist1 < P.nnRatio * (float)bestDist2) {           // TH_LOW, mfNNratio (:234-236)
+                    const int bestIdxF = __builtin_amdgcn_readlane(bestI, who);
+                    int bin = 0;
+                    if (P.checkOri) bin = rot_bin(angK - __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bestAng), who)));
+                    if (lane == 0) {
+                        s_assign[bestIdxF] = i1 | (bin << 16);                                       // seen by the next keyframe feature of this node
+                        if (P.checkOri) atomicAdd(&s_hist[bin], 1);
+                    }
+                    nmWave++;
+                    wave_sync_lds();
+                }
+            }
+        }
+    }
+    if (lane == 0 && nmWave) atomicAdd(&s_nm, nmWave);
+    __syncthreads();
+    if (P.checkOri) {
+        const RotKeep keep = rot_three_maxima(s_hist);                                              // :273-291
+        int removed = 0;
+        for (int i = tid; i < nF; i += 256) {
+            const int a = s_assign[i];
+            if (a >= 0 && !keep.keeps(a >> 16)) { s_assign[i] = -1; removed++; }
+        }
+        if (removed) atomicSub(&s_nm, removed);
+        __syncthreads();
+    }
+    for (int i = tid; i < P.nf; i += 256) { const int a = i < nF ? s_assign[i] : -1; out[i] = a < 0 ? -1 : (a & 0xffff); }
+    if (pointQuality && keyQuality) {
+        // UpdateQualityScores(mCurrentFrame) (Tracking.cc:1174-1176; the rule of k_track_greedy's epilogue).  A keyframe point ends on at
+        // most one frame keypoint: the reference's sequential loop has no cross-iteration dependence here.
+        float* pq = pointQuality + (size_t)p * P.nf;
+        float* kq = keyQuality + (size_t)p * P.nf;
+        for (int i = tid; i < nF; i += 256) {
+            const int a = s_assign[i];
+            if (a < 0) continue;
+            const int m = a & 0xffff;
+            const float mq = pq[m], upd = fminf(mq, kq[i]);
+            if (fabsf(upd - mq) > 0.01f) pq[m] = upd;                                             // kDeltaThresh
+            kq[i] = upd;
+        }
+    }
+    if (tid == 0) nmatchesOut[p] = s_nm;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ivf_tracker_search_by_bow(ivf_tracker* t, const ivf_vocabulary* voc, int levelsup, const uint8_t* d_records, size_t record_bytes, int n_records,
+                              const int32_t* d_pairs, int n_pairs, const int32_t* d_select, const uint8_t* d_point_flags, float nn_ratio,
+                              int check_orientation, float* d_point_quality, float* d_key_quality, int32_t* d_assign, int32_t* d_nmatches,
+                              void* hip_stream)
+{
+    if (!t || !voc || !d_records || !d_pairs || !d_assign || !d_nmatches) return fail(IVF_E_INVALID, "null argument");
+    if (((size_t)d_records & 15) != 0) return fail(IVF_E_INVALID, "the record block must be 16-byte aligned");
+    if (levelsup < 0) return fail(IVF_E_INVALID, "levelsup %d is negative", levelsup);
+    if (!(nn_ratio > 0)) return fail(IVF_E_INVALID, "nn_ratio must be positive");
+    if ((d_point_quality == nullptr) != (d_key_quality == nullptr)) return fail(IVF_E_INVALID, "d_point_quality and d_key_quality come together");
+    VocabularyView V;
+    int rc = vocabulary_view(voc, &V);
+    if (rc != IVF_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    TrackerView v;
+    rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st, &v);
+    if (rc != IVF_OK) return rc;
+    if (V.device != v.device) return fail(IVF_E_INVALID, "the vocabulary lives on device %d, the tracker on device %d", V.device, v.device);
+    if (n_pairs == 0) return IVF_OK;
+    BowParams P;
+    P.nf = v.nf; P.nRecords = n_records; P.nidLevel = V.depth - levelsup; P.checkOri = check_orientation ? 1 : 0;
+    P.recBytes = v.recBytes; P.nnRatio = nn_ratio;
+    const TrackerBowScratch B = tracker_bow_scratch(t);
+    const int2* pairs = (const int2*)d_pairs;
+    size_t npad = 256;
+    while (npad < (size_t)v.nf) npad <<= 1;                   // nfeatures <= 4096: at most 32 KB of keys
+    hipLaunchKernelGGL(k_bow_nodes, dim3((v.nf + 15) / 16, 2 * n_pairs), dim3(256), 0, st, P, V, d_records, pairs, d_select, B.nodeKey);
+    hipLaunchKernelGGL(k_bow_featvec, dim3(2 * n_pairs), dim3(256), npad * sizeof(unsigned long long), st, P, d_records, pairs, d_select, B);
+    hipLaunchKernelGGL(k_bow_search, dim3(n_pairs), dim3(256), (size_t)v.nf * 2 * sizeof(int), st, P, d_records, pairs, d_select, d_point_flags, B,
+                       d_point_quality, d_key_quality, d_assign, d_nmatches);
+    return tracker_end(t, st);
+}
+
+}  // extern "C"

@@ -107,6 +107,45 @@ class BatchTracker:
         check(self._lib.ivf_tracker_points_from_local(self._h, points.data_ptr(), point_offsets.data_ptr(), assign.data_ptr(), n_frames,
                                                       xw.data_ptr(), has_point.data_ptr(), stream_ptr))
 
+    def search_by_bow(self, vocabulary, records, pairs, assign, nmatches, levelsup=4, select=None, point_flags=None, nn_ratio=0.7,
+                      check_orientation=True, point_quality=None, key_quality=None, stream_ptr=None):
+        """Tracking::TrackReferenceKeyFrame's matcher part (ORB/src/Tracking.cc:1159-1176) for n_pairs (keyframe, current) record pairs:
+        Frame::ComputeBoW reduced to mFeatVec, ORBmatcher(nn_ratio, check_orientation).SearchByBoW (ORB/src/ORBmatcher.cc:165-294) and,
+        with the quality arrays, UpdateQualityScores -- the fallback of the pairs run() could not track.  vocabulary: an ORBVocabulary on
+        the tracker's device; pairs: torch.int32 [n_pairs, 2] = (keyframe record, current record); select: torch.int32 [n_pairs] or None,
+        0 leaves a pair out (assign -1, nmatches -2), e.g. (run's nmatches < 20).to(torch.int32); point_flags: torch.uint8
+        [n_records, nfeatures], bit 0 = the keypoint holds a live map point, or None = every keypoint with a stereo depth;
+        point_quality (by keyframe keypoint) / key_quality (by frame keypoint): torch.float32 [n_pairs, nfeatures] in/out or None;
+        assign: torch.int32 [n_pairs, nfeatures] = the keyframe keypoint whose point the frame keypoint receives or -1; nmatches:
+        torch.int32 [n_pairs].  Asynchronous on the given stream."""
+        n_rec = records.numel() // self.record_bytes
+        n_pairs = pairs.shape[0]
+        assert pairs.dtype.is_floating_point is False and pairs.element_size() == 4 and pairs.is_contiguous()
+        assert assign.element_size() == 4 and assign.numel() >= n_pairs * self.nfeatures and nmatches.numel() >= n_pairs
+        assert select is None or (select.element_size() == 4 and select.is_contiguous() and select.numel() >= n_pairs)
+        assert point_flags is None or (point_flags.element_size() == 1 and point_flags.numel() >= n_rec * self.nfeatures)
+        for q in (point_quality, key_quality):
+            assert q is None or (q.is_contiguous() and q.element_size() == 4 and q.numel() >= n_pairs * self.nfeatures)
+        check(self._lib.ivf_tracker_search_by_bow(self._h, vocabulary._h, int(levelsup), records.data_ptr(), self.record_bytes, n_rec,
+                                                  pairs.data_ptr(), n_pairs, None if select is None else select.data_ptr(),
+                                                  None if point_flags is None else point_flags.data_ptr(), float(nn_ratio),
+                                                  int(bool(check_orientation)),
+                                                  None if point_quality is None else point_quality.data_ptr(),
+                                                  None if key_quality is None else key_quality.data_ptr(),
+                                                  assign.data_ptr(), nmatches.data_ptr(), stream_ptr))
+
+    def points_from_keyframe(self, pairs, kf_xw, assign, xw, has_point, stream_ptr=None):
+        """The map points behind search_by_bow()'s assignments: xw[p, i] = kf_xw[keyframe record of pair p, assign[p, i]], has_point = 1
+        where there is one.  kf_xw: torch.float32 [n_records, nfeatures, 3] = GetWorldPos() of the point each keypoint of each record
+        holds; pairs / assign as search_by_bow() took and wrote them.  Asynchronous."""
+        n_pairs = pairs.shape[0]
+        n_rec = kf_xw.numel() // (self.nfeatures * 3)
+        assert pairs.element_size() == 4 and pairs.is_contiguous() and assign.element_size() == 4 and assign.numel() >= n_pairs * self.nfeatures
+        assert kf_xw.is_contiguous() and kf_xw.element_size() == 4 and kf_xw.numel() == n_rec * self.nfeatures * 3
+        assert xw.element_size() == 4 and xw.numel() >= n_pairs * self.nfeatures * 3 and has_point.element_size() == 1 and has_point.numel() >= n_pairs * self.nfeatures
+        check(self._lib.ivf_tracker_points_from_keyframe(self._h, pairs.data_ptr(), n_pairs, n_rec, kf_xw.data_ptr(), assign.data_ptr(),
+                                                         xw.data_ptr(), has_point.data_ptr(), stream_ptr))
+
     def optimize_pose(self, records, frames, xw, has_point, poses, outlier, ninliers, quality=None, n_rounds=4, chi2=None, stream_ptr=None):
         """Optimizer::PoseOptimization (ORB/src/Optimizer.cc:251-503) for n_frames frames in one kernel launch.  frames: torch.int32
         [n_frames] record indices; xw: torch.float32 [n_frames, nfeatures, 3] world position of the point each keypoint holds;
