@@ -1,6 +1,6 @@
 // ivf_bow.h -- what the per-call DBoW2 transform (ivf_match.hip, which alone knows struct ivf_vocabulary) and the batched
-// TrackReferenceKeyFrame matcher (ivf_track_bow.hip) share: the one device text of the vocabulary-tree descent and the views through
-// which ivf_track_bow.hip reaches the vocabulary and the tracker handle's feature-vector scratch.
+// TrackReferenceKeyFrame matcher (ivf_track_bow.hip) share: the one device text of the vocabulary-tree descent, the view through
+// which ivf_track_bow.hip reaches the vocabulary, and the kernel-argument struct of the tracker handle's feature-vector scratch.
 #pragma once
 #include "ivf_grid.h"
 
@@ -43,10 +43,9 @@ struct VocabularyView {
 };
 int vocabulary_view(const ivf_vocabulary* v, VocabularyView* out);
 
-// The handle's scratch of ivf_tracker_search_by_bow, allocated by ivf_tracker_create: slot s = 2 * pair + side (0 = keyframe, 1 = current
+// The handle's scratch of ivf_tracker_search_by_bow (struct ivf_tracker, ivf_tracker.h), allocated by ivf_tracker_create: slot s = 2 * pair + side (0 = keyframe, 1 = current
 // frame).  nodeKey [slots][nf]: node id per keypoint (-1: stopped word); the feature vector in CSR form: fvNode [slots][nf] ascending,
 // fvStart [slots][nf + 1], fvIdx [slots][nf] ascending inside a node, fvN [slots] nodes.
 struct TrackerBowScratch { int *nodeKey, *fvNode, *fvStart, *fvIdx, *fvN; };
-TrackerBowScratch tracker_bow_scratch(ivf_tracker* t);
 
 }  // namespace ivf

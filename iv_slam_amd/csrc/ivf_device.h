@@ -281,21 +281,9 @@ __device__ __forceinline__ void neg_rt_mul(const float* R, const float* t, float
         out[j] = (float)(-((double)R[j] * (double)t[0] + (double)R[3 + j] * (double)t[1] + (double)R[6 + j] * (double)t[2]));
 }
 
-// what ivf_pose.hip needs of a tracker handle (ivf_track.hip alone knows struct ivf_tracker).  tracker_begin: the argument checks every
-// tracker entry point shares, hipSetDevice and the wait for the handle's previous call; tracker_end: the event the next call waits for;
-// v may be null (ivf_track.hip's own entry points)
-struct TrackerView {
-    int nf, nlevels, maxPairs, device;
-    size_t recBytes;
-    float fx, fy, cx, cy, invfx, invfy, bf;
-    float scale[kMaxLevels];
-};
-int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n_records, int n_items, hipStream_t st, TrackerView* v);
-int tracker_end(ivf_tracker* t, hipStream_t st);
-
 }  // namespace ivf
 
-// error returns of the host code (ivf_api.hip, ivf_match.hip, ivf_track.hip)
+// error returns of the host code
 #define fail ivf::set_error
 #define HIPCHK(expr)                                                                                   \
     do { hipError_t e_ = (expr);                                                                        \

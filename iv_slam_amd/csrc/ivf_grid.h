@@ -1,6 +1,6 @@
 // ivf_grid.h -- the one device text of the frame grid (Frame::AssignFeaturesToGrid / PosInGrid / GetFeaturesInArea,
 // ORB/src/Frame.cc:415-430, :615-680), shared by the device-resident ivf_frame (ivf_match.hip, int indices: the ivf_frame_grid ABI)
-// and the batched tracker (ivf_track.hip, unsigned short indices: nfeatures <= 4096), with the two wave helpers the walk needs
+// and the batched tracker (ivf_track.hip, ivf_track_local.hip; unsigned short indices: nfeatures <= 4096), with the two wave helpers the walk needs
 // (ivf_kernels.hip's stereo matcher uses them too).
 #pragma once
 #include "ivf_device.h"

@@ -1530,7 +1530,7 @@ void launch_stereo(const Config& hc, const Config* dc, const Buffers& b, int nPa
 // ------------------------------------------------------------------------------------------------
 // k_pack_gather: one workgroup = one stereo pair; copies the left frame's {count, keypoints, descriptors, uRight} into
 // one contiguous record {n, kps, desc, uRight, depth} of the all-gather block (depth so that a receiving rank can
-// un-project the frame's stereo points, ivf_track.hip).  A kernel rather than 2-D copies so that packing
+// un-project the frame's stereo points: k_track_prepare, ivf_track.hip).  A kernel rather than 2-D copies so that packing
 // never blocks the host thread that keeps the next batches enqueued.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pack_gather(const int* __restrict__ count, const ivf_keypoint* __restrict__ kps,

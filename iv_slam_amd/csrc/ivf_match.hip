@@ -2,7 +2,7 @@
 // DBoW2 vocabulary / BoW vectors, the distinctive descriptor and the quality-score update.
 // Each search builds its candidate lists and Hamming distances on the device (CandSource, node_pairs) and then replays the
 // reference's order-dependent greedy logic on the host.  Its kernels (k_hamming_pairs, k_distinct_median, k_bow_transform, k_grid_build,
-// k_grid_window) are file-local, at the top; the grid they and the batched tracker (ivf_track.hip) share is ivf_grid.h.
+// k_grid_window) are file-local, at the top; the grid they and the batched tracker (ivf_track.hip, ivf_track_local.hip) share is ivf_grid.h.
 #include <cmath>
 #include <climits>
 #include <cstdio>

@@ -1,5 +1,5 @@
 // ivf_pose.hip -- batched, device-resident Optimizer::PoseOptimization (ORB/src/Optimizer.cc:251-503): the consumer of the two batched
-// searches of ivf_track.hip.  g2o's machinery for this call is one 6-dof vertex (VertexSE3Expmap), unary edges
+// searches of ivf_track.hip and ivf_track_local.hip, on the same handle (ivf_tracker.h).  g2o's machinery for this call is one 6-dof vertex (VertexSE3Expmap), unary edges
 // (EdgeSE3ProjectXYZOnlyPose / EdgeStereoSE3ProjectXYZOnlyPose, Thirdparty/g2o/g2o/types/types_six_dof_expmap.{h,cpp}), a dense 6x6
 // system (solvers/linear_solver_dense.h: Eigen::LDLT) and OptimizationAlgorithmLevenberg (core/optimization_algorithm_levenberg.cpp);
 // all of it is restated here in double, the arithmetic the reference runs it in.
@@ -15,7 +15,7 @@
 //                       Loop bounds are compile-time (4 rounds x 10 iterations x 10 trials): NaN input cannot spin the kernel.
 //   k_points_from_pairs Frame::UnprojectStereo (ORB/src/Frame.cc:958-972) of the last-frame keypoint every current keypoint was assigned
 //   k_points_from_local GetWorldPos() of the local map point every keypoint was assigned
-#include "ivf_device.h"
+#include "ivf_tracker.h"
 
 using namespace ivf;
 
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(kThreads) void k_pose_opt(PoseParams Pm, const uint
     float* chiO = chi2Out ? chi2Out + (size_t)f * nf : nullptr;
     for (int i = tid; i < nf; i += kThreads) { outl[i] = 0; if (chiO) chiO[i] = 0.0f; }
     const int ri = frames[f];
-    if ((unsigned)ri >= (unsigned)Pm.nRecords) { if (tid == 0) nInliers[f] = -1; return; }
+    if (!rec_ok(Pm.nRecords, ri)) { if (tid == 0) nInliers[f] = -1; return; }
     const uint8_t* rec = records + (size_t)ri * Pm.recBytes;
     const int nC = rec_count(rec, nf);
     const ivf_keypoint* kps = rec_kps(rec);
@@ -465,22 +465,14 @@ __global__ __launch_bounds__(256) void k_points_from_pairs(PoseParams Pm, float 
     float out[3] = {0.0f, 0.0f, 0.0f};
     uint8_t hp = 0;
     const int2 pr = pairs[p];
-    if ((unsigned)pr.x < (unsigned)Pm.nRecords) {
+    if (rec_ok(Pm.nRecords, pr.x)) {
         const uint8_t* recL = records + (size_t)pr.x * Pm.recBytes;
         const int a = assign[o];
         if (a >= 0 && a < rec_count(recL, Pm.nf)) {
             const float z = rec_depth(recL, Pm.nf)[a];
             if (z > 0) {
                 float Rl[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tl[3] = {0, 0, 0}, Rwl[9], Owl[3], x3[3];
-                if (poses) {
-                    const float* Tl = poses + (size_t)p * 24;
-#pragma unroll
-                    for (int i = 0; i < 3; i++) {
-#pragma unroll
-                        for (int j = 0; j < 3; j++) Rl[3 * i + j] = Tl[4 * i + j];
-                        tl[i] = Tl[4 * i + 3];
-                    }
-                }
+                if (poses) load_pose(poses + (size_t)p * 24, Rl, tl);
 #pragma unroll
                 for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -525,7 +517,7 @@ __global__ __launch_bounds__(256) void k_points_from_keyframe(int nf, int nRecor
     const int kf = pairs[p].x, a = assign[o];
     float out[3] = {0.0f, 0.0f, 0.0f};
     uint8_t hp = 0;
-    if ((unsigned)kf < (unsigned)nRecords && a >= 0 && a < nf) {
+    if (rec_ok(nRecords, kf) && a >= 0 && a < nf) {
         const float* pos = kfXw + ((size_t)kf * nf + a) * 3;
         out[0] = pos[0]; out[1] = pos[1]; out[2] = pos[2];
         hp = 1;
@@ -534,12 +526,12 @@ __global__ __launch_bounds__(256) void k_points_from_keyframe(int nf, int nRecor
     hasPoint[o] = hp;
 }
 
-PoseParams pose_params(const TrackerView& v, int n_records)
+PoseParams pose_params(const TrackParams& T, int n_records)
 {
     PoseParams P;
-    P.nf = v.nf; P.nRecords = n_records; P.recBytes = v.recBytes;
-    P.fx = v.fx; P.fy = v.fy; P.cx = v.cx; P.cy = v.cy; P.bf = v.bf;
-    for (int l = 0; l < kMaxLevels; l++) { const float s2 = v.scale[l] * v.scale[l]; P.invSigma2[l] = 1.0f / s2; }   // mvLevelSigma2, mvInvLevelSigma2
+    P.nf = T.nf; P.nRecords = n_records; P.recBytes = T.recBytes;
+    P.fx = T.fx; P.fy = T.fy; P.cx = T.cx; P.cy = T.cy; P.bf = T.bf;
+    for (int l = 0; l < kMaxLevels; l++) { const float s2 = T.scale[l] * T.scale[l]; P.invSigma2[l] = 1.0f / s2; }   // mvLevelSigma2, mvInvLevelSigma2
     return P;
 }
 
@@ -556,12 +548,11 @@ int ivf_tracker_optimize_pose(ivf_tracker* t, const uint8_t* d_records, size_t r
     if (n_rounds < 1 || n_rounds > kMaxRounds) return fail(IVF_E_INVALID, "n_rounds %d outside [1,%d]", n_rounds, kMaxRounds);
     if (n_frames == 0) return IVF_OK;
     hipStream_t st = (hipStream_t)hip_stream;
-    TrackerView v;
-    const int rc = tracker_begin(t, true, record_bytes, n_records, n_frames, st, &v);
+    const int rc = tracker_begin(t, true, record_bytes, n_records, n_frames, st);
     if (rc != IVF_OK) return rc;
-    const size_t lds = (size_t)v.nf * sizeof(Edge);
+    const size_t lds = (size_t)t->P.nf * sizeof(Edge);
     if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_pose_opt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_pose_opt, dim3(n_frames), dim3(kThreads), lds, st, pose_params(v, n_records), d_records, d_frames, d_xw, d_has_point,
+    hipLaunchKernelGGL(k_pose_opt, dim3(n_frames), dim3(kThreads), lds, st, pose_params(t->P, n_records), d_records, d_frames, d_xw, d_has_point,
                        d_quality, n_rounds, d_poses, d_outlier, d_ninliers, d_chi2);
     return tracker_end(t, st);
 }
@@ -573,10 +564,9 @@ int ivf_tracker_points_from_pairs(ivf_tracker* t, const uint8_t* d_records, size
     if (((size_t)d_records & 15) != 0) return fail(IVF_E_INVALID, "the record block must be 16-byte aligned");
     if (n_pairs == 0) return IVF_OK;
     hipStream_t st = (hipStream_t)hip_stream;
-    TrackerView v;
-    const int rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st, &v);
+    const int rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st);
     if (rc != IVF_OK) return rc;
-    hipLaunchKernelGGL(k_points_from_pairs, dim3((v.nf + 255) / 256, n_pairs), dim3(256), 0, st, pose_params(v, n_records), v.invfx, v.invfy, d_records,
+    hipLaunchKernelGGL(k_points_from_pairs, dim3((t->P.nf + 255) / 256, n_pairs), dim3(256), 0, st, pose_params(t->P, n_records), t->P.invfx, t->P.invfy, d_records,
                        (const int2*)d_pairs, d_poses_pairs, d_assign, d_xw, d_has_point);
     return tracker_end(t, st);
 }
@@ -588,10 +578,9 @@ int ivf_tracker_points_from_local(ivf_tracker* t, const ivf_local_point* d_point
     if (((size_t)d_points & 15) != 0) return fail(IVF_E_INVALID, "the point array must be 16-byte aligned");
     if (n_frames == 0) return IVF_OK;
     hipStream_t st = (hipStream_t)hip_stream;
-    TrackerView v;
-    const int rc = tracker_begin(t, false, 0, 0, n_frames, st, &v);
+    const int rc = tracker_begin(t, false, 0, 0, n_frames, st);
     if (rc != IVF_OK) return rc;
-    hipLaunchKernelGGL(k_points_from_local, dim3((v.nf + 255) / 256, n_frames), dim3(256), 0, st, v.nf, d_points, d_point_offsets, d_assign, d_xw, d_has_point);
+    hipLaunchKernelGGL(k_points_from_local, dim3((t->P.nf + 255) / 256, n_frames), dim3(256), 0, st, t->P.nf, d_points, d_point_offsets, d_assign, d_xw, d_has_point);
     return tracker_end(t, st);
 }
 
@@ -602,10 +591,9 @@ int ivf_tracker_points_from_keyframe(ivf_tracker* t, const int32_t* d_pairs, int
     if (n_records < 1) return fail(IVF_E_INVALID, "n_records must be >= 1");
     if (n_pairs == 0) return IVF_OK;
     hipStream_t st = (hipStream_t)hip_stream;
-    TrackerView v;
-    const int rc = tracker_begin(t, false, 0, 0, n_pairs, st, &v);
+    const int rc = tracker_begin(t, false, 0, 0, n_pairs, st);
     if (rc != IVF_OK) return rc;
-    hipLaunchKernelGGL(k_points_from_keyframe, dim3((v.nf + 255) / 256, n_pairs), dim3(256), 0, st, v.nf, n_records, (const int2*)d_pairs, d_kf_xw,
+    hipLaunchKernelGGL(k_points_from_keyframe, dim3((t->P.nf + 255) / 256, n_pairs), dim3(256), 0, st, t->P.nf, n_records, (const int2*)d_pairs, d_kf_xw,
                        d_assign, d_xw, d_has_point);
     return tracker_end(t, st);
 }

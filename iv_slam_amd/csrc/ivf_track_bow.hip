@@ -17,8 +17,8 @@
 //                  block scan -> the CSR feature vector in the handle's scratch
 //   k_bow_search   one workgroup per pair: node merge (binary search of every keyframe node in the frame's list: only equal ids match,
 //                  the lower_bound walk of :186-270), the common nodes handed to the four waves one at a time, the greedy walk,
-//                  the rotation filter (rot_bin / rot_three_maxima, ivf_device.h), the quality epilogue
-#include "ivf_bow.h"
+//                  the rotation filter (rot_bin / rot_three_maxima, ivf_device.h), the quality epilogue (ivf_tracker.h)
+#include "ivf_tracker.h"
 
 using namespace ivf;
 
@@ -31,11 +31,10 @@ struct BowParams {
     size_t recBytes;
     float nnRatio;
 };
-DEVINL bool rec_ok(const BowParams& P, int r) { return (unsigned)r < (unsigned)P.nRecords; }
 // a pair takes part when the mask selects it and both record indices lie inside the block
 DEVINL bool pair_live(const BowParams& P, const int2 pr, const int* __restrict__ select, int p)
 {
-    return (!select || select[p] != 0) && rec_ok(P, pr.x) && rec_ok(P, pr.y);
+    return (!select || select[p] != 0) && rec_ok(P.nRecords, pr.x) && rec_ok(P.nRecords, pr.y);
 }
 
 __global__ __launch_bounds__(256) void k_bow_nodes(BowParams P, VocabularyView V, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
@@ -244,20 +243,8 @@ __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* 
         __syncthreads();
     }
     for (int i = tid; i < P.nf; i += 256) { const int a = i < nF ? s_assign[i] : -1; out[i] = a < 0 ? -1 : (a & 0xffff); }
-    if (pointQuality && keyQuality) {
-        // UpdateQualityScores(mCurrentFrame) (Tracking.cc:1174-1176; the rule of k_track_greedy's epilogue).  A keyframe point ends on at
-        // most one frame keypoint: the reference's sequential loop has no cross-iteration dependence here.
-        float* pq = pointQuality + (size_t)p * P.nf;
-        float* kq = keyQuality + (size_t)p * P.nf;
-        for (int i = tid; i < nF; i += 256) {
-            const int a = s_assign[i];
-            if (a < 0) continue;
-            const int m = a & 0xffff;
-            const float mq = pq[m], upd = fminf(mq, kq[i]);
-            if (fabsf(upd - mq) > 0.01f) pq[m] = upd;                                             // kDeltaThresh
-            kq[i] = upd;
-        }
-    }
+    // UpdateQualityScores(mCurrentFrame) (Tracking.cc:1174-1176)
+    if (pointQuality && keyQuality) update_quality_scores(s_assign, nF, 0xffff, tid, 256, pointQuality + (size_t)p * P.nf, keyQuality + (size_t)p * P.nf);
     if (tid == 0) nmatchesOut[p] = s_nm;
 }
 
@@ -279,21 +266,22 @@ int ivf_tracker_search_by_bow(ivf_tracker* t, const ivf_vocabulary* voc, int lev
     int rc = vocabulary_view(voc, &V);
     if (rc != IVF_OK) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
-    TrackerView v;
-    rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st, &v);
+    rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st);
     if (rc != IVF_OK) return rc;
-    if (V.device != v.device) return fail(IVF_E_INVALID, "the vocabulary lives on device %d, the tracker on device %d", V.device, v.device);
+    if (V.device != t->cfg.device_id)
+        return fail(IVF_E_INVALID, "the vocabulary lives on device %d, the tracker on device %d", V.device, t->cfg.device_id);
     if (n_pairs == 0) return IVF_OK;
+    const int nf = t->P.nf;
     BowParams P;
-    P.nf = v.nf; P.nRecords = n_records; P.nidLevel = V.depth - levelsup; P.checkOri = check_orientation ? 1 : 0;
-    P.recBytes = v.recBytes; P.nnRatio = nn_ratio;
-    const TrackerBowScratch B = tracker_bow_scratch(t);
+    P.nf = nf; P.nRecords = n_records; P.nidLevel = V.depth - levelsup; P.checkOri = check_orientation ? 1 : 0;
+    P.recBytes = t->P.recBytes; P.nnRatio = nn_ratio;
+    const TrackerBowScratch B = t->bow;
     const int2* pairs = (const int2*)d_pairs;
     size_t npad = 256;
-    while (npad < (size_t)v.nf) npad <<= 1;                   // nfeatures <= 4096: at most 32 KB of keys
-    hipLaunchKernelGGL(k_bow_nodes, dim3((v.nf + 15) / 16, 2 * n_pairs), dim3(256), 0, st, P, V, d_records, pairs, d_select, B.nodeKey);
+    while (npad < (size_t)nf) npad <<= 1;                     // nfeatures <= 4096: at most 32 KB of keys
+    hipLaunchKernelGGL(k_bow_nodes, dim3((nf + 15) / 16, 2 * n_pairs), dim3(256), 0, st, P, V, d_records, pairs, d_select, B.nodeKey);
     hipLaunchKernelGGL(k_bow_featvec, dim3(2 * n_pairs), dim3(256), npad * sizeof(unsigned long long), st, P, d_records, pairs, d_select, B);
-    hipLaunchKernelGGL(k_bow_search, dim3(n_pairs), dim3(256), (size_t)v.nf * 2 * sizeof(int), st, P, d_records, pairs, d_select, d_point_flags, B,
+    hipLaunchKernelGGL(k_bow_search, dim3(n_pairs), dim3(256), (size_t)nf * 2 * sizeof(int), st, P, d_records, pairs, d_select, d_point_flags, B,
                        d_point_quality, d_key_quality, d_assign, d_nmatches);
     return tracker_end(t, st);
 }

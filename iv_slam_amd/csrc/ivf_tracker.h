@@ -1,0 +1,116 @@
+// ivf_tracker.h -- the batched tracker handle and what its four translation units share (not part of the public C-ABI):
+// ivf_track.hip (the handle's life cycle and the TrackWithMotionModel search), ivf_track_local.hip (SearchLocalPoints),
+// ivf_track_bow.hip (TrackReferenceKeyFrame) and ivf_pose.hip (PoseOptimization).  One definition of struct ivf_tracker, one host
+// statement of the camera and record constants (TrackParams), and one device text of every piece the searches repeat.
+#pragma once
+#include "ivf_bow.h"
+#include <vector>
+
+namespace ivf {
+
+constexpr int kListCap = 64;                      // candidates listed per query (one per lane of the greedy wave)
+constexpr int kPrefetch = 16;                     // queries whose lists are in registers ahead of the greedy walk
+constexpr int kMaxTrackFeatures = 4096;           // LDS state of k_track_greedy: 20 B per keypoint
+
+struct TrackParams {                               // uniform kernel arguments
+    int nf, nlevels;
+    float scale[kMaxLevels];
+    float fx, fy, cx, cy, invfx, invfy, bf, b;
+    float minX, minY, maxX, maxY, invW, invH;     // image bounds and mfGridElementWidthInv / HeightInv (Frame.cc:208-209)
+    float thDepth;                                // > 0: UpdateLastFrame's close-point rule
+    float logScale;                               // mfLogScaleFactor = logf(mfScaleFactor) (Frame.cc:106)
+    int checkOri, defaultBlocks;
+    int nRecords;                                 // records in the block of THIS call: every index read from a pair / frame table is checked against it
+    size_t recBytes;
+};
+// a pair / frame table built for another block (a different world size or batch) must not read outside this one: such an entry
+// gets nmatches = -1, assign = -1 and is otherwise skipped
+__device__ __forceinline__ bool rec_ok(int nRecords, int r) { return (unsigned)r < (unsigned)nRecords; }
+// the grid geometry of grid_build / grid_walk (ivf_grid.h), by value: the fields keep their place in the kernel arguments
+__device__ __forceinline__ GridGeom geom_of(const TrackParams& P) { return GridGeom{P.minX, P.minY, P.invW, P.invH}; }
+
+// per-query record written by k_track_prepare / k_local_prepare: projection (u, v), ur = u - bf * invzc, and the packed
+// {octave, minLevel + 1, maxLevel + 1, flags: bit 0 valid, bit 1 blocks}
+struct __attribute__((aligned(16))) Query { float u, v, ur; unsigned bits; };
+__device__ __forceinline__ unsigned pack_bits(int oct, int lo, int hi, int valid, int blocks)
+{ return (unsigned)oct | ((unsigned)(lo + 1) << 8) | ((unsigned)(hi + 1) << 16) | ((unsigned)valid << 24) | ((unsigned)blocks << 25); }
+
+// a row-major 3x4 pose [R | t] (cv::Mat mTcw without its last row)
+__device__ __forceinline__ void load_pose(const float* __restrict__ T, float* R, float* t)
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) R[3 * i + j] = T[4 * i + j];
+        t[i] = T[4 * i + 3];
+    }
+}
+
+// ORBmatcher::UpdateQualityScores (ORBmatcher.cc:1108-1121) at the end of a search, for the keypoints i = tid, tid + stride, ... < n of one
+// frame: assign[i] < 0: no point, else point (assign[i] & idMask).  A point ends on at most one keypoint of the frame, so the
+// reference's sequential loop has no cross-iteration dependence here.
+constexpr float kDeltaThresh = 0.01f;
+__device__ __forceinline__ void update_quality_scores(const int* assign, int n, int idMask, int tid, int stride, float* pq, float* kq)
+{
+    for (int i = tid; i < n; i += stride) {
+        const int a = assign[i];
+        if (a < 0) continue;
+        const int m = a & idMask;
+        const float mq = pq[m], upd = fminf(mq, kq[i]);
+        if (fabsf(upd - mq) > kDeltaThresh) pq[m] = upd;
+        kq[i] = upd;
+    }
+}
+
+// k_track_greedy's candidate admission against the live state in LDS (ORBmatcher.cc:1447-1457): current keypoint i2 is out when a point
+// with observations holds it, or when it has a right coordinate further than the window radius from the projected one
+constexpr int kNoBlock = 0x10000;                 // flag on an assignment made by a point without observations: it does not block (:1447-1449)
+__device__ __forceinline__ bool track_admits(const int* s_assign, const float* s_ur, int i2, float qur, float radius)
+{
+    bool ok = true;
+    const int a = s_assign[i2];
+    if (a >= 0 && !(a & kNoBlock)) ok = false;
+    const float u2 = s_ur[i2];
+    if (u2 > 0) { const float er = fabsf(qur - u2); if (er > radius) ok = false; }
+    return ok;
+}
+
+}  // namespace ivf
+
+struct ivf_tracker {
+    ivf_track_config cfg;
+    ivf::TrackParams P;                   // nRecords is the one per-call field: every entry point sets it in its own copy
+    int *dStart = nullptr, *dCount = nullptr, *dRetry = nullptr;
+    unsigned short* dIdx = nullptr;
+    ivf::Query* dQ = nullptr;
+    unsigned* dLists = nullptr;
+    // scratch of ivf_tracker_search_local, sized at its first call / grown on demand: [max_pairs][localCap] queries, radii, counts, lists
+    ivf::Query* dLQ = nullptr; float* dLRad = nullptr; int* dLCount = nullptr; unsigned* dLLists = nullptr; int localCap = 0;
+    ivf::TrackerBowScratch bow{nullptr, nullptr, nullptr, nullptr, nullptr};   // ivf_tracker_search_by_bow: [2 * max_pairs] slots
+    size_t ldsBytes = 0;
+    hipEvent_t evDone = nullptr;          // end of the previous call: the scratch above belongs to ONE call at a time
+    bool ran = false;
+    std::vector<void*> owned;             // every device allocation of the handle (alloc): ivf_tracker_destroy frees these
+
+    // one hipMalloc the handle owns from here on
+    template <class T> bool alloc(T*& p, size_t bytes)
+    {
+        if (hipMalloc(&p, bytes) != hipSuccess) { p = nullptr; return false; }
+        owned.push_back(p);
+        return true;
+    }
+    // gives one of them back early (null: nothing to do)
+    template <class T> void release(T*& p)
+    {
+        for (size_t i = 0; i < owned.size(); i++)
+            if (p && owned[i] == p) { (void)hipFree(p); owned.erase(owned.begin() + i); break; }
+        p = nullptr;
+    }
+};
+
+namespace ivf {
+// tracker_begin: the argument checks every tracker entry point shares, hipSetDevice and the wait for the handle's previous call;
+// tracker_end: the event the next call waits for
+int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n_records, int n_items, hipStream_t st);
+int tracker_end(ivf_tracker* t, hipStream_t st);
+}  // namespace ivf

@@ -309,3 +309,94 @@ def test_local_points_random_synthetic(iv, seed):
         a, nm = run_local(iv, cam, recs, frames, per_frame, poses, occ, th, 0.8, tracker=tr)
         check_local(cam, recs, frames, per_frame, poses, occ, th, 0.8, a, nm, what="synthetic th %g" % th)
         assert nm[2] == 0 and nm[3] == 0
+
+
+def test_one_handle_through_every_search_equals_fresh_handles(iv):
+    """The handle's owned device buffers: ONE handle (nfeatures 64, max_pairs 2) goes through run, search_local with 8 points per frame,
+    search_local with 40 (its scratch is released and allocated again after use), search_by_bow, optimize_pose and search_local with 8
+    again (no regrowth).  Every output is byte for byte what a fresh handle returns for that call alone; then the handle is destroyed."""
+    import torch
+    from iv_slam_amd import dist as ivd
+    import track_bow_scenes as S
+    from test_gpu_track import _random_records, scale_table
+    nf = 64
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(64)
+    cam = dict(nf=nf, scale=scale_table(), fx=S.CAM["fx"], fy=S.CAM["fy"], cx=S.CAM["cx"], cy=S.CAM["cy"], bf=S.CAM["bf"],
+               b=F(S.CAM["bf"] / S.CAM["fx"]), bounds=S.BOUNDS)
+    recs = _random_records(rng, nf, 3, int(S.W), int(S.H), 1.0)
+    I = np.eye(4, dtype=F)
+    per_frame = [map_points_from(cam, recs[0], I, rng, jitter=0.0), map_points_from(cam, recs[1], I, rng, jitter=0.0)]
+    assert min(len(p) for p in per_frame) > 8
+    block = torch.from_numpy(ivd.pack_records(recs, nf).reshape(-1)).to(dev)
+    pairs = torch.tensor([(0, 1), (1, 2)], dtype=torch.int32, device=dev)
+    frames = [1, 2]
+    # search_by_bow: two scenes of the depth-3 tree that fit 64 features a side
+    tree = S.TREES[3]
+    scs = [S.swapped_ends_scene(tree, 1), S.rotation_scene(tree, 1, [(10.0, 12), (120.0, 8), (250.0, 5), (330.0, 3), (60.0, 1)], "rotation_three_bins")]
+    bow_recs = [r for sc in scs for r in S.records_of(sc)]
+    bow_block = torch.from_numpy(ivd.pack_records(bow_recs, nf).reshape(-1)).to(dev)
+    bow_pairs = torch.tensor([(0, 1), (2, 3)], dtype=torch.int32, device=dev)
+    V = iv.ORBVocabulary(tree["child_start"], tree["child"], tree["desc"], tree["word"], tree["weight"], tree["depth"])
+    # optimize_pose: every stereo keypoint of frames 1 and 2 observes its own un-projection (identity pose) moved by a few centimetres
+    xw = np.zeros((2, nf, 3), F); has = np.zeros((2, nf), np.uint8)
+    for k, ri in enumerate(frames):
+        r = recs[ri]; n = len(r["kps"]); z = r["depth"]
+        xw[k, :n, 0] = (r["kps"]["x"] - cam["cx"]) * z / cam["fx"]; xw[k, :n, 1] = (r["kps"]["y"] - cam["cy"]) * z / cam["fy"]; xw[k, :n, 2] = z
+        xw[k, :n] += rng.normal(0, 0.03, (n, 3)).astype(F)
+        has[k, :n] = z > 0
+    pose_in = np.stack([pose(0.5, [0.02, -0.01, 0.05])[:3, :4].reshape(12), pose(-0.3, [-0.03, 0.0, 0.02])[:3, :4].reshape(12)]).astype(F)
+    pq = rng.uniform(0, 1, (2, nf)).astype(F); kq = rng.uniform(0, 1, (2, nf)).astype(F)
+
+    def out(*tensors):
+        torch.cuda.synchronize()
+        return tuple(t.cpu().numpy() for t in tensors)
+
+    def results():
+        return torch.full((2, nf), -7, dtype=torch.int32, device=dev), torch.full((2,), -7, dtype=torch.int32, device=dev)
+
+    def quality():
+        return torch.from_numpy(pq).to(dev), torch.from_numpy(kq).to(dev)
+
+    def call_run(tr):
+        (a, nm), (dpq, dkq) = results(), quality()
+        tr.run(block, pairs, a, nm, point_quality=dpq, key_quality=dkq)
+        return out(a, nm, dpq, dkq)
+
+    def call_local(cap):
+        return lambda tr: run_local(iv, cam, recs, frames, per_frame, None, None, 3.0, 0.8, max_points=cap, tracker=tr)
+
+    def call_bow(tr):
+        (a, nm), (dpq, dkq) = results(), quality()
+        tr.search_by_bow(V, bow_block, bow_pairs, a, nm, levelsup=1, point_quality=dpq, key_quality=dkq)
+        return out(a, nm, dpq, dkq)
+
+    def call_pose(tr):
+        poses = torch.from_numpy(pose_in).to(dev)
+        outl = torch.full((2, nf), 9, dtype=torch.uint8, device=dev); ninl = torch.full((2,), -7, dtype=torch.int32, device=dev)
+        tr.optimize_pose(block, torch.tensor(frames, dtype=torch.int32, device=dev), torch.from_numpy(xw).to(dev), torch.from_numpy(has).to(dev), poses, outl, ninl)
+        return out(poses, outl, ninl)
+
+    def fresh():
+        return iv.BatchTracker(nf, cam["scale"], float(cam["fx"]), float(cam["fy"]), float(cam["cx"]), float(cam["cy"]), float(cam["bf"]),
+                               cam["bounds"], max_pairs=2, b=float(cam["b"]))
+
+    tr = fresh()
+    steps = [("run", call_run), ("search_local 8", call_local(8)), ("search_local 40", call_local(40)), ("search_by_bow", call_bow),
+             ("optimize_pose", call_pose), ("search_local 8 again", call_local(8))]
+    got = {}
+    for name, call in steps:
+        got[name] = call(tr)
+        alone = call(fresh())
+        assert len(got[name]) == len(alone)
+        for g, e in zip(got[name], alone):
+            assert g.dtype == e.dtype and g.tobytes() == e.tobytes(), name
+    del tr
+    torch.cuda.synchronize()
+    print("matches: run %r, local 8 %r, local 40 %r, bow %r; inliers %r" % tuple(got[k][i].tolist() for k, i in (
+        ("run", 1), ("search_local 8", 1), ("search_local 40", 1), ("search_by_bow", 1), ("optimize_pose", 2))))
+    # the calls did real work: matches in every search, inliers in the optimisation, and the first and last call are the same call
+    assert got["run"][1].min() > 5 and got["search_local 8"][1].sum() > 0 and got["search_local 40"][1].sum() > got["search_local 8"][1].sum()
+    assert got["search_by_bow"][1].tolist() == [S.oracle(O, sc, 1)[1] for sc in scs] and got["search_by_bow"][1].min() > 5
+    assert got["optimize_pose"][2].min() >= 3
+    assert all(g.tobytes() == e.tobytes() for g, e in zip(got["search_local 8 again"], got["search_local 8"]))
