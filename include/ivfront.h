@@ -631,6 +631,38 @@ int  ivf_tracker_search_by_bow(ivf_tracker* t, const ivf_vocabulary* voc, int le
  * point each keypoint of each record holds.  The frames to optimise are the pairs' current records.  Asynchronous on hip_stream. */
 int  ivf_tracker_points_from_keyframe(ivf_tracker* t, const int32_t* d_pairs, int n_pairs, int n_records, const float* d_kf_xw,
                                       const int32_t* d_assign, float* d_xw, uint8_t* d_has_point, void* hip_stream);
+/* Batched PnPsolver (ORB/src/PnPsolver.cc), the step of Tracking::Relocalization (ORB/src/Tracking.cc:2272-2421) between
+ * SearchByBoW(pKF, mCurrentFrame, ...) and PoseOptimization: EPnP inside a RANSAC loop, in double as the reference runs it, for frame
+ * slot f = record d_frames[f].  The correspondences are those the constructor collects (PnPsolver.cc:71-114): mvKeysUn[i] and
+ * mvLevelSigma2[octave] (scale factor squared, in float) of every keypoint i below the record's count with d_has_point[f][i] != 0, and
+ * d_xw[f][i] (both arrays as ivf_tracker_points_from_keyframe writes and ivf_tracker_optimize_pose takes them), in keypoint order.
+ * probability, min_inliers, epsilon, th2 are SetRansacParameters' (Tracking.cc:2317: 0.99, 10, 0.5, 5.991; minSet is 4): :137-156
+ * give mRansacMinInliers and mRansacMaxIts = clamp(ceil(log(1 - p) / log(1 - eps^3)), 1, max_iterations), 1 when mRansacMinInliers == N.
+ * A call runs iterate() to completion: because the loop condition of :186 is an OR, the iterate(5, ...) of Tracking.cc:2339 runs until
+ * mnIterations reaches mRansacMaxIts unless Refine succeeds earlier, and so does this call (where mRansacMaxIts < 5 the reference's
+ * first call goes on to 5 iterations; this one stops at mRansacMaxIts).  The hypotheses are independent, so all of them are computed at
+ * once (one wave each) and the bookkeeping of :213-259 is replayed in iteration order: the first iteration whose Refine (:264-309, on
+ * mvbBestInliers, accepted with MORE than mRansacMinInliers inliers) succeeds returns mRefinedTcw and mvbRefinedInliers; with none, the
+ * best hypothesis and its inliers when it has at least mRansacMinInliers; else no pose.  CheckInliers (:312-343) keeps the reference's
+ * float / double mix.  cvSVD, cvInvert and cvSolve(CV_SVD) are a cyclic Jacobi SVD with a fixed pair order and sweep cap: a 4-point
+ * hypothesis leaves a four-dimensional null space whose basis rounding chooses, so single hypotheses are not comparable between
+ * implementations; Refine's pose is.
+ * d_draws [n_frames][max_iterations][4]: the values rand() returned for the four samples of every iteration (bit 31 is ignored); the
+ * call applies DUtils::Random::RandomInt (Thirdparty/DBoW2/DUtils/Random.cpp:47-50) and the swap-with-back removal of :192-205.  The
+ * sampling is therefore the caller's: reproducible, or glibc's stream to follow the reference exactly.  max_iterations in [1, 300].
+ * Outputs: d_poses [n_frames][12] (row-major 3x4, the f64 mRi / mti narrowed to float, :221-227 / :298-304) is written only where a
+ * pose is returned; d_inlier [n_frames][nfeatures] = vbInliers by keypoint; d_ninliers [n_frames] = nInliers, 0 = cv::Mat() (also for
+ * N < mRansacMinInliers, :177-181), -1 = record index outside [0, n_records): nothing else of that frame is written;
+ * d_iterations [n_frames] (nullable) = mnIterations on return; d_hyp_poses [n_frames][max_iterations][12] and d_hyp_ninliers
+ * [n_frames][max_iterations] (nullable) = pose (narrowed to float) and mnInliersi of every iteration below mRansacMaxIts, the others
+ * untouched.  IVF_E_INVALID: a null required pointer, max_iterations outside [1, 300], probability outside (0, 1), epsilon outside
+ * [0, 1], n_frames > max_pairs.  Every loop has a compile-time bound: NaN input cannot hang the call.  Two runs are bit-identical.
+ * Asynchronous on hip_stream, no host synchronisation; the scratch is allocated at the first call for max_pairs frames and obeys the
+ * handle's one-call-at-a-time rule. */
+int  ivf_tracker_solve_pnp(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_frames, int n_frames,
+                           const float* d_xw, const uint8_t* d_has_point, const uint32_t* d_draws, int max_iterations, double probability,
+                           int min_inliers, float epsilon, float th2, float* d_poses, uint8_t* d_inlier, int32_t* d_ninliers,
+                           int32_t* d_iterations, float* d_hyp_poses, int32_t* d_hyp_ninliers, void* hip_stream);
 /* MapPoint::ComputeDistinctiveDescriptors (ORB/src/MapPoint.cc:247-312): desc = the n observed descriptors (rows of
  * vDescriptors, in mObservations order); *best_index = the row to copy into mDescriptor, *best_median (nullable) its median. */
 int  ivf_distinctive_descriptor(const uint8_t* desc, int n, int* best_index, int* best_median, int device_id);

@@ -1,6 +1,6 @@
-// ivf_tracker.h -- the batched tracker handle and what its four translation units share (not part of the public C-ABI):
+// ivf_tracker.h -- the batched tracker handle and what its five translation units share (not part of the public C-ABI):
 // ivf_track.hip (the handle's life cycle and the TrackWithMotionModel search), ivf_track_local.hip (SearchLocalPoints),
-// ivf_track_bow.hip (TrackReferenceKeyFrame) and ivf_pose.hip (PoseOptimization).  One definition of struct ivf_tracker, one host
+// ivf_track_bow.hip (TrackReferenceKeyFrame), ivf_pose.hip (PoseOptimization) and ivf_pnp.hip (Relocalization's PnPsolver).  One definition of struct ivf_tracker, one host
 // statement of the camera and record constants (TrackParams), and one device text of every piece the searches repeat.
 #pragma once
 #include "ivf_bow.h"
@@ -11,6 +11,12 @@ namespace ivf {
 constexpr int kListCap = 64;                      // candidates listed per query (one per lane of the greedy wave)
 constexpr int kPrefetch = 16;                     // queries whose lists are in registers ahead of the greedy walk
 constexpr int kMaxTrackFeatures = 4096;           // LDS state of k_track_greedy: 20 B per keypoint
+constexpr int kPnpMaxIterations = 300;            // ivf_tracker_solve_pnp: the cap of max_iterations (Tracking.cc:2317 passes 300)
+
+// The handle's scratch of ivf_tracker_solve_pnp (ivf_pnp.hip), allocated at its first call for max_pairs frames: the compacted
+// correspondences [max_pairs][nfeatures] (32 B each), per frame {N, mRansacMinInliers, mRansacMaxIts}, and the f64 pose and inlier count
+// of every hypothesis [max_pairs][kPnpMaxIterations]
+struct PnpScratch { void* corr; void* head; double* hypPose; int* hypN; };
 
 struct TrackParams {                               // uniform kernel arguments
     int nf, nlevels;
@@ -87,6 +93,7 @@ struct ivf_tracker {
     // scratch of ivf_tracker_search_local, sized at its first call / grown on demand: [max_pairs][localCap] queries, radii, counts, lists
     ivf::Query* dLQ = nullptr; float* dLRad = nullptr; int* dLCount = nullptr; unsigned* dLLists = nullptr; int localCap = 0;
     ivf::TrackerBowScratch bow{nullptr, nullptr, nullptr, nullptr, nullptr};   // ivf_tracker_search_by_bow: [2 * max_pairs] slots
+    ivf::PnpScratch pnp{nullptr, nullptr, nullptr, nullptr};
     size_t ldsBytes = 0;
     hipEvent_t evDone = nullptr;          // end of the previous call: the scratch above belongs to ONE call at a time
     bool ran = false;

@@ -166,3 +166,39 @@ class BatchTracker:
                                                   xw.data_ptr(), has_point.data_ptr(), None if quality is None else quality.data_ptr(),
                                                   int(n_rounds), poses.data_ptr(), outlier.data_ptr(), ninliers.data_ptr(),
                                                   None if chi2 is None else chi2.data_ptr(), stream_ptr))
+
+    def solve_pnp(self, records, frames, xw, has_point, draws, poses, inlier, ninliers, max_iterations=300, probability=0.99, min_inliers=10,
+                  epsilon=0.5, th2=5.991, iterations=None, hyp_poses=None, hyp_ninliers=None, stream_ptr=None):
+        """PnPsolver (ORB/src/PnPsolver.cc) as Tracking::Relocalization runs it (ORB/src/Tracking.cc:2315-2339) for n_frames frames at once:
+        EPnP inside RANSAC, iterate() run to completion, Refine on the best inlier set.  frames: torch.int32 [n_frames] record indices;
+        xw: torch.float32 [n_frames, nfeatures, 3] and has_point: torch.uint8 [n_frames, nfeatures] as points_from_keyframe() writes them;
+        draws: torch.uint32-sized [n_frames, max_iterations, 4], the rand() values of the four samples of every iteration (pnp_draws());
+        probability, min_inliers, epsilon, th2: SetRansacParameters' (0.99, 10, 0.5, 5.991 at Tracking.cc:2317), max_iterations 1..300;
+        poses: torch.float32 [n_frames, 12], written only where a pose is returned; inlier: torch.uint8 [n_frames, nfeatures] (vbInliers);
+        ninliers: torch.int32 [n_frames] (0: no pose, -1: bad record index); iterations: torch.int32 [n_frames] or None (mnIterations);
+        hyp_poses: torch.float32 [n_frames, max_iterations, 12] and hyp_ninliers: torch.int32 [n_frames, max_iterations] or None: every
+        hypothesis.  has_point & inlier is the has_point of the optimize_pose() that follows.  Asynchronous on the given stream."""
+        n_rec = records.numel() // self.record_bytes
+        n_frames = frames.numel()
+        nf = self.nfeatures
+        mi = int(max_iterations)
+        assert frames.element_size() == 4 and frames.is_contiguous() and poses.is_contiguous() and poses.element_size() == 4 and poses.numel() == n_frames * 12
+        assert xw.is_contiguous() and xw.element_size() == 4 and xw.numel() >= n_frames * nf * 3
+        assert has_point.element_size() == 1 and has_point.numel() >= n_frames * nf and inlier.element_size() == 1 and inlier.numel() >= n_frames * nf
+        assert draws.is_contiguous() and draws.element_size() == 4 and draws.numel() >= n_frames * mi * 4, "draws are [n_frames, max_iterations, 4]"
+        assert ninliers.element_size() == 4 and ninliers.numel() >= n_frames
+        assert iterations is None or (iterations.element_size() == 4 and iterations.numel() >= n_frames)
+        assert hyp_poses is None or (hyp_poses.is_contiguous() and hyp_poses.element_size() == 4 and hyp_poses.numel() >= n_frames * mi * 12)
+        assert hyp_ninliers is None or (hyp_ninliers.is_contiguous() and hyp_ninliers.element_size() == 4 and hyp_ninliers.numel() >= n_frames * mi)
+        check(self._lib.ivf_tracker_solve_pnp(self._h, records.data_ptr(), self.record_bytes, n_rec, frames.data_ptr(), n_frames,
+                                              xw.data_ptr(), has_point.data_ptr(), draws.data_ptr(), mi, float(probability), int(min_inliers),
+                                              float(epsilon), float(th2), poses.data_ptr(), inlier.data_ptr(), ninliers.data_ptr(),
+                                              None if iterations is None else iterations.data_ptr(),
+                                              None if hyp_poses is None else hyp_poses.data_ptr(),
+                                              None if hyp_ninliers is None else hyp_ninliers.data_ptr(), stream_ptr))
+
+
+def pnp_draws(n_frames, max_iterations, seed):
+    """The sampling input of BatchTracker.solve_pnp: uint32 [n_frames, max_iterations, 4] values in [0, RAND_MAX] from numpy's generator
+    (a host that wants the reference's own stream passes glibc rand() values instead)."""
+    return np.random.default_rng(seed).integers(0, 2 ** 31, size=(int(n_frames), int(max_iterations), 4), dtype=np.uint32)
