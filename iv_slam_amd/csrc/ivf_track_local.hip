@@ -264,7 +264,9 @@ __global__ __launch_bounds__(64) void k_local_greedy(TrackParams P, const uint8_
             if (bestDist > 100) continue;                                               // TH_HIGH (:118)
             if (ks != 0xffffffffu) {
                 const int bestDist2 = (int)(ks >> 12), bestLevel2 = (int)((es >> 12) & 15);
-                if (bestLevel == bestLevel2 && (float)bestDist > nnRatio * (float)bestDist2) continue;   // :120-121
+                // a candidate AT 256 never becomes second best: bestDist2 starts at 256 and `dist < bestDist2` is strict (:78, :110), so
+                // bestLevel2 stays -1 and no ratio test is made
+                if (bestDist2 < 256 && bestLevel == bestLevel2 && (float)bestDist > nnRatio * (float)bestDist2) continue;   // :120-121
             }
             if (lane == 0) s_assign[bestIdx] = ((bits >> 25) & 1) ? m : (m | kLocalNoBlock);          // :123
             nm++;
