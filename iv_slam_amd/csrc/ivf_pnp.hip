@@ -17,13 +17,12 @@
 // compute_pose is one text for both sizes (template on the thread count).  The sums over points go through xor-butterflies in the wave and
 // through LDS in wave order: the tree is fixed, two runs are bit-identical.  The 12x12 MtM, its vectors and every small matrix live in
 // LDS; a Jacobi rotation is spread over lanes (one matrix row each).  Every loop has a compile-time bound: NaN cannot spin a kernel.
-#include "ivf_tracker.h"
+// The sums, the ordered compaction, the frame's pointer set and the pose I/O are ivf_solve.h's, shared with ivf_pose.hip.
+#include "ivf_solve.h"
 
 using namespace ivf;
 
 namespace {
-
-#define DEVINL __device__ __forceinline__
 
 constexpr int kSweeps = 30;                                           // cap of the Jacobi sweeps (convergence takes 6..10)
 constexpr int kRefThreads = 256;
@@ -53,13 +52,6 @@ struct Ws {                                                           // LDS of 
     int ord[12], sord[5];
 };
 
-DEVINL double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);        // a + b == b + a: every lane ends with the same bits
-    return v;
-}
-
 // the K sums of acc[] over the workgroup -> S.sum[0..K)
 template <int NT, int K>
 DEVINL void block_sum(Ws& S, const double* acc, int tid)
@@ -72,12 +64,7 @@ DEVINL void block_sum(Ws& S, const double* acc, int tid)
         if (lane == 0) S.part[wave][k] = v;
     }
     __syncthreads();
-    for (int k = tid; k < K; k += NT) {
-        double v = S.part[0][k];
-#pragma unroll
-        for (int w = 1; w < NT / 64; w++) v = v + S.part[w][k];
-        S.sum[k] = v;
-    }
+    for (int k = tid; k < K; k += NT) S.sum[k] = wave_order_sum<NT / 64>(&S.part[0][k], kSumCap);
     __syncthreads();
 }
 
@@ -477,27 +464,22 @@ DEVINL void compute_pose(Ws& S, const PnpParams& P, const Corr* __restrict__ cor
     }
     __syncthreads();
 }
+// its result, in registers
+DEVINL void load_solution(const Ws& S, double* R, double* t)
+{
+#pragma unroll
+    for (int k = 0; k < 9; k++) R[k] = S.R[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) t[k] = S.t[k];
+}
 
 // mnInliersi of the pose (R, t) in registers over corr[0 .. N); with `list`, also the indices of the inliers in order (NT == kRefThreads)
 template <int NT>
 DEVINL int count_inliers(const PnpParams& P, const double* R, const double* t, const Corr* __restrict__ corr, int N, int tid, int* s_wcnt,
                          unsigned short* list)
 {
-    const int wave = tid >> 6, lane = tid & 63;
-    int total = 0;
-    for (int i0 = 0; i0 < N; i0 += NT) {
-        const int i = i0 + tid;
-        const bool in = i < N && is_inlier(R, t, P.fu, P.fv, P.uc, P.vc, corr[i]);
-        const unsigned long long m = __ballot(in);
-        if (lane == 0) s_wcnt[wave] = __popcll(m);
-        __syncthreads();
-        int base = total;
-#pragma unroll
-        for (int w = 0; w < NT / 64; w++) { const int c = s_wcnt[w]; if (w < wave) base += c; total += c; }
-        if (in && list) list[base + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)i;
-        __syncthreads();
-    }
-    return total;
+    return compact_ordered<NT>(N, s_wcnt, tid, [&](int i) { return is_inlier(R, t, P.fu, P.fv, P.uc, P.vc, corr[i]); },
+                               [&](int i, int slot) { if (list) list[slot] = (unsigned short)i; });
 }
 
 // ---- the correspondences and the RANSAC parameters of every frame --------------------------------------------------------------------
@@ -507,43 +489,24 @@ __global__ __launch_bounds__(256) void k_pnp_prepare(PnpParams P, const uint8_t*
                                                      int* __restrict__ iterations)
 {
     __shared__ int s_wcnt[4];
-    const int f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nf = P.nf;
-    const int ri = frames[f];
-    if (!rec_ok(P.nRecords, ri)) {                                     // nothing of this frame is touched
+    const int f = blockIdx.x, tid = threadIdx.x, nf = P.nf;
+    const FrameObs O = frame_obs(records, P.recBytes, nf, P.nRecords, frames[f], xw, hasPoint, f);
+    if (O.nC < 0) {                                                    // nothing of this frame is touched
         if (tid == 0) { nInliers[f] = -1; head[f] = make_int4(0, 0, 0, 0); }
         return;
     }
     uint8_t* inl = inlierOut + (size_t)f * nf;
     for (int i = tid; i < nf; i += 256) inl[i] = 0;
-    const uint8_t* rec = records + (size_t)ri * P.recBytes;
-    const int nC = rec_count(rec, nf);
-    const ivf_keypoint* kps = rec_kps(rec);
-    const float* X = xw + (size_t)f * nf * 3;
-    const uint8_t* has = hasPoint + (size_t)f * nf;
     Corr* corr = corrAll + (size_t)f * nf;
-    int N = 0;
-    for (int i0 = 0; i0 < nC; i0 += 256) {
-        const int i = i0 + tid;
-        const bool on = i < nC && has[i] != 0;
-        const unsigned long long m = __ballot(on);
-        if (lane == 0) s_wcnt[wave] = __popcll(m);
-        __syncthreads();
-        int base = N, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) { const int c = s_wcnt[w]; if (w < wave) base += c; total += c; }
-        if (on) {
-            const ivf_keypoint kp = kps[i];
-            const int oct = kp.octave < 0 ? 0 : (kp.octave > kMaxLevels - 1 ? kMaxLevels - 1 : kp.octave);
-            Corr c;
-            c.X[0] = X[3 * i]; c.X[1] = X[3 * i + 1]; c.X[2] = X[3 * i + 2];
-            c.u = kp.x; c.v = kp.y;
-            c.maxErr = P.sigma2[oct] * P.th2;                          // mvMaxError[i] = mvSigma2[i] * th2, in float (:160)
-            c.kp = i; c.pad = 0;
-            corr[base + __popcll(m & ((1ull << lane) - 1ull))] = c;
-        }
-        N += total;
-        __syncthreads();
-    }
+    const int N = compact_ordered<256>(O.nC, s_wcnt, tid, [&](int i) { return O.has[i] != 0; }, [&](int i, int slot) {
+        const ivf_keypoint kp = O.kps[i];
+        Corr c;
+        c.X[0] = O.X[3 * i]; c.X[1] = O.X[3 * i + 1]; c.X[2] = O.X[3 * i + 2];
+        c.u = kp.x; c.v = kp.y;
+        c.maxErr = P.sigma2[clamp_octave(kp.octave)] * P.th2;          // mvMaxError[i] = mvSigma2[i] * th2, in float (:160)
+        c.kp = i; c.pad = 0;
+        corr[slot] = c;
+    });
     if (tid == 0) {
         // SetRansacParameters (:137-156)
         float eps = P.epsilon;
@@ -599,29 +562,13 @@ __global__ __launch_bounds__(64) void k_pnp_hyp(PnpParams P, const Corr* __restr
     __syncthreads();
     compute_pose<64>(S, P, corr, s_list, 4, tid);
     double R[9], t[3];
-#pragma unroll
-    for (int k = 0; k < 9; k++) R[k] = S.R[k];
-#pragma unroll
-    for (int k = 0; k < 3; k++) t[k] = S.t[k];
+    load_solution(S, R, t);
     const int ni = count_inliers<64>(P, R, t, corr, N, tid, s_wcnt, nullptr);
     if (tid == 0) {
-        double* hp = hypPose + slot * 12;
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-#pragma unroll
-            for (int j = 0; j < 3; j++) hp[4 * i + j] = R[3 * i + j];
-            hp[4 * i + 3] = t[i];
-        }
+        store_pose(hypPose + slot * 12, R, t);
         hypN[slot] = ni;
         if (outN) outN[slot] = ni;
-        if (outPoses) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-#pragma unroll
-                for (int j = 0; j < 3; j++) outPoses[slot * 12 + 4 * i + j] = (float)R[3 * i + j];
-                outPoses[slot * 12 + 4 * i + 3] = (float)t[i];
-            }
-        }
+        if (outPoses) store_pose(outPoses + slot * 12, R, t);
     }
 }
 
@@ -643,6 +590,11 @@ __global__ __launch_bounds__(kRefThreads) void k_pnp_replay(PnpParams P, const C
     float* T = poses + (size_t)f * 12;
     int best = 0, bestIt = -1;
     double R[9], t[3];
+    // the answer: the pose (R, t) with its n inliers s_list[0 .. n)
+    auto publish = [&](int n) {
+        for (int j = tid; j < n; j += kRefThreads) inl[corr[s_list[j]].kp] = 1;
+        if (tid == 0) { store_pose(T, R, t); nInliers[f] = n; }
+    };
 #pragma unroll 1
     for (int it = 0; it < kPnpMaxIterations; it++) {
         if (it >= maxIts) break;
@@ -650,55 +602,21 @@ __global__ __launch_bounds__(kRefThreads) void k_pnp_replay(PnpParams P, const C
         const int ni = hypN[slot];
         if (!(ni >= minInl && ni > best)) continue;                    // Refine on an unchanged mvbBestInliers fails as it did before
         best = ni; bestIt = it;
-        const double* hp = hypPose + slot * 12;
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-#pragma unroll
-            for (int j = 0; j < 3; j++) R[3 * i + j] = hp[4 * i + j];
-            t[i] = hp[4 * i + 3];
-        }
+        load_hyp(hypPose + slot * 12, R, t);
         const int nb = count_inliers<kRefThreads>(P, R, t, corr, N, tid, s_wcnt, s_list);   // mvbBestInliers (nb == ni)
         compute_pose<kRefThreads>(S, P, corr, s_list, nb, tid);        // Refine (:264-309)
-#pragma unroll
-        for (int k = 0; k < 9; k++) R[k] = S.R[k];
-#pragma unroll
-        for (int k = 0; k < 3; k++) t[k] = S.t[k];
+        load_solution(S, R, t);
         const int nr = count_inliers<kRefThreads>(P, R, t, corr, N, tid, s_wcnt, s_list);   // mvbRefinedInliers
         if (nr > minInl) {                                             // strict (:296)
-            for (int j = tid; j < nr; j += kRefThreads) inl[corr[s_list[j]].kp] = 1;
-            if (tid == 0) {
-#pragma unroll
-                for (int i = 0; i < 3; i++) {
-#pragma unroll
-                    for (int j = 0; j < 3; j++) T[4 * i + j] = (float)R[3 * i + j];
-                    T[4 * i + 3] = (float)t[i];
-                }
-                nInliers[f] = nr;
-                if (iterations) iterations[f] = it + 1;
-            }
+            publish(nr);
+            if (tid == 0 && iterations) iterations[f] = it + 1;
             return;
         }
     }
     if (tid == 0 && iterations) iterations[f] = maxIts;
     if (bestIt < 0) { if (tid == 0) nInliers[f] = 0; return; }         // mnBestInliers < mRansacMinInliers: cv::Mat()
-    const double* hp = hypPose + ((size_t)f * P.maxIterations + bestIt) * 12;
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) R[3 * i + j] = hp[4 * i + j];
-        t[i] = hp[4 * i + 3];
-    }
-    const int nb = count_inliers<kRefThreads>(P, R, t, corr, N, tid, s_wcnt, s_list);
-    for (int j = tid; j < nb; j += kRefThreads) inl[corr[s_list[j]].kp] = 1;
-    if (tid == 0) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-#pragma unroll
-            for (int j = 0; j < 3; j++) T[4 * i + j] = (float)R[3 * i + j];
-            T[4 * i + 3] = (float)t[i];
-        }
-        nInliers[f] = nb;
-    }
+    load_hyp(hypPose + ((size_t)f * P.maxIterations + bestIt) * 12, R, t);
+    publish(count_inliers<kRefThreads>(P, R, t, corr, N, tid, s_wcnt, s_list));
 }
 
 }  // namespace
@@ -731,7 +649,7 @@ int ivf_tracker_solve_pnp(ivf_tracker* t, const uint8_t* d_records, size_t recor
     PnpParams P;
     P.nf = t->P.nf; P.nRecords = n_records; P.recBytes = t->P.recBytes;
     P.fu = (double)t->P.fx; P.fv = (double)t->P.fy; P.uc = (double)t->P.cx; P.vc = (double)t->P.cy;
-    for (int l = 0; l < kMaxLevels; l++) P.sigma2[l] = t->P.scale[l] * t->P.scale[l];   // mvLevelSigma2 (ORBextractor.cc:419-431), as ivf_pose.hip
+    level_sigma2(t->P, P.sigma2);
     P.maxIterations = max_iterations; P.minInliers = min_inliers; P.probability = probability; P.epsilon = epsilon; P.th2 = th2;
     Corr* corr = (Corr*)t->pnp.corr;
     int4* head = (int4*)t->pnp.head;

@@ -1,5 +1,5 @@
 // ivf_pose.hip -- batched, device-resident Optimizer::PoseOptimization (ORB/src/Optimizer.cc:251-503): the consumer of the two batched
-// searches of ivf_track.hip and ivf_track_local.hip, on the same handle (ivf_tracker.h).  g2o's machinery for this call is one 6-dof vertex (VertexSE3Expmap), unary edges
+// searches of ivf_track.hip and ivf_track_local.hip, on the same handle (ivf_tracker.h; the points they hand over: ivf_track_points.hip).  g2o's machinery for this call is one 6-dof vertex (VertexSE3Expmap), unary edges
 // (EdgeSE3ProjectXYZOnlyPose / EdgeStereoSE3ProjectXYZOnlyPose, Thirdparty/g2o/g2o/types/types_six_dof_expmap.{h,cpp}), a dense 6x6
 // system (solvers/linear_solver_dense.h: Eigen::LDLT) and OptimizationAlgorithmLevenberg (core/optimization_algorithm_levenberg.cpp);
 // all of it is restated here in double, the arithmetic the reference runs it in.
@@ -13,15 +13,12 @@
 //                       does the LDLT solve, exp(dx) * estimate, the rho / lambda / nu bookkeeping and the stop tests and publishes
 //                       the next pose and the decision through LDS; every branch around a barrier reads that decision.
 //                       Loop bounds are compile-time (4 rounds x 10 iterations x 10 trials): NaN input cannot spin the kernel.
-//   k_points_from_pairs Frame::UnprojectStereo (ORB/src/Frame.cc:958-972) of the last-frame keypoint every current keypoint was assigned
-//   k_points_from_local GetWorldPos() of the local map point every keypoint was assigned
-#include "ivf_tracker.h"
+// The sums, the ordered compaction, the frame's pointer set and the pose store are ivf_solve.h's, shared with ivf_pnp.hip.
+#include "ivf_solve.h"
 
 using namespace ivf;
 
 namespace {
-
-#define DEVINL __device__ __forceinline__
 
 constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kMaxRounds = 4, kMaxIters = 10, kMaxTrials = 10;        // Optimizer.cc:411-413, maxTrialsAfterFailure (levenberg.cpp:51)
@@ -187,15 +184,8 @@ DEVINL double edge_error(const Edge& ed, const Cam& C, const double* q, const do
     return e[0] * (s * e[0]) + e[1] * (s * e[1]);
 }
 
-DEVINL double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);        // a + b == b + a: every lane ends with the same bits
-    return v;
-}
-
 // One evaluation over the level-0 edges at pose (q, t): the robust chi2, and with BUILD the quadratic form (base_unary_edge.hpp:43-72).
-// Leaves the per-wave sums in part[wave][]; the caller's barrier makes them visible.
+// Leaves the per-wave sums in part[wave][]; the caller's barrier makes them visible and lane 0 adds them in wave order (part_sum).
 template <bool BUILD>
 DEVINL void evaluate(const Edge* s_e, int nE, const Cam& C, const double* s_is2, const double* q, const double* t, bool robust,
                      double (*part)[kSums], int tid)
@@ -244,6 +234,8 @@ DEVINL void evaluate(const Edge* s_e, int nE, const Cam& C, const double* s_is2,
     }
 }
 
+DEVINL double part_sum(const double (*part)[kSums], int k) { return wave_order_sum<kWaves>(&part[0][k], kSums); }
+
 __global__ __launch_bounds__(kThreads) void k_pose_opt(PoseParams Pm, const uint8_t* __restrict__ records, const int* __restrict__ frames,
                                                        const float* __restrict__ xw, const uint8_t* __restrict__ hasPoint,
                                                        const float* __restrict__ quality, int nRounds, float* __restrict__ poses,
@@ -255,51 +247,30 @@ __global__ __launch_bounds__(kThreads) void k_pose_opt(PoseParams Pm, const uint
     __shared__ double s_pose[7], s_est[7];                             // the pose of the next evaluation; the estimate (classification)
     __shared__ double s_M[6][6], s_y[6], s_bx[6];
     __shared__ int s_perm[6], s_wcnt[kWaves], s_cont, s_term, s_nbad;
-    const int f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int nf = Pm.nf;
+    const int f = blockIdx.x, tid = threadIdx.x, nf = Pm.nf;
     uint8_t* outl = outlierOut + (size_t)f * nf;
     float* chiO = chi2Out ? chi2Out + (size_t)f * nf : nullptr;
     for (int i = tid; i < nf; i += kThreads) { outl[i] = 0; if (chiO) chiO[i] = 0.0f; }
-    const int ri = frames[f];
-    if (!rec_ok(Pm.nRecords, ri)) { if (tid == 0) nInliers[f] = -1; return; }
-    const uint8_t* rec = records + (size_t)ri * Pm.recBytes;
-    const int nC = rec_count(rec, nf);
-    const ivf_keypoint* kps = rec_kps(rec);
-    const float* ur = rec_uright(rec, nf);
-    const float* X = xw + (size_t)f * nf * 3;
-    const uint8_t* has = hasPoint + (size_t)f * nf;
+    const FrameObs O = frame_obs(records, Pm.recBytes, nf, Pm.nRecords, frames[f], xw, hasPoint, f);
+    if (O.nC < 0) { if (tid == 0) nInliers[f] = -1; return; }
     const float* ql = quality ? quality + (size_t)f * nf : nullptr;
     if (tid < kMaxLevels) s_is2[tid] = (double)Pm.invSigma2[tid];
     if (tid == 0) s_nbad = 0;
 
     // ---- the edges, in keypoint order (Optimizer.cc:310-399)
     const float deltaMono = (float)sqrt(5.991), deltaStereo = (float)sqrt(7.815);   // :286-287
-    int nE = 0;
-    for (int i0 = 0; i0 < nC; i0 += kThreads) {
-        const int i = i0 + tid;
-        const bool on = i < nC && has[i] != 0;
-        const unsigned long long m = __ballot(on);
-        if (lane == 0) s_wcnt[wave] = __popcll(m);
-        __syncthreads();
-        int base = nE, total = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) { const int c = s_wcnt[w]; if (w < wave) base += c; total += c; }
-        if (on) {
-            const ivf_keypoint kp = kps[i];
-            const float u = ur[i];
-            const bool st = !(u < 0);                                  // mvuRight[i] < 0: monocular (:323)
-            const float q = ql ? ql[i] : 1.0f;
-            Edge ed;
-            ed.X[0] = X[3 * i]; ed.X[1] = X[3 * i + 1]; ed.X[2] = X[3 * i + 2];
-            ed.obs[0] = kp.x; ed.obs[1] = kp.y; ed.obs[2] = u;
-            ed.delta = (st ? deltaStereo : deltaMono) * q;             // the float product of :342 / :380
-            const int oct = kp.octave < 0 ? 0 : (kp.octave > kMaxLevels - 1 ? kMaxLevels - 1 : kp.octave);
-            ed.bits = (unsigned)i | ((unsigned)oct << 12) | (st ? kStereoBit : 0u);
-            s_e[base + __popcll(m & ((1ull << lane) - 1ull))] = ed;
-        }
-        nE += total;
-        __syncthreads();
-    }
+    const int nE = compact_ordered<kThreads>(O.nC, s_wcnt, tid, [&](int i) { return O.has[i] != 0; }, [&](int i, int slot) {
+        const ivf_keypoint kp = O.kps[i];
+        const float u = O.uRight[i];
+        const bool st = !(u < 0);                                      // mvuRight[i] < 0: monocular (:323)
+        const float q = ql ? ql[i] : 1.0f;
+        Edge ed;
+        ed.X[0] = O.X[3 * i]; ed.X[1] = O.X[3 * i + 1]; ed.X[2] = O.X[3 * i + 2];
+        ed.obs[0] = kp.x; ed.obs[1] = kp.y; ed.obs[2] = u;
+        ed.delta = (st ? deltaStereo : deltaMono) * q;                 // the float product of :342 / :380
+        ed.bits = (unsigned)i | ((unsigned)clamp_octave(kp.octave) << 12) | (st ? kStereoBit : 0u);
+        s_e[slot] = ed;
+    });
     if (nE < 3) { if (tid == 0) nInliers[f] = 0; return; }            // :403-404 (nE is the same in every thread)
 
     const Cam C = {(double)Pm.fx, (double)Pm.fy, (double)Pm.cx, (double)Pm.cy, (double)Pm.bf};
@@ -345,10 +316,10 @@ __global__ __launch_bounds__(kThreads) void k_pose_opt(PoseParams Pm, const uint
             __syncthreads();
             if (tid == 0) {
 #pragma unroll
-                for (int k = 0; k < 21; k++) H[k] = ((s_part[0][k] + s_part[1][k]) + s_part[2][k]) + s_part[3][k];
+                for (int k = 0; k < 21; k++) H[k] = part_sum(s_part, k);
 #pragma unroll
-                for (int k = 0; k < 6; k++) b[k] = -(((s_part[0][21 + k] + s_part[1][21 + k]) + s_part[2][21 + k]) + s_part[3][21 + k]);
-                cur = ((s_part[0][27] + s_part[1][27]) + s_part[2][27]) + s_part[3][27];
+                for (int k = 0; k < 6; k++) b[k] = -part_sum(s_part, 21 + k);
+                cur = part_sum(s_part, 27);
                 lastEval = est;
                 ini = cur;
                 if (it == 0) {                                         // computeLambdaInit: _tau * max diagonal (:166-180)
@@ -381,7 +352,7 @@ __global__ __launch_bounds__(kThreads) void k_pose_opt(PoseParams Pm, const uint
                 evaluate<false>(s_e, nE, C, s_is2, s_pose, s_pose + 4, robust, s_part, tid);
                 __syncthreads();
                 if (tid == 0) {
-                    double tmp = ((s_part[0][27] + s_part[1][27]) + s_part[2][27]) + s_part[3][27];
+                    double tmp = part_sum(s_part, 27);
                     lastEval = tr;
                     if (!ok2) tmp = 0x1.fffffffffffffp+1023;
                     double scale = 0.0;
@@ -444,86 +415,9 @@ __global__ __launch_bounds__(kThreads) void k_pose_opt(PoseParams Pm, const uint
         // Converter::toCvMat(SE3Quat) (Converter.cc:49-71)
         double R[3][3];
         quat_to_rot(est.q, R);
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-#pragma unroll
-            for (int j = 0; j < 3; j++) T[4 * i + j] = (float)R[i][j];
-            T[4 * i + 3] = (float)est.t[i];
-        }
+        store_pose(T, &R[0][0], est.t);
         nInliers[f] = nE - s_nbad;
     }
-}
-
-// xw[p][i2] = Frame::UnprojectStereo(assign[p][i2]) of the LAST record of pair p under its last pose (the arithmetic of k_track_prepare)
-__global__ __launch_bounds__(256) void k_points_from_pairs(PoseParams Pm, float invfx, float invfy, const uint8_t* __restrict__ records,
-                                                          const int2* __restrict__ pairs, const float* __restrict__ poses,
-                                                          const int* __restrict__ assign, float* __restrict__ xw, uint8_t* __restrict__ hasPoint)
-{
-    const int p = blockIdx.y, i2 = blockIdx.x * 256 + threadIdx.x;
-    if (i2 >= Pm.nf) return;
-    const size_t o = (size_t)p * Pm.nf + i2;
-    float out[3] = {0.0f, 0.0f, 0.0f};
-    uint8_t hp = 0;
-    const int2 pr = pairs[p];
-    if (rec_ok(Pm.nRecords, pr.x)) {
-        const uint8_t* recL = records + (size_t)pr.x * Pm.recBytes;
-        const int a = assign[o];
-        if (a >= 0 && a < rec_count(recL, Pm.nf)) {
-            const float z = rec_depth(recL, Pm.nf)[a];
-            if (z > 0) {
-                float Rl[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tl[3] = {0, 0, 0}, Rwl[9], Owl[3], x3[3];
-                if (poses) load_pose(poses + (size_t)p * 24, Rl, tl);
-#pragma unroll
-                for (int i = 0; i < 3; i++)
-#pragma unroll
-                    for (int j = 0; j < 3; j++) Rwl[3 * i + j] = Rl[3 * j + i];
-                neg_rt_mul(Rl, tl, Owl);
-                const ivf_keypoint kp = rec_kps(recL)[a];
-                x3[0] = (kp.x - Pm.cx) * z * invfx; x3[1] = (kp.y - Pm.cy) * z * invfy; x3[2] = z;
-                mul_add(Rwl, x3, Owl, out);
-                hp = 1;
-            }
-        }
-    }
-    xw[3 * o] = out[0]; xw[3 * o + 1] = out[1]; xw[3 * o + 2] = out[2];
-    hasPoint[o] = hp;
-}
-
-__global__ __launch_bounds__(256) void k_points_from_local(int nf, const ivf_local_point* __restrict__ points, const int* __restrict__ offsets,
-                                                          const int* __restrict__ assign, float* __restrict__ xw, uint8_t* __restrict__ hasPoint)
-{
-    const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= nf) return;
-    const size_t o = (size_t)f * nf + i;
-    const int m0 = offsets[f], M = offsets[f + 1] - m0, a = assign[o];
-    float out[3] = {0.0f, 0.0f, 0.0f};
-    uint8_t hp = 0;
-    if (m0 >= 0 && a >= 0 && a < M) {
-        const float* pos = points[(size_t)m0 + a].pos;
-        out[0] = pos[0]; out[1] = pos[1]; out[2] = pos[2];
-        hp = 1;
-    }
-    xw[3 * o] = out[0]; xw[3 * o + 1] = out[1]; xw[3 * o + 2] = out[2];
-    hasPoint[o] = hp;
-}
-
-// xw[p][i] = GetWorldPos() of the map point that keyframe keypoint assign[p][i] holds (Tracking.cc:1173: mvpMapPoints = vpMapPointMatches)
-__global__ __launch_bounds__(256) void k_points_from_keyframe(int nf, int nRecords, const int2* __restrict__ pairs, const float* __restrict__ kfXw,
-                                                             const int* __restrict__ assign, float* __restrict__ xw, uint8_t* __restrict__ hasPoint)
-{
-    const int p = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= nf) return;
-    const size_t o = (size_t)p * nf + i;
-    const int kf = pairs[p].x, a = assign[o];
-    float out[3] = {0.0f, 0.0f, 0.0f};
-    uint8_t hp = 0;
-    if (rec_ok(nRecords, kf) && a >= 0 && a < nf) {
-        const float* pos = kfXw + ((size_t)kf * nf + a) * 3;
-        out[0] = pos[0]; out[1] = pos[1]; out[2] = pos[2];
-        hp = 1;
-    }
-    xw[3 * o] = out[0]; xw[3 * o + 1] = out[1]; xw[3 * o + 2] = out[2];
-    hasPoint[o] = hp;
 }
 
 PoseParams pose_params(const TrackParams& T, int n_records)
@@ -531,7 +425,8 @@ PoseParams pose_params(const TrackParams& T, int n_records)
     PoseParams P;
     P.nf = T.nf; P.nRecords = n_records; P.recBytes = T.recBytes;
     P.fx = T.fx; P.fy = T.fy; P.cx = T.cx; P.cy = T.cy; P.bf = T.bf;
-    for (int l = 0; l < kMaxLevels; l++) { const float s2 = T.scale[l] * T.scale[l]; P.invSigma2[l] = 1.0f / s2; }   // mvLevelSigma2, mvInvLevelSigma2
+    level_sigma2(T, P.invSigma2);
+    for (int l = 0; l < kMaxLevels; l++) P.invSigma2[l] = 1.0f / P.invSigma2[l];   // mvInvLevelSigma2 = 1.0f / mvLevelSigma2
     return P;
 }
 
@@ -554,47 +449,6 @@ int ivf_tracker_optimize_pose(ivf_tracker* t, const uint8_t* d_records, size_t r
     if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_pose_opt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_pose_opt, dim3(n_frames), dim3(kThreads), lds, st, pose_params(t->P, n_records), d_records, d_frames, d_xw, d_has_point,
                        d_quality, n_rounds, d_poses, d_outlier, d_ninliers, d_chi2);
-    return tracker_end(t, st);
-}
-
-int ivf_tracker_points_from_pairs(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_pairs, int n_pairs,
-                                  const float* d_poses_pairs, const int32_t* d_assign, float* d_xw, uint8_t* d_has_point, void* hip_stream)
-{
-    if (!t || !d_records || !d_pairs || !d_assign || !d_xw || !d_has_point) return fail(IVF_E_INVALID, "null argument");
-    if (((size_t)d_records & 15) != 0) return fail(IVF_E_INVALID, "the record block must be 16-byte aligned");
-    if (n_pairs == 0) return IVF_OK;
-    hipStream_t st = (hipStream_t)hip_stream;
-    const int rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st);
-    if (rc != IVF_OK) return rc;
-    hipLaunchKernelGGL(k_points_from_pairs, dim3((t->P.nf + 255) / 256, n_pairs), dim3(256), 0, st, pose_params(t->P, n_records), t->P.invfx, t->P.invfy, d_records,
-                       (const int2*)d_pairs, d_poses_pairs, d_assign, d_xw, d_has_point);
-    return tracker_end(t, st);
-}
-
-int ivf_tracker_points_from_local(ivf_tracker* t, const ivf_local_point* d_points, const int32_t* d_point_offsets, const int32_t* d_assign, int n_frames,
-                                  float* d_xw, uint8_t* d_has_point, void* hip_stream)
-{
-    if (!t || !d_points || !d_point_offsets || !d_assign || !d_xw || !d_has_point) return fail(IVF_E_INVALID, "null argument");
-    if (((size_t)d_points & 15) != 0) return fail(IVF_E_INVALID, "the point array must be 16-byte aligned");
-    if (n_frames == 0) return IVF_OK;
-    hipStream_t st = (hipStream_t)hip_stream;
-    const int rc = tracker_begin(t, false, 0, 0, n_frames, st);
-    if (rc != IVF_OK) return rc;
-    hipLaunchKernelGGL(k_points_from_local, dim3((t->P.nf + 255) / 256, n_frames), dim3(256), 0, st, t->P.nf, d_points, d_point_offsets, d_assign, d_xw, d_has_point);
-    return tracker_end(t, st);
-}
-
-int ivf_tracker_points_from_keyframe(ivf_tracker* t, const int32_t* d_pairs, int n_pairs, int n_records, const float* d_kf_xw,
-                                     const int32_t* d_assign, float* d_xw, uint8_t* d_has_point, void* hip_stream)
-{
-    if (!t || !d_pairs || !d_kf_xw || !d_assign || !d_xw || !d_has_point) return fail(IVF_E_INVALID, "null argument");
-    if (n_records < 1) return fail(IVF_E_INVALID, "n_records must be >= 1");
-    if (n_pairs == 0) return IVF_OK;
-    hipStream_t st = (hipStream_t)hip_stream;
-    const int rc = tracker_begin(t, false, 0, 0, n_pairs, st);
-    if (rc != IVF_OK) return rc;
-    hipLaunchKernelGGL(k_points_from_keyframe, dim3((t->P.nf + 255) / 256, n_pairs), dim3(256), 0, st, t->P.nf, n_records, (const int2*)d_pairs, d_kf_xw,
-                       d_assign, d_xw, d_has_point);
     return tracker_end(t, st);
 }
 

@@ -1,0 +1,91 @@
+// ivf_solve.h -- what the two solvers of the batched tracker share, ivf_pose.hip (PoseOptimization) and ivf_pnp.hip (PnPsolver), and
+// the searches do not need: the fixed-tree sums, the ordered compaction, a frame's pointer set, the octave clamp, the pose I/O and
+// the level sigma2 table.
+#pragma once
+#include "ivf_tracker.h"
+
+#define DEVINL __device__ __forceinline__
+
+namespace ivf {
+
+// ---- sums with a fixed tree: two runs are bit-identical
+DEVINL double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);        // a + b == b + a: every lane ends with the same bits
+    return v;
+}
+// the per-wave partials part[0], part[stride], ... of NW waves, summed in wave order: ((p0 + p1) + p2) + p3
+template <int NW>
+DEVINL double wave_order_sum(const double* part, int stride)
+{
+    double v = part[0];
+#pragma unroll
+    for (int w = 1; w < NW; w++) v = v + part[w * stride];
+    return v;
+}
+
+// ---- the workgroup-wide compaction of the items i < n with keep(i), in item order; called by all NT threads, s_wcnt [NT / 64] in LDS.
+// Item i gets slot = the number of kept items before it and runs store(i, slot) between the two barriers of its chunk of NT items:
+// what store() wrote to LDS is visible to the workgroup at the return.  Returns the number kept (the same in every thread).
+template <int NT, class Keep, class Store>
+DEVINL int compact_ordered(int n, int* s_wcnt, int tid, Keep keep, Store store)
+{
+    const int wave = tid >> 6, lane = tid & 63;
+    int total = 0;
+    for (int i0 = 0; i0 < n; i0 += NT) {
+        const int i = i0 + tid;
+        const bool on = i < n && keep(i);
+        const unsigned long long m = __ballot(on);
+        if (lane == 0) s_wcnt[wave] = __popcll(m);
+        __syncthreads();
+        int base = total;
+#pragma unroll
+        for (int w = 0; w < NT / 64; w++) { const int c = s_wcnt[w]; if (w < wave) base += c; total += c; }
+        if (on) store(i, base + __popcll(m & ((1ull << lane) - 1ull)));
+        __syncthreads();
+    }
+    return total;
+}
+
+// ---- what a solver reads of frame f: the keypoints of record ri, the points and flags the caller assigned to them.  nC < 0: ri is
+// outside the block of this call, and the kernel refuses the frame in its own way
+struct FrameObs { const ivf_keypoint* kps; const float* uRight; const float* X; const uint8_t* has; int nC; };
+DEVINL FrameObs frame_obs(const uint8_t* records, size_t recBytes, int nf, int nRecords, int ri, const float* xw, const uint8_t* hasPoint, int f)
+{
+    if (!rec_ok(nRecords, ri)) return FrameObs{nullptr, nullptr, nullptr, nullptr, -1};
+    const uint8_t* rec = records + (size_t)ri * recBytes;
+    return FrameObs{rec_kps(rec), rec_uright(rec, nf), xw + (size_t)f * nf * 3, hasPoint + (size_t)f * nf, rec_count(rec, nf)};
+}
+
+// a keypoint's octave as an index of the level tables
+DEVINL int clamp_octave(int o) { return o < 0 ? 0 : (o > kMaxLevels - 1 ? kMaxLevels - 1 : o); }
+
+// ---- a row-major 3x4 pose [R | t] from / to double R[9], t[3]: the float result, or an f64 hypothesis slot of PnpScratch
+template <class T>
+DEVINL void store_pose(T* out, const double* R, const double* t)
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) out[4 * i + j] = (T)R[3 * i + j];
+        out[4 * i + 3] = (T)t[i];
+    }
+}
+DEVINL void load_hyp(const double* hp, double* R, double* t)
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) R[3 * i + j] = hp[4 * i + j];
+        t[i] = hp[4 * i + 3];
+    }
+}
+
+// mvLevelSigma2 (ORBextractor.cc:419-431) of the handle's scale factors; mvInvLevelSigma2 is 1.0f / s2[l]
+inline void level_sigma2(const TrackParams& T, float* s2)
+{
+    for (int l = 0; l < kMaxLevels; l++) s2[l] = T.scale[l] * T.scale[l];
+}
+
+}  // namespace ivf

@@ -60,12 +60,7 @@ __global__ __launch_bounds__(256) void k_track_prepare(TrackParams P, const uint
     //      identity when none are given (zero-motion prior)
     float Rl[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tl[3] = {0, 0, 0}, Rc[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tc[3] = {0, 0, 0};
     if (poses) { load_pose(poses + (size_t)p * 24, Rl, tl); load_pose(poses + (size_t)p * 24 + 12, Rc, tc); }
-    float Rwl[9], Owl[3], twc[3], tlc[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) Rwl[3 * i + j] = Rl[3 * j + i];                    // mRwc = mRcw.t()
-    neg_rt_mul(Rl, tl, Owl);                                                          // mOw = -mRcw.t() * mtcw
+    float twc[3], tlc[3];
     neg_rt_mul(Rc, tc, twc);                                                          // ORBmatcher.cc:1385
     mul_add(Rl, twc, tl, tlc);                                                        // tlc = Rlw * twc + tlw (:1390)
     const bool bForward = tlc[2] > P.b, bBackward = -tlc[2] > P.b;                    // :1392-1393 (bMono = false)
@@ -100,10 +95,8 @@ __global__ __launch_bounds__(256) void k_track_prepare(TrackParams P, const uint
         Query q; q.u = 0; q.v = 0; q.ur = 0; q.bits = 0;
         if (has) {
             const ivf_keypoint kp = kl[i];
-            // Frame::UnprojectStereo (Frame.cc:958-972)
-            float x3[3], xw[3], xc[3];
-            x3[0] = (kp.x - P.cx) * z * P.invfx; x3[1] = (kp.y - P.cy) * z * P.invfy; x3[2] = z;
-            mul_add(Rwl, x3, Owl, xw);
+            float xw[3], xc[3];
+            unproject_stereo(P, Rl, tl, kp, z, xw);                                   // the pose terms in it do not depend on i
             mul_add(Rc, xw, tc, xc);                                                  // ORBmatcher.cc:1405
             const float invzc = (float)(1.0 / (double)xc[2]);                         // :1409
             if (!(invzc < 0)) {

@@ -1,7 +1,9 @@
-// ivf_tracker.h -- the batched tracker handle and what its five translation units share (not part of the public C-ABI):
+// ivf_tracker.h -- the batched tracker handle and what its six translation units share (not part of the public C-ABI):
 // ivf_track.hip (the handle's life cycle and the TrackWithMotionModel search), ivf_track_local.hip (SearchLocalPoints),
-// ivf_track_bow.hip (TrackReferenceKeyFrame), ivf_pose.hip (PoseOptimization) and ivf_pnp.hip (Relocalization's PnPsolver).  One definition of struct ivf_tracker, one host
-// statement of the camera and record constants (TrackParams), and one device text of every piece the searches repeat.
+// ivf_track_bow.hip (TrackReferenceKeyFrame), ivf_track_points.hip (the points a search hands to a solver), ivf_pose.hip
+// (PoseOptimization) and ivf_pnp.hip (Relocalization's PnPsolver).  One definition of struct ivf_tracker, one host statement of the
+// camera and record constants (TrackParams), and one device text of every piece the searches repeat; what only the two solvers
+// repeat is ivf_solve.h's.
 #pragma once
 #include "ivf_bow.h"
 #include <vector>
@@ -50,6 +52,21 @@ __device__ __forceinline__ void load_pose(const float* __restrict__ T, float* R,
         for (int j = 0; j < 3; j++) R[3 * i + j] = T[4 * i + j];
         t[i] = T[4 * i + 3];
     }
+}
+
+// Frame::UnprojectStereo (Frame.cc:958-972) of keypoint kp at depth z under the frame's pose [Rl | tl]: mRwc * x3Dc + mOw with
+// mRwc = mRcw.t() and mOw = -mRcw.t() * mtcw.  The one statement of it: ivf_tracker_run projects these points (k_track_prepare) and
+// ivf_tracker_points_from_pairs hands the same bits to the solvers.
+__device__ __forceinline__ void unproject_stereo(const TrackParams& P, const float* Rl, const float* tl, const ivf_keypoint& kp, float z, float* xw)
+{
+    float Rwl[9], Owl[3], x3[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) Rwl[3 * i + j] = Rl[3 * j + i];
+    neg_rt_mul(Rl, tl, Owl);
+    x3[0] = (kp.x - P.cx) * z * P.invfx; x3[1] = (kp.y - P.cy) * z * P.invfy; x3[2] = z;
+    mul_add(Rwl, x3, Owl, xw);
 }
 
 // ORBmatcher::UpdateQualityScores (ORBmatcher.cc:1108-1121) at the end of a search, for the keypoints i = tid, tid + stride, ... < n of one

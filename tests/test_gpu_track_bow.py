@@ -1,4 +1,4 @@
-"""ivf_tracker_search_by_bow / ivf_tracker_points_from_keyframe (iv_slam_amd/csrc/ivf_track_bow.hip, ivf_pose.hip) -- the matcher part of
+"""ivf_tracker_search_by_bow / ivf_tracker_points_from_keyframe (iv_slam_amd/csrc/ivf_track_bow.hip, ivf_track_points.hip) -- the matcher part of
 Tracking::TrackReferenceKeyFrame (ORB/src/Tracking.cc:1159-1176) for many (keyframe, current frame) pairs on the device -- against the C
 oracle's SearchByBoW on feature vectors built from its own transform, and against the per-call ivf_bow_transform + ivf_bow_vectors +
 ivf_search_by_bow path on the same data.  Every comparison is bit for bit (integers, and the min of floats in the quality update)."""
