@@ -79,10 +79,11 @@ def relu6(x):
     return np.clip(x, F(0), F(6))
 
 
-def forward(W, bgr_u8, out_size, enc_size=(512, 512), return_taps=False, resume=None):
+def forward(W, bgr_u8, out_size, enc_size=(512, 512), return_taps=False, resume=None, all_taps=False, last=None):
     """W: {state_dict name: f32 array}.  Returns (cost_f32 HxW, cost_u8 HxW[, taps]).
-    resume = (i, x): start after block i from its recorded output x (taps["block<i>"], kept for i >= 14) instead of from the image --
-    tests/fcn_probe.py's networks share their encoder."""
+    resume = (i, x): start after block i from its recorded output x (taps["block<i>"]; i = 0: the stem's output taps["f0"]) instead of from the
+    image -- the probe networks of tests/fcn_probe.py and tests/fcn_stage_probe.py share their encoder.
+    all_taps: record every "block<i>" (without it i >= 14 only).  last = i: stop after block i and return (None, None, taps)."""
     from iv_slam_amd.fcn_weights import BLOCKS          # architecture table (data)
     taps = {}
     if resume is None:
@@ -108,8 +109,10 @@ def forward(W, bgr_u8, out_size, enc_size=(512, 512), return_taps=False, resume=
         taps.setdefault("block_absmax", {})[i] = float(np.abs(x).max())     # the un-clamped activations (linear bottleneck + residual)
         if i in (7, 17):
             taps["f%d" % i] = x
-        if i >= 14:
+        if i >= 14 or all_taps:
             taps["block%d" % i] = x
+        if last is not None and i >= last:
+            return None, None, taps
     y = np.maximum(bn(conv2d(x, W["decoder.cbr.0.weight"], 1, 1), W, "decoder.cbr.1"), F(0))
     y = conv2d(y, W["decoder.conv_last.weight"]) + W["decoder.conv_last.bias"][None, :, None, None]
     taps["logits"] = y.astype(np.float32)

@@ -14,9 +14,10 @@ is nine orders below anything the FCN tests resolve.
 
   mutate(name, tensor) -> tensor   is applied at every tap, in graph order, and the graph continues from what it returns: the
                                    fault-injection hook of tests/test_fcn_probe_cpu.py
-  resume = (name, tensor)          start from a recorded "block<i>" tap instead of the image (the probe networks of tests/fcn_probe.py
+  resume = (name, tensor)          start from a recorded "block<i>" or "f0" tap instead of the image (the probe networks of tests/fcn_probe.py
                                    share their encoder: only the tail is recomputed).  mutate is NOT re-applied to the resumed tap.
   keep(name) -> bool               which taps to return (all by default; the early expansions are 50 MB each)
+  stop = name                      return (None, None, taps) right after that tap instead of running on to the cost map
 """
 import numpy as np
 import torch
@@ -26,6 +27,10 @@ MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
 MAX_THREADS = 16
 D = torch.float64
+
+
+class _Stop(Exception):
+    pass
 
 
 def _t(a):
@@ -48,7 +53,7 @@ def preprocess(bgr_u8):
 
 
 @torch.no_grad()
-def forward(W, bgr_u8, out_size, enc_size=(512, 512), mutate=None, resume=None, keep=None):
+def forward(W, bgr_u8, out_size, enc_size=(512, 512), mutate=None, resume=None, keep=None, stop=None):
     from iv_slam_amd.fcn_weights import BLOCKS          # architecture table (data)
     nthreads = torch.get_num_threads()
     torch.set_num_threads(min(nthreads, MAX_THREADS))
@@ -60,6 +65,8 @@ def forward(W, bgr_u8, out_size, enc_size=(512, 512), mutate=None, resume=None, 
                 x = mutate(name, x)
             if keep is None or keep(name):
                 taps[name] = x
+            if name == stop:
+                raise _Stop
             return x
 
         first = 1
@@ -69,8 +76,8 @@ def forward(W, bgr_u8, out_size, enc_size=(512, 512), mutate=None, resume=None, 
             x = tap("f0", x)
         else:
             name, x = resume
-            assert name.startswith("block") and "." not in name, name
-            first = int(name[5:]) + 1
+            assert name == "f0" or (name.startswith("block") and "." not in name), name
+            first = 1 if name == "f0" else int(name[5:]) + 1
             x = x.to(D)
         for i, (inp, oup, t, s, d, res) in enumerate(BLOCKS, start=1):
             if i < first:
@@ -92,6 +99,8 @@ def forward(W, bgr_u8, out_size, enc_size=(512, 512), mutate=None, resume=None, 
         y = F.interpolate(y, size=tuple(out_size), mode="bilinear", align_corners=False)
         cost = torch.sigmoid(20.0 * (y - 0.5))[0, 0].numpy().copy()
         return cost, logits, taps
+    except _Stop:
+        return None, None, taps
     finally:
         torch.set_num_threads(nthreads)
 

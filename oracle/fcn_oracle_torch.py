@@ -24,14 +24,16 @@ def _bn(x, T, p):
     return F.batch_norm(x, T[p + ".running_mean"], T[p + ".running_var"], T[p + ".weight"], T[p + ".bias"], False, 0.0, 1e-5)
 
 
-def _graph(T, x, out_size, enc_size=(512, 512), taps=None, resume=None):
+def _graph(T, x, out_size, enc_size=(512, 512), taps=None, resume=None, all_taps=False):
     """the layer list on a normalised NCHW f32 tensor (RGB) -> cost map [N, H, W] f32.
-    taps: a dict that receives "block14" .. "block17" and "logits"; resume = i: x is block i's recorded output and the list starts after it
-    (tests/fcn_probe.py's networks share their encoder)."""
+    taps: a dict that receives "block14" .. "block17" and "logits" (all_taps: "f0" and every "block<i>"); resume = i: x is block i's recorded
+    output (i = 0: the stem's, "f0") and the list starts after it (the probe networks of tests/ share their encoder)."""
     from iv_slam_amd.fcn_weights import BLOCKS
     if resume is None:
         x = F.interpolate(x, size=enc_size, mode="bilinear", align_corners=False)
         x = F.relu6(_bn(F.conv2d(x, T["encoder.features.0.0.weight"], None, 2, 1), T, "encoder.features.0.1"))
+        if taps is not None and all_taps:
+            taps["f0"] = x
     for i, (inp, oup, t, s, d, res) in enumerate(BLOCKS, start=1):
         if resume is not None and i <= resume:
             continue
@@ -45,7 +47,7 @@ def _graph(T, x, out_size, enc_size=(512, 512), taps=None, resume=None):
             y = F.relu6(_bn(F.conv2d(y, T[p + ".3.weight"], None, s, d, d, inp * t), T, p + ".4"))
             y = _bn(F.conv2d(y, T[p + ".6.weight"]), T, p + ".7")
         x = x + y if res else y
-        if taps is not None and i >= 14:
+        if taps is not None and (i >= 14 or all_taps):
             taps["block%d" % i] = x
     y = F.relu(_bn(F.conv2d(x, T["decoder.cbr.0.weight"], None, 1, 1), T, "decoder.cbr.1"))
     y = F.conv2d(y, T["decoder.conv_last.weight"], T["decoder.conv_last.bias"])
@@ -62,18 +64,18 @@ def _preprocess(bgr_u8):
 
 
 @torch.no_grad()
-def forward(T, bgr_u8, out_size, enc_size=(512, 512), taps=None, resume=None):
+def forward(T, bgr_u8, out_size, enc_size=(512, 512), taps=None, resume=None, all_taps=False):
     """T = prepare(W); bgr_u8 HxWx3 u8 (or a batch NxHxWx3).  Returns (cost f32 [N,]H,W, u8).
     taps / resume = (i, block i's output as a [N,C,64,64] f32 tensor; bgr_u8 is then unused): see _graph."""
     if resume is not None:
         single = False
-        cost = _graph(T, resume[1], out_size, enc_size, taps, resume[0])
+        cost = _graph(T, resume[1], out_size, enc_size, taps, resume[0], all_taps)
     else:
         a = np.asarray(bgr_u8)
         single = a.ndim == 3
         if single:
             a = a[None]
-        cost = _graph(T, _preprocess(a), out_size, enc_size, taps)
+        cost = _graph(T, _preprocess(a), out_size, enc_size, taps, None, all_taps)
     u8 = (cost * 255.0).to(torch.uint8)
     cost, u8 = cost.numpy(), u8.numpy()
     return (cost[0], u8[0]) if single else (cost, u8)
