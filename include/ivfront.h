@@ -631,6 +631,44 @@ int  ivf_tracker_search_by_bow(ivf_tracker* t, const ivf_vocabulary* voc, int le
  * point each keypoint of each record holds.  The frames to optimise are the pairs' current records.  Asynchronous on hip_stream. */
 int  ivf_tracker_points_from_keyframe(ivf_tracker* t, const int32_t* d_pairs, int n_pairs, int n_records, const float* d_kf_xw,
                                       const int32_t* d_assign, float* d_xw, uint8_t* d_has_point, void* hip_stream);
+/* Tracking::Relocalization after its first pose (ORB/src/Tracking.cc:2351-2404), for n_pairs (keyframe, lost frame) pairs of gather
+ * records without leaving the device: ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)
+ * (ORB/src/ORBmatcher.cc:1520-1652; the reference calls it with (10, 100) at Tracking.cc:2375 and (3, 64) at :2391).  For every
+ * keypoint i of the keyframe record, in order: skipped when it holds no point, a bad one or a found one (:1541-1543); x3Dc = Rcw * xw +
+ * tcw, u = fx * xc * invzc + cx with invzc = 1.0 / zc narrowed to float and NO test on the sign of zc (:1547-1554: a point behind the
+ * camera whose projection lands inside the image is searched for); the four bounds (:1556-1559); dist3D = |xw - Ow| inside
+ * [0.8f * min_distance, 1.2f * max_distance] (:1562-1570); MapPoint::PredictScale (MapPoint.cc:407-422); the window of radius
+ * th * scale[level] on levels [level - 1, level + 1] (:1575-1577; level - 1 == -1 is GetFeaturesInArea's own rule, Frame.cc:615-668);
+ * the FIRST minimum of the descriptor distance among the keypoints that hold no point (:1587-1602), accepted when <= orb_dist (:1604);
+ * with check_orientation the 30-bin histogram of keyframe angle - frame angle and ComputeThreeMaxima (:1609-1645): keypoints of the other
+ * bins are freed again after the walk; UpdateQualityScores(CurrentFrame) (:1647-1649) when the quality arrays are given.  Results equal
+ * ivf_search_by_projection_reloc on the same data, bit for bit.
+ * d_pairs [n_pairs][2] = (keyframe record, current record) and d_select [n_pairs] (nullable) as in ivf_tracker_search_by_bow, except
+ * that a pair left out keeps its d_assign: d_select 0 gives d_nmatches = -2, a record index outside [0, n_records) gives -1.
+ * d_poses [n_pairs][12] = CurrentFrame.mTcw (row-major 3x4), NULL = identity.  d_kf_points [n_records][nfeatures] (16-byte aligned) =
+ * the map point each keypoint of each record holds: pos, min_distance, max_distance and desc (GetDescriptor()) are read, flags bit 0 =
+ * no point / isBad(), normal is ignored; the angle is the keyframe record's own keypoint's.  pos must agree with the d_kf_xw that
+ * ivf_tracker_points_from_keyframe reads, which turns d_assign into the solvers' d_xw / d_has_point after this call as after
+ * ivf_tracker_search_by_bow.  d_found [n_pairs][nfeatures] by keyframe keypoint = sAlreadyFound; NULL = the keyframe keypoints present
+ * in d_assign on entry (the rebuild of Tracking.cc:2386-2389).  d_assign [n_pairs][nfeatures], in/out: for each keypoint of the current
+ * frame the keyframe keypoint whose point it holds, or -1; entries >= 0 on entry are occupied (:1590) and never change.  d_nmatches
+ * [n_pairs] = the return value (nadditional).  d_point_quality (by keyframe keypoint) / d_key_quality (by frame keypoint), both
+ * [n_pairs][nfeatures], both or neither, in/out: the update runs over every keypoint that holds a point on return; as in the reference,
+ * where sAlreadyFound always contains what the frame holds, a point must not end on two keypoints (d_found covers d_assign's entries).
+ * IVF_E_INVALID: orb_dist outside [0, 255] (at 256 the reference indexes with -1), th <= 0, n_pairs > max_pairs, a null required
+ * pointer.  Every loop has a compile-time bound: a NaN pose cannot hang the call.  Asynchronous on hip_stream; uses the scratch of
+ * ivf_tracker_search_local (grown to nfeatures queries per pair at the first call) and obeys the handle's one-call-at-a-time rule. */
+int  ivf_tracker_search_reloc(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_pairs, int n_pairs,
+                              const int32_t* d_select, const float* d_poses, const ivf_local_point* d_kf_points, const uint8_t* d_found, float th,
+                              int orb_dist, int check_orientation, float* d_point_quality, float* d_key_quality, int32_t* d_assign,
+                              int32_t* d_nmatches, void* hip_stream);
+/* The set bookkeeping around that search, on d_assign [n_frames][nfeatures] in place: d_assign[f][i] = -1 where
+ * (d_mask[f][i] != 0) != keep_when_set (d_mask [n_frames][nfeatures], NULL = nothing is dropped); then, if d_found is given,
+ * d_found[f][k] = 1 for every k still in d_assign[f], 0 elsewhere.  keep_when_set = 1 on ivf_tracker_solve_pnp's d_inlier with d_found =
+ * sFound is Tracking.cc:2351-2361; keep_when_set = 0 on ivf_tracker_optimize_pose's d_outlier is :2368-2370 and :2398-2400.
+ * n_frames <= max_pairs.  Asynchronous on hip_stream. */
+int  ivf_tracker_filter_assign(ivf_tracker* t, int32_t* d_assign, int n_frames, const uint8_t* d_mask, int keep_when_set, uint8_t* d_found,
+                               void* hip_stream);
 /* Batched PnPsolver (ORB/src/PnPsolver.cc), the step of Tracking::Relocalization (ORB/src/Tracking.cc:2272-2421) between
  * SearchByBoW(pKF, mCurrentFrame, ...) and PoseOptimization: EPnP inside a RANSAC loop, in double as the reference runs it, for frame
  * slot f = record d_frames[f].  The correspondences are those the constructor collects (PnPsolver.cc:71-114): mvKeysUn[i] and

@@ -165,6 +165,8 @@ _SIGS = {
     "ivf_tracker_points_from_local": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, vp]),
     "ivf_tracker_search_by_bow": (C.c_int, [vp, vp, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
     "ivf_tracker_points_from_keyframe": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "ivf_tracker_search_reloc": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "ivf_tracker_filter_assign": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, vp]),
     "ivf_tracker_solve_pnp": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_float, C.c_float,
                                         vp, vp, vp, vp, vp, vp, vp]),
     "ivf_fcn_create": (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),

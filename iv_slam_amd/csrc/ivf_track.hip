@@ -404,6 +404,22 @@ int tracker_end(ivf_tracker* t, hipStream_t st)
     t->ran = true;
     return IVF_OK;
 }
+int tracker_grow_local(ivf_tracker* t, int cap)
+{
+    if (cap <= t->localCap) return IVF_OK;
+    // grow the scratch: the previous call (if any) must be done with the old buffers before they are freed
+    if (t->ran) HIPCHK(hipEventSynchronize(t->evDone));
+    auto drop = [&] { t->release(t->dLQ); t->release(t->dLRad); t->release(t->dLCount); t->release(t->dLLists); t->localCap = 0; };
+    drop();
+    const size_t n = (size_t)t->cfg.max_pairs * (size_t)cap;
+    if (!(t->alloc(t->dLQ, n * sizeof(Query)) && t->alloc(t->dLRad, n * sizeof(float)) && t->alloc(t->dLCount, n * sizeof(int)) &&
+          t->alloc(t->dLLists, n * kListCap * sizeof(unsigned)))) {
+        drop();
+        return fail(IVF_E_NO_DEVICE, "device allocation failed for %d frames x %d local map points", t->cfg.max_pairs, cap);
+    }
+    t->localCap = cap;
+    return IVF_OK;
+}
 }  // namespace ivf
 
 extern "C" {

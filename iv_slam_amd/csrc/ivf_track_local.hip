@@ -19,34 +19,6 @@ namespace {
 
 #define DEVINL __device__ __forceinline__
 
-// glibc >= 2.27 logf (oracle/ivf_oracle.c:orc_logf is the same arithmetic, checked against libm for every positive
-// normal float): what MapPoint::PredictScale's log(ratio) resolves to.  Positive normal arguments only (a distance ratio).
-__constant__ double c_logfT[16][2] = {
-    {0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2}, {0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2},
-    {0x1.49539f0f010bp+0, -0x1.01eae7f513a67p-2},  {0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3},
-    {0x1.30d190c8864a5p+0, -0x1.6574f0ac07758p-3}, {0x1.25e227b0b8eap+0, -0x1.1aa2bc79c81p-3},
-    {0x1.1bb4a4a1a343fp+0, -0x1.a4e76ce8c0e5ep-4}, {0x1.12358f08ae5bap+0, -0x1.1973c5a611cccp-4},
-    {0x1.0953f419900a7p+0, -0x1.252f438e10c1ep-5}, {0x1p+0, 0x0p+0},
-    {0x1.e608cfd9a47acp-1, 0x1.aa5aa5df25984p-5},  {0x1.ca4b31f026aap-1, 0x1.c5e53aa362eb4p-4},
-    {0x1.b2036576afce6p-1, 0x1.526e57720db08p-3},  {0x1.9c2d163a1aa2dp-1, 0x1.bc2860d22477p-3},
-    {0x1.886e6037841edp-1, 0x1.1058bc8a07ee1p-2},  {0x1.767dcf5534862p-1, 0x1.4043057b6ee09p-2}};
-DEVINL float glibc_logf(float x)
-{
-    const unsigned ix = __builtin_bit_cast(unsigned, x);
-    if (ix == 0x3f800000u) return 0.0f;
-    const unsigned tmp = ix - 0x3f330000u;
-    const int i = (int)((tmp >> 19) & 15u);
-    const int k = (int)tmp >> 23;
-    const double z = (double)__builtin_bit_cast(float, ix - (tmp & 0xff800000u)), invc = c_logfT[i][0], logc = c_logfT[i][1];
-    const double r = z * invc - 1.0;
-    const double y0 = logc + (double)k * 0x1.62e42fefa39efp-1;
-    const double r2 = r * r;
-    double y = 0x1.5575b0be00b6ap-2 * r + -0x1.ffffef20a4123p-2;
-    y = -0x1.00ea348b88334p-2 * r2 + y;
-    y = y * r2 + (y0 + r);
-    return (float)y;
-}
-
 static_assert(sizeof(ivf_local_point) == 80, "ivf_local_point is read as five 16-byte pieces");
 constexpr int kLocalNoBlock = 0x40000000;         // assignment made by a point without observations: later points may replace it (:87-89)
 
@@ -92,10 +64,7 @@ __global__ __launch_bounds__(256) void k_local_prepare(TrackParams P, const uint
                         const double dt = (double)PO[0] * (double)mp.normal[0] + (double)PO[1] * (double)mp.normal[1] + (double)PO[2] * (double)mp.normal[2];
                         const float viewCos = (float)(dt / (double)dist);             // :596
                         if (!(viewCos < cosLimit)) {                                  // :598
-                            // MapPoint::PredictScale (MapPoint.cc:407-422)
-                            const float ratio = mp.max_distance / dist;
-                            int lv = (int)ceilf(glibc_logf(ratio) / P.logScale);
-                            lv = lv < 0 ? 0 : (lv >= P.nlevels ? P.nlevels - 1 : lv);
+                            const int lv = predict_scale(P, mp.max_distance, dist);
                             float r = ((double)viewCos > 0.998) ? 2.5f : 4.0f;        // RadiusByViewingCos (ORBmatcher.cc:137-143)
                             if (th != 1.0f) r *= th;                                  // :65-66
                             radius = r * P.scale[lv];                                 // :69
@@ -307,19 +276,8 @@ extern "C" int ivf_tracker_search_local(ivf_tracker* t, const uint8_t* d_records
     hipStream_t st = (hipStream_t)hip_stream;
     const int rc = tracker_begin(t, true, record_bytes, n_records, n_frames, st);
     if (rc != IVF_OK) return rc;
-    if (max_points_per_frame > t->localCap) {
-        // grow the scratch: the previous call (if any) must be done with the old buffers before they are freed
-        if (t->ran) HIPCHK(hipEventSynchronize(t->evDone));
-        auto drop = [&] { t->release(t->dLQ); t->release(t->dLRad); t->release(t->dLCount); t->release(t->dLLists); t->localCap = 0; };
-        drop();
-        const size_t n = (size_t)t->cfg.max_pairs * (size_t)max_points_per_frame;
-        if (!(t->alloc(t->dLQ, n * sizeof(Query)) && t->alloc(t->dLRad, n * sizeof(float)) && t->alloc(t->dLCount, n * sizeof(int)) &&
-              t->alloc(t->dLLists, n * kListCap * sizeof(unsigned)))) {
-            drop();
-            return fail(IVF_E_NO_DEVICE, "device allocation failed for %d frames x %d local map points", t->cfg.max_pairs, max_points_per_frame);
-        }
-        t->localCap = max_points_per_frame;
-    }
+    const int rg = tracker_grow_local(t, max_points_per_frame);
+    if (rg != IVF_OK) return rg;
     TrackParams P = t->P;
     P.nRecords = n_records;
     const int M = max_points_per_frame;

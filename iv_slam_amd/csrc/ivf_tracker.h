@@ -1,6 +1,7 @@
-// ivf_tracker.h -- the batched tracker handle and what its six translation units share (not part of the public C-ABI):
+// ivf_tracker.h -- the batched tracker handle and what its seven translation units share (not part of the public C-ABI):
 // ivf_track.hip (the handle's life cycle and the TrackWithMotionModel search), ivf_track_local.hip (SearchLocalPoints),
-// ivf_track_bow.hip (TrackReferenceKeyFrame), ivf_track_points.hip (the points a search hands to a solver), ivf_pose.hip
+// ivf_track_bow.hip (TrackReferenceKeyFrame), ivf_track_reloc.hip (Relocalization's SearchByProjection and the set bookkeeping around
+// it), ivf_track_points.hip (the points a search hands to a solver), ivf_pose.hip
 // (PoseOptimization) and ivf_pnp.hip (Relocalization's PnPsolver).  One definition of struct ivf_tracker, one host statement of the
 // camera and record constants (TrackParams), and one device text of every piece the searches repeat; what only the two solvers
 // repeat is ivf_solve.h's.
@@ -37,7 +38,44 @@ __device__ __forceinline__ bool rec_ok(int nRecords, int r) { return (unsigned)r
 // the grid geometry of grid_build / grid_walk (ivf_grid.h), by value: the fields keep their place in the kernel arguments
 __device__ __forceinline__ GridGeom geom_of(const TrackParams& P) { return GridGeom{P.minX, P.minY, P.invW, P.invH}; }
 
-// per-query record written by k_track_prepare / k_local_prepare: projection (u, v), ur = u - bf * invzc, and the packed
+// glibc >= 2.27 logf (oracle/ivf_oracle.c:orc_logf is the same arithmetic, checked against libm for every positive
+// normal float): what MapPoint::PredictScale's log(ratio) resolves to.  Positive normal arguments only (a distance ratio); any other
+// bit pattern still indexes inside the table and returns some finite or non-finite float.
+static __constant__ double c_logfT[16][2] = {
+    {0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2}, {0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2},
+    {0x1.49539f0f010bp+0, -0x1.01eae7f513a67p-2},  {0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3},
+    {0x1.30d190c8864a5p+0, -0x1.6574f0ac07758p-3}, {0x1.25e227b0b8eap+0, -0x1.1aa2bc79c81p-3},
+    {0x1.1bb4a4a1a343fp+0, -0x1.a4e76ce8c0e5ep-4}, {0x1.12358f08ae5bap+0, -0x1.1973c5a611cccp-4},
+    {0x1.0953f419900a7p+0, -0x1.252f438e10c1ep-5}, {0x1p+0, 0x0p+0},
+    {0x1.e608cfd9a47acp-1, 0x1.aa5aa5df25984p-5},  {0x1.ca4b31f026aap-1, 0x1.c5e53aa362eb4p-4},
+    {0x1.b2036576afce6p-1, 0x1.526e57720db08p-3},  {0x1.9c2d163a1aa2dp-1, 0x1.bc2860d22477p-3},
+    {0x1.886e6037841edp-1, 0x1.1058bc8a07ee1p-2},  {0x1.767dcf5534862p-1, 0x1.4043057b6ee09p-2}};
+__device__ __forceinline__ float glibc_logf(float x)
+{
+    const unsigned ix = __builtin_bit_cast(unsigned, x);
+    if (ix == 0x3f800000u) return 0.0f;
+    const unsigned tmp = ix - 0x3f330000u;
+    const int i = (int)((tmp >> 19) & 15u);
+    const int k = (int)tmp >> 23;
+    const double z = (double)__builtin_bit_cast(float, ix - (tmp & 0xff800000u)), invc = c_logfT[i][0], logc = c_logfT[i][1];
+    const double r = z * invc - 1.0;
+    const double y0 = logc + (double)k * 0x1.62e42fefa39efp-1;
+    const double r2 = r * r;
+    double y = 0x1.5575b0be00b6ap-2 * r + -0x1.ffffef20a4123p-2;
+    y = -0x1.00ea348b88334p-2 * r2 + y;
+    y = y * r2 + (y0 + r);
+    return (float)y;
+}
+// MapPoint::PredictScale (MapPoint.cc:407-422) as compiled: logf, a float quotient, std::ceil(float), the clamp to [0, nlevels - 1].
+// The one statement of it: k_local_prepare (SearchLocalPoints) and k_reloc_prepare (Relocalization's SearchByProjection).
+__device__ __forceinline__ int predict_scale(const TrackParams& P, float maxDistance, float dist)
+{
+    const float ratio = maxDistance / dist;
+    const int lv = (int)ceilf(glibc_logf(ratio) / P.logScale);
+    return lv < 0 ? 0 : (lv >= P.nlevels ? P.nlevels - 1 : lv);
+}
+
+// per-query record written by k_track_prepare / k_local_prepare / k_reloc_prepare: projection (u, v), ur = u - bf * invzc, and the packed
 // {octave, minLevel + 1, maxLevel + 1, flags: bit 0 valid, bit 1 blocks}
 struct __attribute__((aligned(16))) Query { float u, v, ur; unsigned bits; };
 __device__ __forceinline__ unsigned pack_bits(int oct, int lo, int hi, int valid, int blocks)
@@ -107,7 +145,8 @@ struct ivf_tracker {
     unsigned short* dIdx = nullptr;
     ivf::Query* dQ = nullptr;
     unsigned* dLists = nullptr;
-    // scratch of ivf_tracker_search_local, sized at its first call / grown on demand: [max_pairs][localCap] queries, radii, counts, lists
+    // scratch of ivf_tracker_search_local and ivf_tracker_search_reloc (nfeatures queries per pair), sized at the first call / grown on
+    // demand (tracker_grow_local): [max_pairs][localCap] queries, radii, counts, lists
     ivf::Query* dLQ = nullptr; float* dLRad = nullptr; int* dLCount = nullptr; unsigned* dLLists = nullptr; int localCap = 0;
     ivf::TrackerBowScratch bow{nullptr, nullptr, nullptr, nullptr, nullptr};   // ivf_tracker_search_by_bow: [2 * max_pairs] slots
     ivf::PnpScratch pnp{nullptr, nullptr, nullptr, nullptr};
@@ -134,7 +173,9 @@ struct ivf_tracker {
 
 namespace ivf {
 // tracker_begin: the argument checks every tracker entry point shares, hipSetDevice and the wait for the handle's previous call;
-// tracker_end: the event the next call waits for
+// tracker_end: the event the next call waits for;
+// tracker_grow_local: the local-search scratch (dLQ, dLRad, dLCount, dLLists) for at least `cap` queries per frame / pair
 int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n_records, int n_items, hipStream_t st);
 int tracker_end(ivf_tracker* t, hipStream_t st);
+int tracker_grow_local(ivf_tracker* t, int cap);
 }  // namespace ivf

@@ -146,6 +146,50 @@ class BatchTracker:
         check(self._lib.ivf_tracker_points_from_keyframe(self._h, pairs.data_ptr(), n_pairs, n_rec, kf_xw.data_ptr(), assign.data_ptr(),
                                                          xw.data_ptr(), has_point.data_ptr(), stream_ptr))
 
+    def search_reloc(self, records, pairs, kf_points, assign, nmatches, th=10.0, orb_dist=100, select=None, poses=None, found=None,
+                     check_orientation=True, point_quality=None, key_quality=None, stream_ptr=None):
+        """ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORB/src/ORBmatcher.cc:1520-1652) as
+        Tracking::Relocalization runs it after its first pose (ORB/src/Tracking.cc:2375 with (10, 100), :2391 with (3, 64)), for n_pairs
+        (keyframe, current) record pairs.  pairs: torch.int32 [n_pairs, 2]; select: torch.int32 [n_pairs] or None, 0 leaves a pair out
+        (nmatches -2, assign untouched); poses: torch.float32 [n_pairs, 12] = CurrentFrame.mTcw or None = identity; kf_points:
+        torch.uint8 view of LOCAL_POINT_DTYPE records [n_records, nfeatures] (80 B each), the map point each keypoint of each record holds
+        (flags bit 0 = none / bad); found: torch.uint8 [n_pairs, nfeatures] by keyframe keypoint (sAlreadyFound) or None = the keyframe
+        keypoints in assign on entry; assign: torch.int32 [n_pairs, nfeatures], in/out: the keyframe keypoint whose point each frame
+        keypoint holds or -1, entries >= 0 on entry are occupied and kept; nmatches: torch.int32 [n_pairs] (nadditional);
+        point_quality (by keyframe keypoint) / key_quality (by frame keypoint): torch.float32 [n_pairs, nfeatures] in/out or None.
+        Asynchronous on the given stream."""
+        n_rec = records.numel() // self.record_bytes
+        n_pairs = pairs.shape[0]
+        assert pairs.dtype.is_floating_point is False and pairs.element_size() == 4 and pairs.is_contiguous()
+        assert assign.element_size() == 4 and assign.is_contiguous() and assign.numel() >= n_pairs * self.nfeatures and nmatches.numel() >= n_pairs
+        assert select is None or (select.element_size() == 4 and select.is_contiguous() and select.numel() >= n_pairs)
+        assert poses is None or (poses.is_contiguous() and poses.element_size() == 4 and poses.numel() == n_pairs * 12), "poses are per pair: [n_pairs, 12]"
+        assert kf_points.is_contiguous() and kf_points.numel() * kf_points.element_size() >= n_rec * self.nfeatures * 80
+        assert found is None or (found.element_size() == 1 and found.is_contiguous() and found.numel() >= n_pairs * self.nfeatures)
+        for q in (point_quality, key_quality):
+            assert q is None or (q.is_contiguous() and q.element_size() == 4 and q.numel() >= n_pairs * self.nfeatures)
+        check(self._lib.ivf_tracker_search_reloc(self._h, records.data_ptr(), self.record_bytes, n_rec, pairs.data_ptr(), n_pairs,
+                                                 None if select is None else select.data_ptr(),
+                                                 None if poses is None else poses.data_ptr(), kf_points.data_ptr(),
+                                                 None if found is None else found.data_ptr(), float(th), int(orb_dist),
+                                                 int(bool(check_orientation)),
+                                                 None if point_quality is None else point_quality.data_ptr(),
+                                                 None if key_quality is None else key_quality.data_ptr(),
+                                                 assign.data_ptr(), nmatches.data_ptr(), stream_ptr))
+
+    def filter_assign(self, assign, mask=None, keep_when_set=True, found=None, stream_ptr=None):
+        """The set bookkeeping of Tracking::Relocalization around search_reloc(), in place: assign[f, i] = -1 where (mask[f, i] != 0) !=
+        keep_when_set (mask: torch.uint8 [n_frames, nfeatures] or None = nothing is dropped); then found[f, k] = 1 for every k still in
+        assign[f], 0 elsewhere (found: torch.uint8 [n_frames, nfeatures] or None).  mask = solve_pnp()'s inlier, keep_when_set = True and
+        found = sFound: Tracking.cc:2351-2361; mask = optimize_pose()'s outlier, keep_when_set = False: :2368-2370, :2398-2400.
+        assign: torch.int32 [n_frames, nfeatures].  Asynchronous on the given stream."""
+        n_frames = assign.numel() // self.nfeatures
+        assert assign.element_size() == 4 and assign.is_contiguous() and assign.numel() == n_frames * self.nfeatures
+        for m in (mask, found):
+            assert m is None or (m.element_size() == 1 and m.is_contiguous() and m.numel() >= n_frames * self.nfeatures)
+        check(self._lib.ivf_tracker_filter_assign(self._h, assign.data_ptr(), n_frames, None if mask is None else mask.data_ptr(),
+                                                  int(bool(keep_when_set)), None if found is None else found.data_ptr(), stream_ptr))
+
     def optimize_pose(self, records, frames, xw, has_point, poses, outlier, ninliers, quality=None, n_rounds=4, chi2=None, stream_ptr=None):
         """Optimizer::PoseOptimization (ORB/src/Optimizer.cc:251-503) for n_frames frames in one kernel launch.  frames: torch.int32
         [n_frames] record indices; xw: torch.float32 [n_frames, nfeatures, 3] world position of the point each keypoint holds;
