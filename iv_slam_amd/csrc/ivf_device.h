@@ -6,6 +6,8 @@
 #include <vector>
 #include "../../include/ivfront.h"
 
+#define DEVINL __device__ __forceinline__
+
 namespace ivf {
 
 constexpr int kMaxLevels = IVF_MAX_LEVELS;

@@ -21,8 +21,6 @@
 
 namespace ivf {
 
-#define DEVINL __device__ __forceinline__
-
 static __device__ const int8_t __attribute__((aligned(16))) d_pattern[1024] = {
 #include "../../include/ivf_pattern31.inc"
 };

@@ -12,8 +12,6 @@
 
 namespace ivf {
 
-#define DEVINL __device__ __forceinline__
-
 // ------------------------------------------------------------------------------------------------
 // libstdc++ std::nth_element (bits/stl_algo.h __introselect) on 64-bit keys whose high word is the
 // response as f32 bits (responses are >= 0, so unsigned compare == float compare).  Must replay the

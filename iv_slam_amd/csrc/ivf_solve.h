@@ -4,8 +4,6 @@
 #pragma once
 #include "ivf_tracker.h"
 
-#define DEVINL __device__ __forceinline__
-
 namespace ivf {
 
 // ---- sums with a fixed tree: two runs are bit-identical

@@ -20,16 +20,30 @@
 //   k_track_greedy   one wave per frame pair walks the queries in order: assignment state, uRight and angles of the current
 //                    frame live in LDS, the lists of the next 16 queries are in registers before they are needed, the first
 //                    minimum is a DPP row_shr / row_bcast reduction of (distance << 6 | list position); histogram in one VGPR
-//                    (lane = bin).  Queries whose window overflowed the list are re-walked in place against the live state.
+//                    (lane = bin).  Queries whose window overflowed the list are re-walked in place against the live state
+//                    (first_min_in_window, ivf_search.h).
 // The grid itself -- grid_build / grid_walk, here with unsigned short indices (nfeatures <= 4096) -- is ivf_grid.h's, shared with the
-// device-resident ivf_frame (ivf_match.hip).
-#include "ivf_tracker.h"
+// device-resident ivf_frame (ivf_match.hip); the pieces the three projection searches repeat (liveness, the ordered list, the gates, the
+// first minimum) are ivf_search.h's.  This file also owns the candidate scratch all three use, one call at a time
+// (tracker_grow_queries), and their shared argument checks (search_args_ok).
+#include "ivf_search.h"
 #include <climits>
 #include <cstring>
 
 using namespace ivf;
 
 namespace {
+
+// k_track_greedy's candidate admission against the live state in LDS (ORBmatcher.cc:1447-1457): current keypoint i2 is out when a point
+// with observations holds it, or when its right coordinate fails ur_admits
+constexpr int kNoBlock = 0x10000;                 // flag on an assignment made by a point without observations: it does not block (:1447-1449)
+DEVINL bool track_admits(const int* s_assign, const float* s_ur, int i2, float qur, float radius)
+{
+    const int a = s_assign[i2];
+    const bool held = a >= 0 && !(a & kNoBlock);
+    const bool ur = ur_admits(s_ur[i2], qur, radius);
+    return !held && ur;
+}
 
 // ------------------------------------------------------------------------------------------------
 // k_track_prepare: one workgroup per frame pair
@@ -46,7 +60,7 @@ __global__ __launch_bounds__(256) void k_track_prepare(TrackParams P, const uint
     __shared__ int s_nStereo, s_nClose;
     const int p = blockIdx.x, tid = threadIdx.x;
     const int2 pr = pairs[p];
-    if (!rec_ok(P.nRecords, pr.x) || !rec_ok(P.nRecords, pr.y)) { if (tid == 0) retryFlag[p] = 0; return; }
+    if (!pair_live(P.nRecords, pr, nullptr, p)) { if (tid == 0) retryFlag[p] = 0; return; }
     const uint8_t* recL = records + (size_t)pr.x * P.recBytes;
     const uint8_t* recC = records + (size_t)pr.y * P.recBytes;
     const int nL = rec_count(recL, P.nf), nC = rec_count(recC, P.nf);
@@ -101,7 +115,7 @@ __global__ __launch_bounds__(256) void k_track_prepare(TrackParams P, const uint
             const float invzc = (float)(1.0 / (double)xc[2]);                         // :1409
             if (!(invzc < 0)) {
                 const float u = P.fx * xc[0] * invzc + P.cx, v = P.fy * xc[1] * invzc + P.cy;
-                if (!(u < P.minX || u > P.maxX) && !(v < P.minY || v > P.maxY)) {
+                if (in_image(P, u, v)) {
                     const int o = kp.octave;
                     int lo, hi;
                     if (bForward) { lo = o; hi = -1; } else if (bBackward) { lo = 0; hi = o; } else { lo = o - 1; hi = o + 1; }   // :1429-1434
@@ -126,7 +140,7 @@ __global__ __launch_bounds__(256) void k_track_window(TrackParams P, const uint8
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (onlyFlagged && !retryFlag[p]) return;
     const int2 pr = pairs[p];
-    if (!rec_ok(P.nRecords, pr.x) || !rec_ok(P.nRecords, pr.y)) return;
+    if (!pair_live(P.nRecords, pr, nullptr, p)) return;
     const uint8_t* recL = records + (size_t)pr.x * P.recBytes;
     const uint8_t* recC = records + (size_t)pr.y * P.recBytes;
     const int nL = rec_count(recL, P.nf);
@@ -140,14 +154,7 @@ __global__ __launch_bounds__(256) void k_track_window(TrackParams P, const uint8
         const uint4 qa = qd[0], qb = qd[1];
         unsigned* L = lists + ((size_t)p * P.nf + i) * kListCap;
         grid_walk(geom_of(P), rec_kps(recC), rec_desc(recC, P.nf), gStart + (size_t)p * (kGC * kGR + 1), gIdx + (size_t)p * P.nf,
-                  q.u, q.v, r, lo, hi, qa, qb, lane, [&](bool ok, int i2, int d) {
-                      const unsigned long long m = __ballot(ok);
-                      if (ok) {
-                          const int pos = total + __popcll(m & ((1ull << lane) - 1ull));
-                          if (pos < kListCap) L[pos] = (unsigned)i2 | ((unsigned)d << 16);
-                      }
-                      total += __popcll(m);
-                  });
+                  q.u, q.v, r, lo, hi, qa, qb, lane, [&](bool ok, int i2, int d) { list_append(ok, lane, total, L, (unsigned)i2 | ((unsigned)d << 16)); });
     }
     if (lane == 0) count[(size_t)p * P.nf + i] = total;
 }
@@ -171,7 +178,7 @@ __global__ __launch_bounds__(64) void k_track_greedy(TrackParams P, const uint8_
     float* s_ang = (float*)(s_mem + 2 * P.nf);                // [nf] CurrentFrame.mvKeysUn[].angle
     unsigned* s_match = (unsigned*)(s_mem + 3 * P.nf);        // [nf] matches in the order they were made: idx2 | bin << 16
     const int2 pr = pairs[p];
-    if (!rec_ok(P.nRecords, pr.x) || !rec_ok(P.nRecords, pr.y)) {
+    if (!pair_live(P.nRecords, pr, nullptr, p)) {
         for (int i = lane; i < P.nf; i += 64) assignOut[(size_t)p * P.nf + i] = -1;
         if (lane == 0) { nmatchesOut[p] = -1; retryFlag[p] = 0; }
         return;
@@ -236,45 +243,19 @@ __global__ __launch_bounds__(64) void k_track_greedy(TrackParams P, const uint8_
                 const unsigned bits = (unsigned)__builtin_amdgcn_readlane((int)myQ.bits, k);
                 const float radius = th * P.scale[bits & 0xff];
                 int bestDist = 256, bestIdx2 = -1;
+                auto admits = [&](int i2) { return track_admits(s_assign, s_ur, i2, qur, radius); };
                 if (cnt <= kListCap) {
                     const unsigned e = Lp[(size_t)i * kListCap + lane];
                     const int i2 = e & 0xffff, d = e >> 16;
-                    bool ok = lane < cnt;
-                    if (ok) ok = track_admits(s_assign, s_ur, i2, qur, radius);
-                    const unsigned key1 = ok ? ((unsigned)d << 6) | (unsigned)lane : 0xffffffffu;
-                    const unsigned best = wave_min_u32(key1);                           // first minimum in list order (:1463-1467)
-                    if (best != 0xffffffffu) {
-                        bestDist = best >> 6;
-                        bestIdx2 = __builtin_amdgcn_readlane(i2, best & 63);
-                    }
+                    first_min_in_list(lane < cnt, d, i2, lane, admits, bestDist, bestIdx2);  // first minimum in list order (:1463-1467)
                 } else {
                     // the window overflowed its list: walk it again, against the live assignment state
                     const float qu = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myQ.u), k));
                     const float qv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myQ.v), k));
                     const int lo = (int)((bits >> 8) & 0xff) - 1, hi = (int)((bits >> 16) & 0xff) - 1;
                     const uint4* qd = (const uint4*)(rec_desc(recL, P.nf) + (size_t)i * 32);
-                    const uint4 qa = qd[0], qb = qd[1];
-                    unsigned long long bestKey = ~0ull;                                    // dist << 32 | ordinal
-                    unsigned ordinal = 0;
-                    grid_walk(geom_of(P), kc, rec_desc(recC, P.nf), gStart + (size_t)p * (kGC * kGR + 1), gIdx + (size_t)p * P.nf, qu, qv, radius,
-                              lo, hi, qa, qb, lane, [&](bool ok, int i2, int d) {
-                                  const unsigned long long m = __ballot(ok);
-                                  const unsigned pos = ordinal + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-                                  ordinal += (unsigned)__popcll(m);
-                                  if (ok) ok = track_admits(s_assign, s_ur, i2, qur, radius);
-                                  if (ok) {
-                                      const unsigned long long key2 = ((unsigned long long)(unsigned)d << 32) | (unsigned long long)pos;
-                                      if (key2 < bestKey) { bestKey = key2; bestIdx2 = i2; }
-                                  }
-                              });
-                    // lanes hold their own best (key, i2): reduce to the smallest key
-                    unsigned hiK = (unsigned)(bestKey >> 32), loK = (unsigned)bestKey;
-                    const unsigned minHi = wave_min_u32(hiK);
-                    const unsigned loC = hiK == minHi ? loK : 0xffffffffu;
-                    const unsigned minLo = wave_min_u32(loC);
-                    const unsigned long long who = __ballot(hiK == minHi && loK == minLo && bestKey != ~0ull);
-                    if (who) { bestDist = (int)minHi; bestIdx2 = __builtin_amdgcn_readlane(bestIdx2, __ffsll((long long)who) - 1); }
-                    else bestIdx2 = -1;
+                    first_min_in_window(geom_of(P), kc, rec_desc(recC, P.nf), gStart + (size_t)p * (kGC * kGR + 1), gIdx + (size_t)p * P.nf, qu, qv, radius,
+                                        lo, hi, qd[0], qd[1], lane, admits, bestDist, bestIdx2);
                 }
                 if (bestIdx2 >= 0 && bestDist <= 100) {                                     // TH_HIGH (:1469)
                     if (lane == 0) s_assign[bestIdx2] = ((bits >> 25) & 1u) ? i : (i | kNoBlock);
@@ -404,20 +385,30 @@ int tracker_end(ivf_tracker* t, hipStream_t st)
     t->ran = true;
     return IVF_OK;
 }
-int tracker_grow_local(ivf_tracker* t, int cap)
+int search_args_ok(const ivf_tracker* t, const void* records, const void* items, bool has_points, const void* points, const void* assign,
+                   const void* nmatches, int n_items, const float* point_quality, const float* key_quality)
 {
-    if (cap <= t->localCap) return IVF_OK;
+    if (!t || !records || !items || (has_points && !points) || !assign || !nmatches) return fail(IVF_E_INVALID, "null argument");
+    if (((size_t)records & 15) != 0 || ((size_t)points & 15) != 0)
+        return fail(IVF_E_INVALID, has_points ? "the record block and the point array must be 16-byte aligned" : "the record block must be 16-byte aligned");
+    if (n_items != 0 && (point_quality == nullptr) != (key_quality == nullptr))
+        return fail(IVF_E_INVALID, "d_point_quality and d_key_quality come together");
+    return IVF_OK;
+}
+int tracker_grow_queries(ivf_tracker* t, int cap)
+{
+    if (cap <= t->queryCap) return IVF_OK;
     // grow the scratch: the previous call (if any) must be done with the old buffers before they are freed
     if (t->ran) HIPCHK(hipEventSynchronize(t->evDone));
-    auto drop = [&] { t->release(t->dLQ); t->release(t->dLRad); t->release(t->dLCount); t->release(t->dLLists); t->localCap = 0; };
+    auto drop = [&] { t->release(t->dQ); t->release(t->dLRad); t->release(t->dCount); t->release(t->dLists); t->queryCap = 0; };
     drop();
     const size_t n = (size_t)t->cfg.max_pairs * (size_t)cap;
-    if (!(t->alloc(t->dLQ, n * sizeof(Query)) && t->alloc(t->dLRad, n * sizeof(float)) && t->alloc(t->dLCount, n * sizeof(int)) &&
-          t->alloc(t->dLLists, n * kListCap * sizeof(unsigned)))) {
+    if (!(t->alloc(t->dQ, n * sizeof(Query)) && t->alloc(t->dLRad, n * sizeof(float)) && t->alloc(t->dCount, n * sizeof(int)) &&
+          t->alloc(t->dLists, n * kListCap * sizeof(unsigned)))) {
         drop();
-        return fail(IVF_E_NO_DEVICE, "device allocation failed for %d frames x %d local map points", t->cfg.max_pairs, cap);
+        return fail(IVF_E_NO_DEVICE, "device allocation failed for %d frames x %d queries", t->cfg.max_pairs, cap);
     }
-    t->localCap = cap;
+    t->queryCap = cap;
     return IVF_OK;
 }
 }  // namespace ivf
@@ -469,11 +460,10 @@ int ivf_tracker_create(const ivf_track_config* cfg, ivf_tracker** out)
     const size_t np = (size_t)cfg->max_pairs, nf = (size_t)cfg->nfeatures;
     t->ldsBytes = nf * 20;
     const bool ok = t->alloc(t->dStart, np * (kGC * kGR + 1) * sizeof(int)) && t->alloc(t->dIdx, np * nf * sizeof(unsigned short)) &&
-                    t->alloc(t->dQ, np * nf * sizeof(Query)) && t->alloc(t->dCount, np * nf * sizeof(int)) &&
-                    t->alloc(t->dLists, np * nf * kListCap * sizeof(unsigned)) && t->alloc(t->dRetry, np * sizeof(int)) &&
+                    t->alloc(t->dRetry, np * sizeof(int)) &&
                     t->alloc(t->bow.nodeKey, 2 * np * nf * sizeof(int)) && t->alloc(t->bow.fvNode, 2 * np * nf * sizeof(int)) &&
                     t->alloc(t->bow.fvStart, 2 * np * (nf + 1) * sizeof(int)) && t->alloc(t->bow.fvIdx, 2 * np * nf * sizeof(int)) &&
-                    t->alloc(t->bow.fvN, 2 * np * sizeof(int));
+                    t->alloc(t->bow.fvN, 2 * np * sizeof(int)) && tracker_grow_queries(t, cfg->nfeatures) == IVF_OK;
     if (!ok) {
         ivf_tracker_destroy(t);
         return fail(IVF_E_NO_DEVICE, "device allocation failed for a tracker of %d pairs x %d features", cfg->max_pairs, cfg->nfeatures);
@@ -495,15 +485,15 @@ int ivf_tracker_run(ivf_tracker* t, const uint8_t* d_records, size_t record_byte
                     const float* d_poses, const uint8_t* d_point_flags, float* d_point_quality, float* d_key_quality,
                     int32_t* d_assign, int32_t* d_nmatches, void* hip_stream)
 {
-    if (!t || !d_records || !d_pairs || !d_assign || !d_nmatches) return fail(IVF_E_INVALID, "null argument");
-    if (((size_t)d_records & 15) != 0) return fail(IVF_E_INVALID, "the record block must be 16-byte aligned");
-    if (n_pairs == 0) return IVF_OK;
-    if ((d_point_quality == nullptr) != (d_key_quality == nullptr)) return fail(IVF_E_INVALID, "d_point_quality and d_key_quality come together");
+    const int ra = search_args_ok(t, d_records, d_pairs, false, nullptr, d_assign, d_nmatches, n_pairs, d_point_quality, d_key_quality);
+    if (ra != IVF_OK || n_pairs == 0) return ra;
     hipStream_t st = (hipStream_t)hip_stream;
     // the per-pair grids, query tables and candidate lists are scratch of the HANDLE: a run enqueued on another stream than the
     // previous one queues behind it (use one tracker per stream to let runs overlap)
     const int rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st);
     if (rc != IVF_OK) return rc;
+    const int rg = tracker_grow_queries(t, t->P.nf);                                   // a no-op unless a larger request failed
+    if (rg != IVF_OK) return rg;
     TrackParams P = t->P;
     P.nRecords = n_records;
     const int2* pairs = (const int2*)d_pairs;

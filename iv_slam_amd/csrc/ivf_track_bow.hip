@@ -18,31 +18,25 @@
 //   k_bow_search   one workgroup per pair: node merge (binary search of every keyframe node in the frame's list: only equal ids match,
 //                  the lower_bound walk of :186-270), the common nodes handed to the four waves one at a time, the greedy walk,
 //                  the rotation filter (rot_bin / rot_three_maxima, ivf_device.h), the quality epilogue (ivf_tracker.h)
-#include "ivf_tracker.h"
+// Which pairs take part (pair_live) is ivf_search.h's, the one test of it for every search of the handle.
+#include "ivf_search.h"
 
 using namespace ivf;
 
 namespace {
-
-#define DEVINL __device__ __forceinline__
 
 struct BowParams {
     int nf, nRecords, nidLevel, checkOri;
     size_t recBytes;
     float nnRatio;
 };
-// a pair takes part when the mask selects it and both record indices lie inside the block
-DEVINL bool pair_live(const BowParams& P, const int2 pr, const int* __restrict__ select, int p)
-{
-    return (!select || select[p] != 0) && rec_ok(P.nRecords, pr.x) && rec_ok(P.nRecords, pr.y);
-}
 
 __global__ __launch_bounds__(256) void k_bow_nodes(BowParams P, VocabularyView V, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
                                                   const int* __restrict__ select, int* __restrict__ nodeKey)
 {
     const int s = blockIdx.y, p = s >> 1, tid = threadIdx.x;
     const int2 pr = pairs[p];
-    if (!pair_live(P, pr, select, p)) return;
+    if (!pair_live(P.nRecords, pr, select, p)) return;
     const uint8_t* rec = records + (size_t)((s & 1) ? pr.y : pr.x) * P.recBytes;
     const int n = rec_count(rec, P.nf);
     if ((int)blockIdx.x * 16 >= n) return;
@@ -64,7 +58,7 @@ __global__ __launch_bounds__(256) void k_bow_featvec(BowParams P, const uint8_t*
     __shared__ int s_m;
     const int s = blockIdx.x, p = s >> 1, tid = threadIdx.x;
     const int2 pr = pairs[p];
-    if (!pair_live(P, pr, select, p)) return;
+    if (!pair_live(P.nRecords, pr, select, p)) return;
     const uint8_t* rec = records + (size_t)((s & 1) ? pr.y : pr.x) * P.recBytes;
     const int n = rec_count(rec, P.nf);
     unsigned npad = 256;
@@ -135,7 +129,7 @@ __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* 
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     int* out = assignOut + (size_t)p * P.nf;
     const int2 pr = pairs[p];
-    if (!pair_live(P, pr, select, p)) {
+    if (!pair_live(P.nRecords, pr, select, p)) {
         for (int i = tid; i < P.nf; i += 256) out[i] = -1;
         if (tid == 0) nmatchesOut[p] = (select && select[p] == 0) ? -2 : -1;
         return;

@@ -11,13 +11,13 @@
 //   k_local_window   one wave per (frame, map point): ordered candidate list, entry = index | octave << 12 | distance << 16
 //   k_local_greedy   one wave per frame: walks the points in order against the occupancy state in LDS; best and second best are
 //                    two DPP minimum reductions of (distance << 12 | list position)
-#include "ivf_tracker.h"
+// The map-point gates, the right-coordinate gate, the ordered list and the prefetched walk over the lists are ivf_search.h's; the candidate
+// scratch is the handle's one set (ivf_track.hip: tracker_grow_queries), here with max_points_per_frame queries per frame.
+#include "ivf_search.h"
 
 using namespace ivf;
 
 namespace {
-
-#define DEVINL __device__ __forceinline__
 
 static_assert(sizeof(ivf_local_point) == 80, "ivf_local_point is read as five 16-byte pieces");
 constexpr int kLocalNoBlock = 0x40000000;         // assignment made by a point without observations: later points may replace it (:87-89)
@@ -55,22 +55,17 @@ __global__ __launch_bounds__(256) void k_local_prepare(TrackParams P, const uint
             if (!(Pc[2] < 0.0f)) {                                                    // :571
                 const float invz = 1.0f / Pc[2];
                 const float u = P.fx * Pc[0] * invz + P.cx, v = P.fy * Pc[1] * invz + P.cy;
-                if (!(u < P.minX || u > P.maxX) && !(v < P.minY || v > P.maxY)) {     // :579-582
-                    const float PO[3] = {mp.pos[0] - Ow[0], mp.pos[1] - Ow[1], mp.pos[2] - Ow[2]};
-                    const double n2 = (double)PO[0] * (double)PO[0] + (double)PO[1] * (double)PO[1] + (double)PO[2] * (double)PO[2];
-                    const float dist = (float)sqrt(n2);                               // cv::norm (:588)
-                    const float minD = 0.8f * mp.min_distance, maxD = 1.2f * mp.max_distance;     // MapPoint.cc:378-388
-                    if (!(dist < minD || dist > maxD)) {                              // :590
-                        const double dt = (double)PO[0] * (double)mp.normal[0] + (double)PO[1] * (double)mp.normal[1] + (double)PO[2] * (double)mp.normal[2];
-                        const float viewCos = (float)(dt / (double)dist);             // :596
-                        if (!(viewCos < cosLimit)) {                                  // :598
-                            const int lv = predict_scale(P, mp.max_distance, dist);
-                            float r = ((double)viewCos > 0.998) ? 2.5f : 4.0f;        // RadiusByViewingCos (ORBmatcher.cc:137-143)
-                            if (th != 1.0f) r *= th;                                  // :65-66
-                            radius = r * P.scale[lv];                                 // :69
-                            q.u = u; q.v = v; q.ur = u - P.bf * invz;                 // :606-608
-                            q.bits = (unsigned)lv | (1u << 24) | ((unsigned)((mp.flags >> 1) & 1) << 25);
-                        }
+                float dist; int lv;
+                if (in_image(P, u, v) && point_range_level(P, mp, Ow, dist, lv)) {     // :579-582, :588-590
+                    const float PO[3] = {mp.pos[0] - Ow[0], mp.pos[1] - Ow[1], mp.pos[2] - Ow[2]};   // P - Ow again: the same bits
+                    const double dt = (double)PO[0] * (double)mp.normal[0] + (double)PO[1] * (double)mp.normal[1] + (double)PO[2] * (double)mp.normal[2];
+                    const float viewCos = (float)(dt / (double)dist);                 // :596
+                    if (!(viewCos < cosLimit)) {                                      // :598
+                        float r = ((double)viewCos > 0.998) ? 2.5f : 4.0f;            // RadiusByViewingCos (ORBmatcher.cc:137-143)
+                        if (th != 1.0f) r *= th;                                      // :65-66
+                        radius = r * P.scale[lv];                                     // :69
+                        q.u = u; q.v = v; q.ur = u - P.bf * invz;                     // :606-608
+                        q.bits = (unsigned)lv | (1u << 24) | ((unsigned)((mp.flags >> 1) & 1) << 25);
                     }
                 }
             }
@@ -103,13 +98,8 @@ __global__ __launch_bounds__(256) void k_local_window(TrackParams P, const uint8
         unsigned* L = lists + ((size_t)f * maxM + m) * kListCap;
         grid_walk(geom_of(P), kc, rec_desc(recC, P.nf), gStart + (size_t)f * (kGC * kGR + 1), gIdx + (size_t)f * P.nf,
                   q.u, q.v, r, lv - 1, lv, qa, qb, lane, [&](bool ok, int i2, int d) {
-                      if (ok) { const float u2 = urC[i2]; if (u2 > 0) { const float er = fabsf(q.ur - u2); if (er > r) ok = false; } }   // :91-96
-                      const unsigned long long mk = __ballot(ok);
-                      if (ok) {
-                          const int pos = total + __popcll(mk & ((1ull << lane) - 1ull));
-                          if (pos < kListCap) L[pos] = (unsigned)i2 | ((unsigned)kc[i2].octave << 12) | ((unsigned)d << 16);
-                      }
-                      total += __popcll(mk);
+                      if (ok) ok = ur_admits(urC[i2], q.ur, r);                           // :91-96
+                      list_append(ok, lane, total, L, (unsigned)i2 | ((unsigned)kc[i2].octave << 12) | ((unsigned)d << 16));
                   });
     }
     if (lane == 0) count[(size_t)f * maxM + m] = total;
@@ -163,93 +153,63 @@ __global__ __launch_bounds__(64) void k_local_greedy(TrackParams P, const uint8_
     int nm = 0;
     auto blocked = [&](int i2) { const int a = s_assign[i2]; return a == -2 || (a >= 0 && !(a & kLocalNoBlock)); };   // :87-89
 
-    // r06: the next group's lists are in flight while this one is walked (unconditional loads at clamped indices, two register sets that alternate
-    // by unrolling -- see k_track_greedy); before, every group of 16 queries started with a full trip to memory
-    struct LGrp { unsigned ent[kPrefetch]; int myCnt; unsigned myBits; };
-    const int Mc = max(M - 1, 0);
-    auto load_group = [&](int g0, LGrp& g) {
-        const int gi = min(g0 + (lane & (kPrefetch - 1)), Mc);
-        g.myCnt = C[gi]; g.myBits = Q[gi].bits;
-#pragma unroll
-        for (int k = 0; k < kPrefetch; k++) g.ent[k] = Lp[(size_t)min(g0 + k, Mc) * kListCap + lane];
-    };
-    auto process = [&](const int g0, const LGrp& grp) {
-        const int myCnt = (g0 + (lane & (kPrefetch - 1))) < M ? grp.myCnt : 0;
-        const unsigned myBits = grp.myBits;
-        const unsigned (&ent)[kPrefetch] = grp.ent;
-#pragma unroll
-        for (int k = 0; k < kPrefetch; k++) {
-            const int m = g0 + k;
-            const int cnt = __builtin_amdgcn_readlane(myCnt, k);
-            if (m >= M || cnt == 0) continue;                                         // vIndices.empty() (:71)
-            const unsigned bits = (unsigned)__builtin_amdgcn_readlane((int)myBits, k);
-            unsigned kb = 0xffffffffu, eb = 0, ks = 0xffffffffu, es = 0;               // best / second: key = dist << 12 | ordinal, entry
-            if (cnt <= kListCap) {
-                const unsigned e = ent[k];
-                const bool ok = lane < cnt && !blocked((int)(e & 0xfff));
-                const unsigned key = ok ? ((e >> 16) << 12) | (unsigned)lane : 0xffffffffu;
-                kb = wave_min_u32(key);
-                if (kb != 0xffffffffu) {
-                    const int bl = (int)(kb & 63);
-                    eb = (unsigned)__builtin_amdgcn_readlane((int)e, bl);
-                    ks = wave_min_u32(lane == bl ? 0xffffffffu : key);
-                    if (ks != 0xffffffffu) es = (unsigned)__builtin_amdgcn_readlane((int)e, (int)(ks & 63));
-                }
-            } else {
-                // the window overflowed its list: walk it again against the live occupancy state, 64 candidates at a time
-                const Query q = Q[m];
-                const float r = Rd[m];
-                const int lv = bits & 0xff;
-                const uint4* qd = (const uint4*)points[m0 + m].desc;
-                const uint4 qa = qd[0], qb = qd[1];
-                const float* urC = rec_uright(recC, P.nf);
-                const ivf_keypoint* kc = rec_kps(recC);
-                unsigned ordinal = 0;
-                grid_walk(geom_of(P), kc, rec_desc(recC, P.nf), gStart + (size_t)f * (kGC * kGR + 1), gIdx + (size_t)f * P.nf, q.u, q.v, r,
-                          lv - 1, lv, qa, qb, lane, [&](bool ok, int i2, int d) {
-                              if (ok) { const float u2 = urC[i2]; if (u2 > 0) { const float er = fabsf(q.ur - u2); if (er > r) ok = false; } }
-                              const unsigned long long mk = __ballot(ok);
-                              const unsigned pos = ordinal + (unsigned)__popcll(mk & ((1ull << lane) - 1ull));
-                              ordinal += (unsigned)__popcll(mk);
-                              if (ok && blocked(i2)) ok = false;
-                              const unsigned e = ok ? ((unsigned)i2 | ((unsigned)kc[i2].octave << 12) | ((unsigned)d << 16)) : 0u;
-                              const unsigned key = ok ? ((unsigned)d << 12) | pos : 0xffffffffu;
-                              const unsigned k1 = wave_min_u32(key);
-                              if (k1 == 0xffffffffu) return;
-                              const unsigned long long w1 = __ballot(key == k1);
-                              const int l1 = __ffsll((long long)w1) - 1;
-                              const unsigned e1 = (unsigned)__builtin_amdgcn_readlane((int)e, l1);
-                              const unsigned k2 = wave_min_u32(lane == l1 ? 0xffffffffu : key);
-                              unsigned e2 = 0;
-                              if (k2 != 0xffffffffu) {
-                                  const unsigned long long w2 = __ballot(key == k2 && lane != l1);
-                                  e2 = (unsigned)__builtin_amdgcn_readlane((int)e, __ffsll((long long)w2) - 1);
-                              }
-                              merge_top2(kb, eb, ks, es, k1, e1, k2, e2);
-                          });
+    walk_lists_prefetched(M, C, Lp, lane, [&](int m) { return Q[m].bits; }, [&](int m, int cnt, unsigned e, auto aux) {
+        const unsigned bits = aux();
+        unsigned kb = 0xffffffffu, eb = 0, ks = 0xffffffffu, es = 0;               // best / second: key = dist << 12 | ordinal, entry
+        if (cnt <= kListCap) {
+            const bool ok = lane < cnt && !blocked((int)(e & 0xfff));
+            const unsigned key = ok ? ((e >> 16) << 12) | (unsigned)lane : 0xffffffffu;
+            kb = wave_min_u32(key);
+            if (kb != 0xffffffffu) {
+                const int bl = (int)(kb & 63);
+                eb = (unsigned)__builtin_amdgcn_readlane((int)e, bl);
+                ks = wave_min_u32(lane == bl ? 0xffffffffu : key);
+                if (ks != 0xffffffffu) es = (unsigned)__builtin_amdgcn_readlane((int)e, (int)(ks & 63));
             }
-            if (kb == 0xffffffffu) continue;
-            const int bestDist = (int)(kb >> 12), bestIdx = (int)(eb & 0xfff), bestLevel = (int)((eb >> 12) & 15);
-            if (bestDist > 100) continue;                                               // TH_HIGH (:118)
-            if (ks != 0xffffffffu) {
-                const int bestDist2 = (int)(ks >> 12), bestLevel2 = (int)((es >> 12) & 15);
-                // a candidate AT 256 never becomes second best: bestDist2 starts at 256 and `dist < bestDist2` is strict (:78, :110), so
-                // bestLevel2 stays -1 and no ratio test is made
-                if (bestDist2 < 256 && bestLevel == bestLevel2 && (float)bestDist > nnRatio * (float)bestDist2) continue;   // :120-121
-            }
-            if (lane == 0) s_assign[bestIdx] = ((bits >> 25) & 1) ? m : (m | kLocalNoBlock);          // :123
-            nm++;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        } else {
+            // the window overflowed its list: walk it again against the live occupancy state, 64 candidates at a time
+            const Query q = Q[m];
+            const float r = Rd[m];
+            const int lv = bits & 0xff;
+            const uint4* qd = (const uint4*)points[m0 + m].desc;
+            const uint4 qa = qd[0], qb = qd[1];
+            const float* urC = rec_uright(recC, P.nf);
+            const ivf_keypoint* kc = rec_kps(recC);
+            int ordinal = 0;
+            grid_walk(geom_of(P), kc, rec_desc(recC, P.nf), gStart + (size_t)f * (kGC * kGR + 1), gIdx + (size_t)f * P.nf, q.u, q.v, r,
+                      lv - 1, lv, qa, qb, lane, [&](bool ok, int i2, int d) {
+                          if (ok) ok = ur_admits(urC[i2], q.ur, r);
+                          const unsigned pos = (unsigned)list_ordinal(ok, lane, ordinal);
+                          if (ok && blocked(i2)) ok = false;
+                          const unsigned ew = ok ? ((unsigned)i2 | ((unsigned)kc[i2].octave << 12) | ((unsigned)d << 16)) : 0u;
+                          const unsigned key = ok ? ((unsigned)d << 12) | pos : 0xffffffffu;
+                          const unsigned k1 = wave_min_u32(key);
+                          if (k1 == 0xffffffffu) return;
+                          const unsigned long long w1 = __ballot(key == k1);
+                          const int l1 = __ffsll((long long)w1) - 1;
+                          const unsigned e1 = (unsigned)__builtin_amdgcn_readlane((int)ew, l1);
+                          const unsigned k2 = wave_min_u32(lane == l1 ? 0xffffffffu : key);
+                          unsigned e2 = 0;
+                          if (k2 != 0xffffffffu) {
+                              const unsigned long long w2 = __ballot(key == k2 && lane != l1);
+                              e2 = (unsigned)__builtin_amdgcn_readlane((int)ew, __ffsll((long long)w2) - 1);
+                          }
+                          merge_top2(kb, eb, ks, es, k1, e1, k2, e2);
+                      });
         }
-    };
-    if (M > 0) {
-        LGrp gA, gB;
-        load_group(0, gA);
-        for (int g0 = 0; g0 < M; g0 += 2 * kPrefetch) {
-            load_group(g0 + kPrefetch, gB); process(g0, gA);
-            if (g0 + kPrefetch < M) { load_group(g0 + 2 * kPrefetch, gA); process(g0 + kPrefetch, gB); }
+        if (kb == 0xffffffffu) return;
+        const int bestDist = (int)(kb >> 12), bestIdx = (int)(eb & 0xfff), bestLevel = (int)((eb >> 12) & 15);
+        if (bestDist > 100) return;                                                 // TH_HIGH (:118)
+        if (ks != 0xffffffffu) {
+            const int bestDist2 = (int)(ks >> 12), bestLevel2 = (int)((es >> 12) & 15);
+            // a candidate AT 256 never becomes second best: bestDist2 starts at 256 and `dist < bestDist2` is strict (:78, :110), so
+            // bestLevel2 stays -1 and no ratio test is made
+            if (bestDist2 < 256 && bestLevel == bestLevel2 && (float)bestDist > nnRatio * (float)bestDist2) return;   // :120-121
         }
-    }
+        if (lane == 0) s_assign[bestIdx] = ((bits >> 25) & 1) ? m : (m | kLocalNoBlock);          // :123
+        nm++;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    });
     __builtin_amdgcn_wave_barrier();
     int* out = assignOut + (size_t)f * P.nf;
     for (int i = lane; i < P.nf; i += 64) { const int a = i < nC ? s_assign[i] : -1; out[i] = a < 0 ? -1 : (a & ~kLocalNoBlock); }
@@ -267,26 +227,25 @@ extern "C" int ivf_tracker_search_local(ivf_tracker* t, const uint8_t* d_records
                                         int max_points_per_frame, const uint8_t* d_occupied, float th, float nn_ratio, float cos_limit,
                                         float* d_point_quality, float* d_key_quality, int32_t* d_assign, int32_t* d_nmatches, void* hip_stream)
 {
-    if (!t || !d_records || !d_frames || !d_points || !d_point_offsets || !d_assign || !d_nmatches) return fail(IVF_E_INVALID, "null argument");
-    if (((size_t)d_records & 15) != 0 || ((size_t)d_points & 15) != 0) return fail(IVF_E_INVALID, "the record block and the point array must be 16-byte aligned");
-    if (n_frames == 0) return IVF_OK;
+    if (!d_point_offsets) return fail(IVF_E_INVALID, "null argument");
+    const int ra = search_args_ok(t, d_records, d_frames, true, d_points, d_assign, d_nmatches, n_frames, d_point_quality, d_key_quality);
+    if (ra != IVF_OK || n_frames == 0) return ra;
     if (max_points_per_frame < 1 || max_points_per_frame >= kLocalNoBlock) return fail(IVF_E_INVALID, "max_points_per_frame %d out of range", max_points_per_frame);
     if (!(th > 0) || !(nn_ratio > 0)) return fail(IVF_E_INVALID, "th and nn_ratio must be positive");
-    if ((d_point_quality == nullptr) != (d_key_quality == nullptr)) return fail(IVF_E_INVALID, "d_point_quality and d_key_quality come together");
     hipStream_t st = (hipStream_t)hip_stream;
     const int rc = tracker_begin(t, true, record_bytes, n_records, n_frames, st);
     if (rc != IVF_OK) return rc;
-    const int rg = tracker_grow_local(t, max_points_per_frame);
+    const int rg = tracker_grow_queries(t, max_points_per_frame);
     if (rg != IVF_OK) return rg;
     TrackParams P = t->P;
     P.nRecords = n_records;
     const int M = max_points_per_frame;
     hipLaunchKernelGGL(k_local_prepare, dim3(n_frames), dim3(256), 0, st, P, d_records, d_frames, d_poses, d_points, d_point_offsets, th, cos_limit, M,
-                       t->dStart, t->dIdx, t->dLQ, t->dLRad);
+                       t->dStart, t->dIdx, t->dQ, t->dLRad);
     hipLaunchKernelGGL(k_local_window, dim3((M + 3) / 4, n_frames), dim3(256), 0, st, P, d_records, d_frames, d_points, d_point_offsets, M,
-                       t->dStart, t->dIdx, t->dLQ, t->dLRad, t->dLCount, t->dLLists);
+                       t->dStart, t->dIdx, t->dQ, t->dLRad, t->dCount, t->dLists);
     hipLaunchKernelGGL(k_local_greedy, dim3(n_frames), dim3(64), (size_t)P.nf * 4, st, P, d_records, d_frames, d_points, d_point_offsets, M,
-                       t->dStart, t->dIdx, t->dLQ, t->dLRad, d_occupied, nn_ratio, t->dLCount, t->dLLists, d_point_quality, d_key_quality,
+                       t->dStart, t->dIdx, t->dQ, t->dLRad, d_occupied, nn_ratio, t->dCount, t->dLists, d_point_quality, d_key_quality,
                        d_assign, d_nmatches);
     return tracker_end(t, st);
 }

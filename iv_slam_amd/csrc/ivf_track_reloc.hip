@@ -16,7 +16,9 @@
 //   k_reloc_greedy   one wave per pair: walks the keyframe keypoints in order against the occupancy state in LDS; the first minimum is a
 //                    DPP minimum reduction of (distance << 6 | list position)
 //   k_filter_assign  one workgroup per frame
-#include "ivf_tracker.h"
+// Pair liveness, the map-point gates, the ordered list, the first minimum (of a list and of an overflowed window) and the prefetched walk
+// over the lists are ivf_search.h's; the candidate scratch is the handle's one set (ivf_track.hip: tracker_grow_queries).
+#include "ivf_search.h"
 
 using namespace ivf;
 
@@ -25,12 +27,6 @@ namespace {
 static_assert(sizeof(ivf_local_point) == 80, "ivf_local_point is read as five 16-byte pieces");
 constexpr int kRelocEntry = 1 << 24;              // s_assign: the keypoint held this point before the call (occupied, never changed)
 constexpr int kRelocIdMask = 0xffff;              // s_assign: keyframe keypoint | rotation bin << 16 | kRelocEntry
-
-// a pair takes part when the mask selects it and both record indices lie inside the block
-__device__ __forceinline__ bool reloc_live(int nRecords, const int2 pr, const int* __restrict__ select, int p)
-{
-    return (!select || select[p] != 0) && rec_ok(nRecords, pr.x) && rec_ok(nRecords, pr.y);
-}
 
 // one workgroup per pair: grid of the current record, sAlreadyFound, then ORBmatcher.cc:1537-1575 of every keyframe keypoint
 __global__ __launch_bounds__(256) void k_reloc_prepare(TrackParams P, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
@@ -45,7 +41,7 @@ __global__ __launch_bounds__(256) void k_reloc_prepare(TrackParams P, const uint
     __shared__ uint8_t s_found[kMaxTrackFeatures];
     const int p = blockIdx.x, tid = threadIdx.x;
     const int2 pr = pairs[p];
-    if (!reloc_live(P.nRecords, pr, select, p)) return;
+    if (!pair_live(P.nRecords, pr, select, p)) return;
     const uint8_t* recK = records + (size_t)pr.x * P.recBytes;
     const uint8_t* recC = records + (size_t)pr.y * P.recBytes;
     const int nK = rec_count(recK, P.nf), nC = rec_count(recC, P.nf);
@@ -76,17 +72,11 @@ __global__ __launch_bounds__(256) void k_reloc_prepare(TrackParams P, const uint
             mul_add(R, mp.pos, t, xc);                                                // :1547
             const float invzc = (float)(1.0 / (double)xc[2]);                         // :1551; no test on its sign
             const float u = P.fx * xc[0] * invzc + P.cx, v = P.fy * xc[1] * invzc + P.cy;
-            if (!(u < P.minX || u > P.maxX) && !(v < P.minY || v > P.maxY)) {         // :1556-1559
-                const float PO[3] = {mp.pos[0] - Ow[0], mp.pos[1] - Ow[1], mp.pos[2] - Ow[2]};
-                const double n2 = (double)PO[0] * (double)PO[0] + (double)PO[1] * (double)PO[1] + (double)PO[2] * (double)PO[2];
-                const float dist3D = (float)sqrt(n2);                                 // cv::norm (:1563)
-                const float minD = 0.8f * mp.min_distance, maxD = 1.2f * mp.max_distance;     // MapPoint.cc:378-388
-                if (!(dist3D < minD || dist3D > maxD)) {                              // :1569
-                    const int lv = predict_scale(P, mp.max_distance, dist3D);         // :1572
-                    radius = th * P.scale[lv];                                        // :1575
-                    q.u = u; q.v = v;
-                    q.bits = (unsigned)lv | (1u << 24);
-                }
+            float dist3D; int lv;
+            if (in_image(P, u, v) && point_range_level(P, mp, Ow, dist3D, lv)) {      // :1556-1559, :1563-1572
+                radius = th * P.scale[lv];                                            // :1575
+                q.u = u; q.v = v;
+                q.bits = (unsigned)lv | (1u << 24);
             }
         }
         Q[i] = q; Rd[i] = radius;
@@ -104,7 +94,7 @@ __global__ __launch_bounds__(256) void k_reloc_window(TrackParams P, const uint8
     const int p = blockIdx.y;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int2 pr = pairs[p];
-    if (!reloc_live(P.nRecords, pr, select, p)) return;
+    if (!pair_live(P.nRecords, pr, select, p)) return;
     const uint8_t* recK = records + (size_t)pr.x * P.recBytes;
     const uint8_t* recC = records + (size_t)pr.y * P.recBytes;
     if (i >= rec_count(recK, P.nf)) return;
@@ -117,14 +107,7 @@ __global__ __launch_bounds__(256) void k_reloc_window(TrackParams P, const uint8
         const uint4 qa = qd[0], qb = qd[1];
         unsigned* L = lists + ((size_t)p * P.nf + i) * kListCap;
         grid_walk(geom_of(P), rec_kps(recC), rec_desc(recC, P.nf), gStart + (size_t)p * (kGC * kGR + 1), gIdx + (size_t)p * P.nf,
-                  q.u, q.v, r, lv - 1, lv + 1, qa, qb, lane, [&](bool ok, int i2, int d) {
-                      const unsigned long long mk = __ballot(ok);
-                      if (ok) {
-                          const int pos = total + __popcll(mk & ((1ull << lane) - 1ull));
-                          if (pos < kListCap) L[pos] = (unsigned)i2 | ((unsigned)d << 16);
-                      }
-                      total += __popcll(mk);
-                  });
+                  q.u, q.v, r, lv - 1, lv + 1, qa, qb, lane, [&](bool ok, int i2, int d) { list_append(ok, lane, total, L, (unsigned)i2 | ((unsigned)d << 16)); });
     }
     if (lane == 0) count[(size_t)p * P.nf + i] = total;
 }
@@ -144,7 +127,7 @@ __global__ __launch_bounds__(64) void k_reloc_greedy(TrackParams P, const uint8_
     __shared__ int s_hist[32];                                // rotHist[b].size()
     const int p = blockIdx.x, lane = threadIdx.x;
     const int2 pr = pairs[p];
-    if (!reloc_live(P.nRecords, pr, select, p)) {
+    if (!pair_live(P.nRecords, pr, select, p)) {
         if (lane == 0) nmatchesOut[p] = (select && select[p] == 0) ? -2 : -1;
         return;
     }
@@ -165,69 +148,26 @@ __global__ __launch_bounds__(64) void k_reloc_greedy(TrackParams P, const uint8_
     const unsigned* Lp = lists + (size_t)p * P.nf * kListCap;
     int nm = 0;
 
-    // the next group's lists are in flight while this one is walked (unconditional loads at clamped indices, two register sets that
-    // alternate by unrolling -- see k_local_greedy)
-    struct RGrp { unsigned ent[kPrefetch]; int myCnt; float myAng; };
-    const int Kc = max(nK - 1, 0);
-    auto load_group = [&](int g0, RGrp& g) {
-        const int gi = min(g0 + (lane & (kPrefetch - 1)), Kc);
-        g.myCnt = C[gi]; g.myAng = kK[gi].angle;
-#pragma unroll
-        for (int k = 0; k < kPrefetch; k++) g.ent[k] = Lp[(size_t)min(g0 + k, Kc) * kListCap + lane];
-    };
-    auto process = [&](const int g0, const RGrp& grp) {
-        const int myCnt = (g0 + (lane & (kPrefetch - 1))) < nK ? grp.myCnt : 0;
-        const unsigned (&ent)[kPrefetch] = grp.ent;
-#pragma unroll
-        for (int k = 0; k < kPrefetch; k++) {
-            const int i = g0 + k;
-            const int cnt = __builtin_amdgcn_readlane(myCnt, k);
-            if (i >= nK || cnt == 0) continue;                                          // vIndices2.empty() (:1579); an invalid query lists nothing
-            int bestDist = 256, bestIdx2 = -1;
-            if (cnt <= kListCap) {
-                const unsigned e = ent[k];
-                const int i2 = (int)(e & 0xffff);
-                const bool ok = lane < cnt && s_assign[i2] == -1;
-                const unsigned key = ok ? ((e >> 16) << 6) | (unsigned)lane : 0xffffffffu;
-                const unsigned best = wave_min_u32(key);
-                if (best != 0xffffffffu) { bestDist = (int)(best >> 6); bestIdx2 = __builtin_amdgcn_readlane(i2, (int)(best & 63)); }
-            } else {
-                // the window overflowed its list: walk it again against the live occupancy state, 64 candidates at a time
-                const Query q = Q[i];
-                const int lv = q.bits & 0xff;
-                const uint4* qd = (const uint4*)kfPoints[(size_t)pr.x * P.nf + i].desc;
-                const uint4 qa = qd[0], qb = qd[1];
-                grid_walk(geom_of(P), kc, rec_desc(recC, P.nf), gStart + (size_t)p * (kGC * kGR + 1), gIdx + (size_t)p * P.nf, q.u, q.v, Rd[i],
-                          lv - 1, lv + 1, qa, qb, lane, [&](bool ok, int i2, int d) {
-                              if (ok && s_assign[i2] != -1) ok = false;
-                              const unsigned key = ok ? ((unsigned)d << 6) | (unsigned)lane : 0xffffffffu;
-                              const unsigned best = wave_min_u32(key);
-                              // a later step replaces the best only with a smaller distance: the first minimum in window order
-                              if (best != 0xffffffffu && (int)(best >> 6) < bestDist) {
-                                  bestDist = (int)(best >> 6);
-                                  bestIdx2 = __builtin_amdgcn_readlane(i2, (int)(best & 63));
-                              }
-                          });
-            }
-            if (bestIdx2 < 0 || bestDist > orbDist) continue;                           // :1604
-            int bin = 0;
-            if (checkOri) {
-                const float angK = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, grp.myAng), k));
-                bin = rot_bin(angK - kc[bestIdx2].angle);                               // :1611-1616
-            }
-            if (lane == 0) { s_assign[bestIdx2] = i | (bin << 16); if (checkOri) s_hist[bin]++; }      // :1606, :1618
-            nm++;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    auto free = [&](int i2) { return s_assign[i2] == -1; };                             // :1590
+    // vIndices2.empty() (:1579) is the walk's cnt == 0
+    walk_lists_prefetched(nK, C, Lp, lane, [&](int i) { return kK[i].angle; }, [&](int i, int cnt, unsigned e, auto angK) {
+        int bestDist = 256, bestIdx2 = -1;
+        if (cnt <= kListCap) {
+            first_min_in_list(lane < cnt, (int)(e >> 16), (int)(e & 0xffff), lane, free, bestDist, bestIdx2);
+        } else {
+            // the window overflowed its list: walk it again against the live occupancy state, 64 candidates at a time
+            const Query q = Q[i];
+            const int lv = q.bits & 0xff;
+            const uint4* qd = (const uint4*)kfPoints[(size_t)pr.x * P.nf + i].desc;
+            first_min_in_window(geom_of(P), kc, rec_desc(recC, P.nf), gStart + (size_t)p * (kGC * kGR + 1), gIdx + (size_t)p * P.nf, q.u, q.v, Rd[i],
+                                lv - 1, lv + 1, qd[0], qd[1], lane, free, bestDist, bestIdx2);
         }
-    };
-    if (nK > 0) {
-        RGrp gA, gB;
-        load_group(0, gA);
-        for (int g0 = 0; g0 < nK; g0 += 2 * kPrefetch) {
-            load_group(g0 + kPrefetch, gB); process(g0, gA);
-            if (g0 + kPrefetch < nK) { load_group(g0 + 2 * kPrefetch, gA); process(g0 + kPrefetch, gB); }
-        }
-    }
+        if (bestIdx2 < 0 || bestDist > orbDist) return;                                 // :1604
+        const int bin = checkOri ? rot_bin(angK() - kc[bestIdx2].angle) : 0;              // :1611-1616
+        if (lane == 0) { s_assign[bestIdx2] = i | (bin << 16); if (checkOri) s_hist[bin]++; }      // :1606, :1618
+        nm++;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    });
     wave_sync_lds();
     // ComputeThreeMaxima (:1654-1695): the matches of every other bin are taken back; their keypoints were occupied while the walk ran
     if (checkOri) {
@@ -279,26 +219,25 @@ int ivf_tracker_search_reloc(ivf_tracker* t, const uint8_t* d_records, size_t re
                              int orb_dist, int check_orientation, float* d_point_quality, float* d_key_quality, int32_t* d_assign,
                              int32_t* d_nmatches, void* hip_stream)
 {
-    if (!t || !d_records || !d_pairs || !d_kf_points || !d_assign || !d_nmatches) return fail(IVF_E_INVALID, "null argument");
-    if (((size_t)d_records & 15) != 0 || ((size_t)d_kf_points & 15) != 0) return fail(IVF_E_INVALID, "the record block and the point array must be 16-byte aligned");
+    const int ra = search_args_ok(t, d_records, d_pairs, true, d_kf_points, d_assign, d_nmatches, n_pairs, d_point_quality, d_key_quality);
+    if (ra != IVF_OK) return ra;
     if (!(th > 0)) return fail(IVF_E_INVALID, "th must be positive");
     if (orb_dist < 0 || orb_dist > 255) return fail(IVF_E_INVALID, "orb_dist %d outside [0,255]", orb_dist);
-    if ((d_point_quality == nullptr) != (d_key_quality == nullptr)) return fail(IVF_E_INVALID, "d_point_quality and d_key_quality come together");
     hipStream_t st = (hipStream_t)hip_stream;
     const int rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st);
     if (rc != IVF_OK) return rc;
     if (n_pairs == 0) return IVF_OK;
-    const int rg = tracker_grow_local(t, t->P.nf);
+    const int rg = tracker_grow_queries(t, t->P.nf);
     if (rg != IVF_OK) return rg;
     TrackParams P = t->P;
     P.nRecords = n_records;
     const int2* pairs = (const int2*)d_pairs;
     hipLaunchKernelGGL(k_reloc_prepare, dim3(n_pairs), dim3(256), 0, st, P, d_records, pairs, d_select, d_poses, d_kf_points, d_found, d_assign, th,
-                       t->dStart, t->dIdx, t->dLQ, t->dLRad);
+                       t->dStart, t->dIdx, t->dQ, t->dLRad);
     hipLaunchKernelGGL(k_reloc_window, dim3((P.nf + 3) / 4, n_pairs), dim3(256), 0, st, P, d_records, pairs, d_select, d_kf_points, t->dStart, t->dIdx,
-                       t->dLQ, t->dLRad, t->dLCount, t->dLLists);
+                       t->dQ, t->dLRad, t->dCount, t->dLists);
     hipLaunchKernelGGL(k_reloc_greedy, dim3(n_pairs), dim3(64), (size_t)P.nf * sizeof(int), st, P, d_records, pairs, d_select, d_kf_points, t->dStart,
-                       t->dIdx, t->dLQ, t->dLRad, orb_dist, check_orientation ? 1 : 0, t->dLCount, t->dLLists, d_point_quality, d_key_quality,
+                       t->dIdx, t->dQ, t->dLRad, orb_dist, check_orientation ? 1 : 0, t->dCount, t->dLists, d_point_quality, d_key_quality,
                        d_assign, d_nmatches);
     return tracker_end(t, st);
 }

@@ -3,8 +3,9 @@
 // ivf_track_bow.hip (TrackReferenceKeyFrame), ivf_track_reloc.hip (Relocalization's SearchByProjection and the set bookkeeping around
 // it), ivf_track_points.hip (the points a search hands to a solver), ivf_pose.hip
 // (PoseOptimization) and ivf_pnp.hip (Relocalization's PnPsolver).  One definition of struct ivf_tracker, one host statement of the
-// camera and record constants (TrackParams), and one device text of every piece the searches repeat; what only the two solvers
-// repeat is ivf_solve.h's.
+// camera and record constants (TrackParams), and the device pieces searches and solvers both read (the query record, the pose algebra,
+// PredictScale, UpdateQualityScores); what only the projection searches repeat is ivf_search.h's, what only the two solvers repeat
+// ivf_solve.h's.
 #pragma once
 #include "ivf_bow.h"
 #include <vector>
@@ -67,7 +68,7 @@ __device__ __forceinline__ float glibc_logf(float x)
     return (float)y;
 }
 // MapPoint::PredictScale (MapPoint.cc:407-422) as compiled: logf, a float quotient, std::ceil(float), the clamp to [0, nlevels - 1].
-// The one statement of it: k_local_prepare (SearchLocalPoints) and k_reloc_prepare (Relocalization's SearchByProjection).
+// The one statement of it, behind point_range_level (ivf_search.h): SearchLocalPoints and Relocalization's SearchByProjection.
 __device__ __forceinline__ int predict_scale(const TrackParams& P, float maxDistance, float dist)
 {
     const float ratio = maxDistance / dist;
@@ -123,31 +124,17 @@ __device__ __forceinline__ void update_quality_scores(const int* assign, int n, 
     }
 }
 
-// k_track_greedy's candidate admission against the live state in LDS (ORBmatcher.cc:1447-1457): current keypoint i2 is out when a point
-// with observations holds it, or when it has a right coordinate further than the window radius from the projected one
-constexpr int kNoBlock = 0x10000;                 // flag on an assignment made by a point without observations: it does not block (:1447-1449)
-__device__ __forceinline__ bool track_admits(const int* s_assign, const float* s_ur, int i2, float qur, float radius)
-{
-    bool ok = true;
-    const int a = s_assign[i2];
-    if (a >= 0 && !(a & kNoBlock)) ok = false;
-    const float u2 = s_ur[i2];
-    if (u2 > 0) { const float er = fabsf(qur - u2); if (er > radius) ok = false; }
-    return ok;
-}
-
 }  // namespace ivf
 
 struct ivf_tracker {
     ivf_track_config cfg;
     ivf::TrackParams P;                   // nRecords is the one per-call field: every entry point sets it in its own copy
-    int *dStart = nullptr, *dCount = nullptr, *dRetry = nullptr;
+    int *dStart = nullptr, *dRetry = nullptr;
     unsigned short* dIdx = nullptr;
-    ivf::Query* dQ = nullptr;
-    unsigned* dLists = nullptr;
-    // scratch of ivf_tracker_search_local and ivf_tracker_search_reloc (nfeatures queries per pair), sized at the first call / grown on
-    // demand (tracker_grow_local): [max_pairs][localCap] queries, radii, counts, lists
-    ivf::Query* dLQ = nullptr; float* dLRad = nullptr; int* dLCount = nullptr; unsigned* dLLists = nullptr; int localCap = 0;
+    // the candidate scratch of the three projection searches, [max_pairs][queryCap] queries, radii (search_local, search_reloc),
+    // counts, lists: queryCap starts at nfeatures (run and search_reloc index it with that stride) and grows on demand
+    // (tracker_grow_queries) to search_local's max_points_per_frame, its stride
+    ivf::Query* dQ = nullptr; float* dLRad = nullptr; int* dCount = nullptr; unsigned* dLists = nullptr; int queryCap = 0;
     ivf::TrackerBowScratch bow{nullptr, nullptr, nullptr, nullptr, nullptr};   // ivf_tracker_search_by_bow: [2 * max_pairs] slots
     ivf::PnpScratch pnp{nullptr, nullptr, nullptr, nullptr};
     size_t ldsBytes = 0;
@@ -174,8 +161,12 @@ struct ivf_tracker {
 namespace ivf {
 // tracker_begin: the argument checks every tracker entry point shares, hipSetDevice and the wait for the handle's previous call;
 // tracker_end: the event the next call waits for;
-// tracker_grow_local: the local-search scratch (dLQ, dLRad, dLCount, dLLists) for at least `cap` queries per frame / pair
+// search_args_ok: what the three projection searches check alike -- the pointers (points: the array of search_local / search_reloc),
+// the 16-byte alignment of what the kernels read as uint4 and, in a call of n_items != 0, that the quality arrays come together;
+// tracker_grow_queries: the candidate scratch (dQ, dLRad, dCount, dLists) for at least `cap` queries per frame / pair
 int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n_records, int n_items, hipStream_t st);
 int tracker_end(ivf_tracker* t, hipStream_t st);
-int tracker_grow_local(ivf_tracker* t, int cap);
+int search_args_ok(const ivf_tracker* t, const void* records, const void* items, bool has_points, const void* points, const void* assign,
+                   const void* nmatches, int n_items, const float* point_quality, const float* key_quality);
+int tracker_grow_queries(ivf_tracker* t, int cap);
 }  // namespace ivf
