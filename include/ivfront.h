@@ -701,6 +701,65 @@ int  ivf_tracker_solve_pnp(ivf_tracker* t, const uint8_t* d_records, size_t reco
                            const float* d_xw, const uint8_t* d_has_point, const uint32_t* d_draws, int max_iterations, double probability,
                            int min_inliers, float epsilon, float th2, float* d_poses, uint8_t* d_inlier, int32_t* d_ninliers,
                            int32_t* d_iterations, float* d_hyp_poses, int32_t* d_hyp_ninliers, void* hip_stream);
+/* The first two lines of Tracking::Relocalization (ORB/src/Tracking.cc:2274-2285), on the device: with them the chain runs from a lost
+ * frame's gather record to its restart pose without the host reading anything.
+ *
+ * ivf_tracker_bow_vectors: Frame::ComputeBoW's mBowVec (ORB/src/Frame.cc:683-694) for frame slot f = record d_frames[f], i.e.
+ * TemplatedVocabulary::transform (TemplatedVocabulary.h:1126-1204) with the ORB vocabulary's TF_IDF weights and L1_NORM.  Every keypoint
+ * below the record's count descends the tree (:1217-1259, the descent ivf_bow_transform and ivf_tracker_search_by_bow run); a leaf of
+ * weight <= 0 contributes nothing (:1157); a word that k keypoints reach holds the result of k successive `+= weight` from 0.0
+ * (BowVector.cpp:34-46: the map's operator[] then addWeight), added in keypoint order; the L1 norm is the sum of fabs(value) in ascending
+ * word order and every value is divided by it when it is > 0.0 (BowVector.cpp:62-84).  All of it in f64, nothing fused or
+ * reassociated: word ids and value bits equal ivf_bow_transform + ivf_bow_vectors on the same descriptors.
+ * d_bow_word / d_bow_value [n_frames][nfeatures]: the words ascending and their values, -1 / 0.0 beyond the count; d_bow_n [n_frames]:
+ * the number of words, -1 for a record index outside [0, n_records): nothing else of that slot is written.  n_frames is not bound by
+ * max_pairs (the call needs no scratch of the handle).  IVF_E_INVALID: a null required pointer, n_frames < 0, a vocabulary on another
+ * device than the tracker.  Every loop is bounded by nfeatures or by the depth of the tree.  Asynchronous on hip_stream; obeys the
+ * handle's one-call-at-a-time rule. */
+int  ivf_tracker_bow_vectors(ivf_tracker* t, const ivf_vocabulary* voc, const uint8_t* d_records, size_t record_bytes, int n_records,
+                             const int32_t* d_frames, int n_frames, int32_t* d_bow_word, double* d_bow_value, int32_t* d_bow_n,
+                             void* hip_stream);
+/* ivf_tracker_reloc_candidates: KeyFrameDatabase::DetectRelocalizationCandidates (ORB/src/KeyFrameDatabase.cc:199-309) with
+ * mpVoc->score = L1Scoring::score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68), for n_frames lost frames against one database of
+ * n_keyframes keyframes.  The database is flat device arrays the caller keeps between calls, keyframe index = order of
+ * KeyFrameDatabase::add: d_kf_bow_word / d_kf_bow_value [n_keyframes][nfeatures] and d_kf_bow_n [n_keyframes] as
+ * ivf_tracker_bow_vectors wrote them when the keyframe was inserted; d_kf_live [n_keyframes] (nullable), 0 = erased: in no inverted
+ * list, so it shares no word, is never scored and is skipped as a neighbour; d_kf_neigh [n_keyframes][10] =
+ * GetBestCovisibilityKeyFrames(10) as keyframe indices in order, -1 after the last; d_kf_reloc_score [n_keyframes] (nullable, NULL =
+ * 0.0f), read-only: the mRelocScore each keyframe holds BEFORE this call, the same for every frame of the batch -- the reference reads it
+ * (:276-277) for a neighbour that shares a word with the frame but was not scored, and that is all such a neighbour contributes;
+ * d_kf_record [n_keyframes]: the gather record of each keyframe in the block the later searches read, -1 = none.  The frames:
+ * d_bow_word / d_bow_value / d_bow_n as ivf_tracker_bow_vectors wrote them and d_frame_record [n_frames].  Per frame:
+ *   mnRelocWords of keyframe k = the number of words both vectors hold (:207-222), 0 = the keyframe is absent;
+ *   minCommonWords = (int)(maxCommonWords * 0.8f), the product in float (:235); keyframes with mnRelocWords > minCommonWords are scored
+ *   (:246): the f64 sum of fabs(vi - wi) - fabs(vi) - fabs(wi), vi the frame's value, over the common words in ascending word order
+ *   (ScoringObject.cpp:34-59), then -score / 2.0 narrowed to float (:249);
+ *   per scored keyframe accScore = its score, then for its neighbours in order -- skipping -1 (or any index outside the database),
+ *   erased keyframes and those that share no word (:273) -- accScore += s in float, s = the neighbour's score of this query if it was
+ *   scored, else its d_kf_reloc_score; pBestKF moves to the neighbour on s > bestScore, strictly (:276-281);
+ *   bestAccScore starts at 0 (:259, :285); entries with accScore > 0.75f * bestAccScore, strictly, are retained (:290-297);
+ *   the distinct pBestKF of the retained entries come out in the order of lScoreAndMatch (:294-305), which is the order of first
+ *   encounter walking the frame's words ascending and each word's inverted list in insertion order (:207-221), i.e. scored keyframes
+ *   ordered by (smallest shared word, keyframe index), each pBestKF at its first retained occurrence.
+ * Outputs: d_cand [n_frames][max_candidates] keyframe indices, -1 beyond the count; d_ncand [n_frames] the true count, even above
+ * max_candidates (then the first max_candidates are written); d_pairs [n_frames * max_candidates][2] and d_select
+ * [n_frames * max_candidates]: slot f * max_candidates + j = (d_kf_record[candidate j], d_frame_record[f]) and 1 for a written
+ * candidate whose keyframe has a record (>= 0), else (-1, -1) and 0 -- what ivf_tracker_search_by_bow, ivf_tracker_search_reloc and
+ * (through the pairs' frame column) ivf_tracker_solve_pnp take, n_pairs = n_frames * max_candidates <= max_pairs being the caller's to
+ * respect; d_scores [n_frames][n_keyframes] (nullable): the float score of every scored keyframe, the NaN with bits 0x7fc00000
+ * elsewhere -- what the caller folds into its mRelocScore state (:250); d_common [n_frames][n_keyframes] (nullable): mnRelocWords.
+ * n_keyframes == 0 or a frame with d_bow_n <= 0 gives d_ncand = 0.  IVF_E_INVALID: a null required pointer, max_candidates < 1,
+ * n_keyframes < 0, n_frames < 0, a vocabulary on another device than the tracker.  Every loop is bounded by nfeatures, n_keyframes or
+ * 10; garbage input (unsorted words, a count above nfeatures, a neighbour outside the database) may give a meaningless answer but no
+ * read outside the arrays.  Two runs are bit-identical.  Asynchronous on hip_stream, no host synchronisation; the scratch
+ * (40 bytes per frame and keyframe) sits on the handle, grows on demand (the one place where the call waits, for the handle's previous
+ * call, before it frees the smaller buffers) and obeys the one-call-at-a-time rule. */
+int  ivf_tracker_reloc_candidates(ivf_tracker* t, const ivf_vocabulary* voc, const int32_t* d_kf_bow_word, const double* d_kf_bow_value,
+                                  const int32_t* d_kf_bow_n, const uint8_t* d_kf_live, const int32_t* d_kf_neigh,
+                                  const float* d_kf_reloc_score, const int32_t* d_kf_record, int n_keyframes, const int32_t* d_bow_word,
+                                  const double* d_bow_value, const int32_t* d_bow_n, const int32_t* d_frame_record, int n_frames,
+                                  int max_candidates, int32_t* d_cand, int32_t* d_ncand, int32_t* d_pairs, int32_t* d_select,
+                                  float* d_scores, int32_t* d_common, void* hip_stream);
 /* MapPoint::ComputeDistinctiveDescriptors (ORB/src/MapPoint.cc:247-312): desc = the n observed descriptors (rows of
  * vDescriptors, in mObservations order); *best_index = the row to copy into mDescriptor, *best_median (nullable) its median. */
 int  ivf_distinctive_descriptor(const uint8_t* desc, int n, int* best_index, int* best_median, int device_id);

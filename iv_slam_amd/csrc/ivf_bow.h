@@ -1,6 +1,7 @@
 // ivf_bow.h -- what the per-call DBoW2 transform (ivf_match.hip, which alone knows struct ivf_vocabulary) and the batched
-// TrackReferenceKeyFrame matcher (ivf_track_bow.hip) share: the one device text of the vocabulary-tree descent, the view through
-// which ivf_track_bow.hip reaches the vocabulary, and the kernel-argument struct of the tracker handle's feature-vector scratch.
+// TrackReferenceKeyFrame matcher (ivf_track_bow.hip) share, and with them the batched mBowVec of ivf_track_db.hip: the one device text of
+// the vocabulary-tree descent, the view through which the tracker's units reach the vocabulary, and the kernel-argument struct of the
+// tracker handle's feature-vector scratch.
 #pragma once
 #include "ivf_grid.h"
 
@@ -34,12 +35,15 @@ __device__ __forceinline__ void bow_descend(const int* __restrict__ childStart, 
     leaf = node;
 }
 
-// what ivf_track_bow.hip needs of a vocabulary: the tree in HBM and, per node, whether a descriptor that ends there enters the feature
-// vector at all (weight > 0: TemplatedVocabulary.h:1157 skips stopped words)
+// what ivf_track_bow.hip and ivf_track_db.hip need of a vocabulary: the tree in HBM and, per node, whether a descriptor that ends there
+// enters the feature vector at all (weight > 0: TemplatedVocabulary.h:1157 skips stopped words); for mBowVec (ivf_track_db.hip) the word
+// id and the weight of every node as ivf_vocabulary_create received them
 struct VocabularyView {
     int device, nNodes, depth;
     const int *childStart, *child;
     const uint8_t *nodeDesc, *wordLive;
+    const int* nodeWord;
+    const double* nodeWeight;
 };
 int vocabulary_view(const ivf_vocabulary* v, VocabularyView* out);
 

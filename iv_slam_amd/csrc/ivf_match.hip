@@ -1117,6 +1117,7 @@ struct ivf_vocabulary {
     int device = 0, nNodes = 0, depth = 0, maxChildren = 0;
     int *dChildStart = nullptr, *dChild = nullptr; uint8_t* dDesc = nullptr;
     uint8_t* dLive = nullptr;             // [nNodes] weight > 0: what the batched matcher (ivf_track_bow.hip) needs of the weights
+    int* dWord = nullptr; double* dWeight = nullptr;   // [nNodes] word id and weight: the batched mBowVec (ivf_track_db.hip)
     std::vector<int> word; std::vector<double> weight; std::vector<int> childStart;
 };
 
@@ -1155,7 +1156,8 @@ int ivf_vocabulary_create(int n_nodes, const int32_t* child_start, const int32_t
     v->word.assign(node_word, node_word + n_nodes); v->weight.assign(node_weight, node_weight + n_nodes);
     v->childStart.assign(child_start, child_start + n_nodes + 1);
     if (hipMalloc(&v->dChildStart, (size_t)(n_nodes + 1) * sizeof(int)) != hipSuccess || hipMalloc(&v->dChild, (size_t)std::max(nChild, 1) * sizeof(int)) != hipSuccess ||
-        hipMalloc(&v->dDesc, (size_t)n_nodes * 32) != hipSuccess || hipMalloc(&v->dLive, (size_t)n_nodes) != hipSuccess) {
+        hipMalloc(&v->dDesc, (size_t)n_nodes * 32) != hipSuccess || hipMalloc(&v->dLive, (size_t)n_nodes) != hipSuccess ||
+        hipMalloc(&v->dWord, (size_t)n_nodes * sizeof(int)) != hipSuccess || hipMalloc(&v->dWeight, (size_t)n_nodes * sizeof(double)) != hipSuccess) {
         ivf_vocabulary_destroy(v);
         return fail(IVF_E_NO_DEVICE, "hipMalloc failed for the vocabulary");
     }
@@ -1164,7 +1166,9 @@ int ivf_vocabulary_create(int n_nodes, const int32_t* child_start, const int32_t
     if (hipMemcpy(v->dChildStart, child_start, (size_t)(n_nodes + 1) * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(v->dChild, child, (size_t)nChild * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(v->dDesc, node_desc, (size_t)n_nodes * 32, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(v->dLive, live.data(), (size_t)n_nodes, hipMemcpyHostToDevice) != hipSuccess) {
+        hipMemcpy(v->dLive, live.data(), (size_t)n_nodes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v->dWord, node_word, (size_t)n_nodes * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v->dWeight, node_weight, (size_t)n_nodes * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
         ivf_vocabulary_destroy(v);
         return fail(IVF_E_NO_DEVICE, "vocabulary upload failed");
     }
@@ -1180,6 +1184,8 @@ void ivf_vocabulary_destroy(ivf_vocabulary* v)
     if (v->dChild) (void)hipFree(v->dChild);
     if (v->dDesc) (void)hipFree(v->dDesc);
     if (v->dLive) (void)hipFree(v->dLive);
+    if (v->dWord) (void)hipFree(v->dWord);
+    if (v->dWeight) (void)hipFree(v->dWeight);
     delete v;
 }
 
@@ -1281,7 +1287,7 @@ int ivf_update_quality_scores(const int32_t* assign, int n, float* kp_quality, f
 int ivf::vocabulary_view(const ivf_vocabulary* v, VocabularyView* out)
 {
     if (!v || !out) return fail(IVF_E_INVALID, "null vocabulary");
-    *out = VocabularyView{v->device, v->nNodes, v->depth, v->dChildStart, v->dChild, v->dDesc, v->dLive};
+    *out = VocabularyView{v->device, v->nNodes, v->depth, v->dChildStart, v->dChild, v->dDesc, v->dLive, v->dWord, v->dWeight};
     return IVF_OK;
 }
 

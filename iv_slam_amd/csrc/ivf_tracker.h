@@ -1,7 +1,8 @@
-// ivf_tracker.h -- the batched tracker handle and what its seven translation units share (not part of the public C-ABI):
+// ivf_tracker.h -- the batched tracker handle and what its eight translation units share (not part of the public C-ABI):
 // ivf_track.hip (the handle's life cycle and the TrackWithMotionModel search), ivf_track_local.hip (SearchLocalPoints),
 // ivf_track_bow.hip (TrackReferenceKeyFrame), ivf_track_reloc.hip (Relocalization's SearchByProjection and the set bookkeeping around
-// it), ivf_track_points.hip (the points a search hands to a solver), ivf_pose.hip
+// it), ivf_track_db.hip (Relocalization's first two lines: mBowVec and KeyFrameDatabase::DetectRelocalizationCandidates),
+// ivf_track_points.hip (the points a search hands to a solver), ivf_pose.hip
 // (PoseOptimization) and ivf_pnp.hip (Relocalization's PnPsolver).  One definition of struct ivf_tracker, one host statement of the
 // camera and record constants (TrackParams), and the device pieces searches and solvers both read (the query record, the pose algebra,
 // PredictScale, UpdateQualityScores); what only the projection searches repeat is ivf_search.h's, what only the two solvers repeat
@@ -21,6 +22,15 @@ constexpr int kPnpMaxIterations = 300;            // ivf_tracker_solve_pnp: the 
 // correspondences [max_pairs][nfeatures] (32 B each), per frame {N, mRansacMinInliers, mRansacMaxIts}, and the f64 pose and inlier count
 // of every hypothesis [max_pairs][kPnpMaxIterations]
 struct PnpScratch { void* corr; void* head; double* hypPose; int* hypN; };
+
+// The handle's scratch of ivf_tracker_reloc_candidates (ivf_track_db.hip), grown on demand to cap >= n_frames * n_keyframes cells and
+// frameCap >= n_frames: per (frame, keyframe) mnRelocWords, the smallest shared word, this query's score, accScore, pBestKF, the place
+// (smallest shared word << 32 | keyframe) of the first retained entry that names the keyframe as its pBestKF, and the frame's compacted
+// candidate list (keyframe and place); per frame maxCommonWords
+struct DbScratch {
+    int *common, *minWord; float* score; float* acc; int* best; unsigned long long* place; int* list; unsigned long long* listKey; int* maxCommon;
+    size_t cap; int frameCap;
+};
 
 struct TrackParams {                               // uniform kernel arguments
     int nf, nlevels;
@@ -137,6 +147,7 @@ struct ivf_tracker {
     ivf::Query* dQ = nullptr; float* dLRad = nullptr; int* dCount = nullptr; unsigned* dLists = nullptr; int queryCap = 0;
     ivf::TrackerBowScratch bow{nullptr, nullptr, nullptr, nullptr, nullptr};   // ivf_tracker_search_by_bow: [2 * max_pairs] slots
     ivf::PnpScratch pnp{nullptr, nullptr, nullptr, nullptr};
+    ivf::DbScratch db{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
     size_t ldsBytes = 0;
     hipEvent_t evDone = nullptr;          // end of the previous call: the scratch above belongs to ONE call at a time
     bool ran = false;

@@ -146,6 +146,63 @@ class BatchTracker:
         check(self._lib.ivf_tracker_points_from_keyframe(self._h, pairs.data_ptr(), n_pairs, n_rec, kf_xw.data_ptr(), assign.data_ptr(),
                                                          xw.data_ptr(), has_point.data_ptr(), stream_ptr))
 
+    def bow_vectors(self, vocabulary, records, frames, bow_word, bow_value, bow_n, stream_ptr=None):
+        """Frame::ComputeBoW's mBowVec (ORB/src/Frame.cc:683-694; TemplatedVocabulary.h:1126-1204 with TF_IDF / L1_NORM) for n_frames
+        records at once, the first line of Tracking::Relocalization (ORB/src/Tracking.cc:2274) and what a keyframe brings to the database
+        when it is inserted.  frames: torch.int32 [n_frames] record indices (any number of them); bow_word: torch.int32
+        [n_frames, nfeatures], the words ascending, -1 beyond the count; bow_value: torch.float64 [n_frames, nfeatures]; bow_n:
+        torch.int32 [n_frames], -1 for a record index outside the block.  Bit for bit what ORBVocabulary.transform gives on the same
+        descriptors.  Asynchronous on the given stream."""
+        n_rec = records.numel() // self.record_bytes
+        n_frames = frames.numel()
+        nf = self.nfeatures
+        assert frames.element_size() == 4 and frames.is_contiguous() and not frames.dtype.is_floating_point
+        assert bow_word.element_size() == 4 and bow_word.is_contiguous() and bow_word.numel() >= n_frames * nf
+        assert bow_value.element_size() == 8 and bow_value.dtype.is_floating_point and bow_value.is_contiguous() and bow_value.numel() >= n_frames * nf
+        assert bow_n.element_size() == 4 and bow_n.is_contiguous() and bow_n.numel() >= n_frames
+        check(self._lib.ivf_tracker_bow_vectors(self._h, vocabulary._h, records.data_ptr(), self.record_bytes, n_rec, frames.data_ptr(), n_frames,
+                                                bow_word.data_ptr(), bow_value.data_ptr(), bow_n.data_ptr(), stream_ptr))
+
+    def reloc_candidates(self, vocabulary, kf_bow_word, kf_bow_value, kf_bow_n, kf_neigh, kf_record, bow_word, bow_value, bow_n, frame_record,
+                         cand, ncand, pairs, select, kf_live=None, kf_reloc_score=None, scores=None, common=None, stream_ptr=None):
+        """KeyFrameDatabase::DetectRelocalizationCandidates (ORB/src/KeyFrameDatabase.cc:199-309, L1 score) for n_frames lost frames
+        against a database of n_keyframes keyframes held as flat tensors, keyframe index = insertion order.  kf_bow_word / kf_bow_value
+        [n_keyframes, nfeatures] and kf_bow_n [n_keyframes] as bow_vectors() wrote them; kf_neigh: torch.int32 [n_keyframes, 10] =
+        GetBestCovisibilityKeyFrames(10) as keyframe indices, -1 padded; kf_record: torch.int32 [n_keyframes], the keyframe's gather record
+        or -1; kf_live: torch.uint8 [n_keyframes] or None, 0 = erased; kf_reloc_score: torch.float32 [n_keyframes] or None (= 0), the
+        mRelocScore every keyframe holds before this call (read-only); bow_word / bow_value / bow_n: the frames' vectors; frame_record:
+        torch.int32 [n_frames].  Outputs: cand: torch.int32 [n_frames, max_candidates] (max_candidates = cand.shape[1]) keyframe indices
+        in the reference's order, -1 beyond the count; ncand: torch.int32 [n_frames], the true count; pairs: torch.int32
+        [n_frames * max_candidates, 2] and select: torch.int32 [n_frames * max_candidates], the pair table search_by_bow(), search_reloc()
+        and solve_pnp() start from (n_frames * max_candidates <= max_pairs there); scores: torch.float32 [n_frames, n_keyframes] or None,
+        the score of every scored keyframe and the NaN 0x7fc00000 elsewhere; common: torch.int32 [n_frames, n_keyframes] or None
+        (mnRelocWords).  Asynchronous on the given stream, no host read."""
+        nf = self.nfeatures
+        n_kf = kf_bow_n.numel()
+        n_frames = bow_n.numel()
+        assert cand.dim() == 2 and cand.shape[0] == n_frames and cand.shape[1] >= 1, "cand is [n_frames, max_candidates]"
+        max_cand = int(cand.shape[1])
+        for w, v, n, m in ((kf_bow_word, kf_bow_value, kf_bow_n, n_kf), (bow_word, bow_value, bow_n, n_frames)):
+            assert w.element_size() == 4 and w.is_contiguous() and w.numel() >= m * nf and n.element_size() == 4 and n.is_contiguous()
+            assert v.element_size() == 8 and v.dtype.is_floating_point and v.is_contiguous() and v.numel() >= m * nf
+        assert kf_neigh.element_size() == 4 and kf_neigh.is_contiguous() and kf_neigh.numel() == n_kf * 10, "kf_neigh is [n_keyframes, 10]"
+        assert kf_record.element_size() == 4 and kf_record.is_contiguous() and kf_record.numel() >= n_kf
+        assert kf_live is None or (kf_live.element_size() == 1 and kf_live.is_contiguous() and kf_live.numel() >= n_kf)
+        assert kf_reloc_score is None or (kf_reloc_score.element_size() == 4 and kf_reloc_score.dtype.is_floating_point and kf_reloc_score.is_contiguous() and kf_reloc_score.numel() >= n_kf)
+        assert frame_record.element_size() == 4 and frame_record.is_contiguous() and frame_record.numel() >= n_frames
+        assert cand.element_size() == 4 and cand.is_contiguous() and ncand.element_size() == 4 and ncand.is_contiguous() and ncand.numel() >= n_frames
+        assert pairs.element_size() == 4 and pairs.is_contiguous() and pairs.numel() >= n_frames * max_cand * 2
+        assert select.element_size() == 4 and select.is_contiguous() and select.numel() >= n_frames * max_cand
+        assert scores is None or (scores.element_size() == 4 and scores.dtype.is_floating_point and scores.is_contiguous() and scores.numel() >= n_frames * n_kf)
+        assert common is None or (common.element_size() == 4 and common.is_contiguous() and common.numel() >= n_frames * n_kf)
+        check(self._lib.ivf_tracker_reloc_candidates(self._h, vocabulary._h, kf_bow_word.data_ptr(), kf_bow_value.data_ptr(), kf_bow_n.data_ptr(),
+                                                     None if kf_live is None else kf_live.data_ptr(), kf_neigh.data_ptr(),
+                                                     None if kf_reloc_score is None else kf_reloc_score.data_ptr(), kf_record.data_ptr(), n_kf,
+                                                     bow_word.data_ptr(), bow_value.data_ptr(), bow_n.data_ptr(), frame_record.data_ptr(), n_frames,
+                                                     max_cand, cand.data_ptr(), ncand.data_ptr(), pairs.data_ptr(), select.data_ptr(),
+                                                     None if scores is None else scores.data_ptr(),
+                                                     None if common is None else common.data_ptr(), stream_ptr))
+
     def search_reloc(self, records, pairs, kf_points, assign, nmatches, th=10.0, orb_dist=100, select=None, poses=None, found=None,
                      check_orientation=True, point_quality=None, key_quality=None, stream_ptr=None):
         """ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORB/src/ORBmatcher.cc:1520-1652) as
