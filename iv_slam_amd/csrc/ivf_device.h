@@ -240,6 +240,23 @@ __device__ __forceinline__ void wave_sync_lds()
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
+// lane k's value to every lane (k uniform): v_readlane moves 32 bits, anything else goes through it dword by dword
+template <class T> __device__ __forceinline__ T readlane_b32(T v, int k)
+{
+    static_assert(sizeof(T) == 4, "one dword");
+    return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k));
+}
+__device__ __forceinline__ float readlane_f32(float v, int k) { return readlane_b32(v, k); }
+__device__ __forceinline__ double readlane_f64(double v, int k)
+{
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = readlane_b32((unsigned)b, k), hi = readlane_b32((unsigned)(b >> 32), k);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ uint4 readlane_u4(const uint4 v, int k)
+{
+    return make_uint4(readlane_b32(v.x, k), readlane_b32(v.y, k), readlane_b32(v.z, k), readlane_b32(v.w, k));
+}
 // The rotation-consistency filter of the batched searches, the one device text of it (k_track_greedy, k_bow_search): a match falls into
 // one of 30 bins by the angle between its two keypoints (ORBmatcher.cc:244-251, :1476-1484), ComputeThreeMaxima (:1654-1695) keeps up to
 // three bins, every match of another bin is taken back.

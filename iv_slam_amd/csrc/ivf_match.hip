@@ -2,7 +2,8 @@
 // DBoW2 vocabulary / BoW vectors, the distinctive descriptor and the quality-score update.
 // Each search builds its candidate lists and Hamming distances on the device (CandSource, node_pairs) and then replays the
 // reference's order-dependent greedy logic on the host.  Its kernels (k_hamming_pairs, k_distinct_median, k_bow_transform, k_grid_build,
-// k_grid_window) are file-local, at the top; the grid they and the batched tracker (ivf_track.hip, ivf_track_local.hip) share is ivf_grid.h.
+// k_grid_window) are file-local, at the top; the grid they and the batched tracker (ivf_track.hip, ivf_track_local.hip) share is ivf_grid.h,
+// the descent k_bow_transform and the tracker's BoW units share ivf_bow.h.
 #include <cmath>
 #include <climits>
 #include <cstdio>
@@ -66,18 +67,12 @@ void launch_distinct_median(const uint8_t* desc, int n, int* median, hipStream_t
     hipLaunchKernelGGL(k_distinct_median, dim3(n), dim3(256), 0, s, desc, n, median);
 }
 
-// ---- DBoW2 vocabulary-tree descent (TemplatedVocabulary.h:1217-1259): 16 lanes per descriptor, bow_descend (ivf_bow.h)
+// ---- DBoW2 vocabulary-tree descent (TemplatedVocabulary.h:1217-1259): the n descriptors as one record slot of bow_descend_slot (ivf_bow.h)
 __global__ __launch_bounds__(256) void k_bow_transform(const int* __restrict__ childStart, const int* __restrict__ child,
                                                       const uint8_t* __restrict__ nodeDesc, const uint8_t* __restrict__ desc,
                                                       int n, int nidLevel, int* __restrict__ leaf, int* __restrict__ nodeAt)
 {
-    const int f = (blockIdx.x * 256 + threadIdx.x) >> 4, sub = threadIdx.x & 15;
-    const bool live = f < n;
-    const uint4* pf = (const uint4*)(desc + (size_t)(live ? f : 0) * 32);
-    const uint4 a0 = pf[0], a1 = pf[1];
-    int node, nid;
-    bow_descend(childStart, child, nodeDesc, a0, a1, sub, nidLevel, node, nid);
-    if (live && sub == 0) { leaf[f] = node; nodeAt[f] = nidLevel <= 0 ? 0 : nid; }
+    bow_descend_slot(childStart, child, nodeDesc, desc, n, blockIdx.x, nidLevel, [&](int f, int node, int nid) { leaf[f] = node; nodeAt[f] = nid; });
 }
 
 void launch_bow_transform(const int* childStart, const int* child, const uint8_t* nodeDesc, const uint8_t* desc, int n, int nidLevel,

@@ -86,7 +86,6 @@ template <class LoadAux, class Body>
 DEVINL void walk_lists_prefetched(int n, const int* __restrict__ C, const unsigned* __restrict__ Lp, int lane, LoadAux loadAux, Body body)
 {
     using Aux = decltype(loadAux(0));
-    static_assert(sizeof(Aux) == 4, "the auxiliary word goes through readlane");
     struct Grp { unsigned ent[kPrefetch]; int myCnt; Aux myAux; };
     const int nc = max(n - 1, 0);
     auto load_group = [&](int g0, Grp& g) {
@@ -101,7 +100,7 @@ DEVINL void walk_lists_prefetched(int n, const int* __restrict__ C, const unsign
         for (int k = 0; k < kPrefetch; k++) {
             const int cnt = __builtin_amdgcn_readlane(myCnt, k);
             if (g0 + k >= n || cnt == 0) continue;                                      // an empty window; an invalid query lists nothing
-            body(g0 + k, cnt, grp.ent[k], [&] { return __builtin_bit_cast(Aux, __builtin_amdgcn_readlane(__builtin_bit_cast(int, grp.myAux), k)); });
+            body(g0 + k, cnt, grp.ent[k], [&] { return readlane_b32(grp.myAux, k); });
         }
     };
     if (n > 0) {

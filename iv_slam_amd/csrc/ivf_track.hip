@@ -378,6 +378,16 @@ int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n
     if (t->ran) HIPCHK(hipStreamWaitEvent(st, t->evDone, 0));                          // the handle runs one call at a time
     return IVF_OK;
 }
+int tracker_begin_with_vocabulary(ivf_tracker* t, const ivf_vocabulary* voc, VocabularyView* V, bool reads_records, size_t record_bytes, int n_records,
+                                  int n_items, hipStream_t st)
+{
+    int rc = vocabulary_view(voc, V);
+    if (rc == IVF_OK) rc = tracker_begin(t, reads_records, record_bytes, n_records, n_items, st);
+    if (rc != IVF_OK) return rc;
+    if (V->device != t->cfg.device_id)
+        return fail(IVF_E_INVALID, "the vocabulary lives on device %d, the tracker on device %d", V->device, t->cfg.device_id);
+    return IVF_OK;
+}
 int tracker_end(ivf_tracker* t, hipStream_t st)
 {
     HIPCHK(hipGetLastError());

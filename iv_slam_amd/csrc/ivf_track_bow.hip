@@ -12,10 +12,10 @@
 // histogram needs the bin counts and the members of each bin, not the push order.
 //
 // Kernels (gfx950, wave = 64; no workgroup waits for another, every loop is bounded by nfeatures or by the node count):
-//   k_bow_nodes    16 lanes per keypoint of every record slot (2 * pair + side): bow_descend (ivf_bow.h), the per-call transform's descent
-//   k_bow_featvec  one workgroup per slot: bitonic sort of the unique 64-bit keys (node id << 32 | feature index) in LDS, run starts by a
-//                  block scan -> the CSR feature vector in the handle's scratch
-//   k_bow_search   one workgroup per pair: node merge (binary search of every keyframe node in the frame's list: only equal ids match,
+//   k_bow_nodes    every record slot (2 * pair + side) through bow_descend_slot (ivf_bow.h): the node of every keypoint, -1 on a stopped word
+//   k_bow_featvec  one workgroup per slot: sort_keys_and_runs (ivf_bow.h) on the keys node id << 32 | feature index -> the CSR feature
+//                  vector in the handle's scratch
+//   k_bow_search   one workgroup per pair: node merge (sorted_find of every keyframe node in the frame's list: only equal ids match,
 //                  the lower_bound walk of :186-270), the common nodes handed to the four waves one at a time, the greedy walk,
 //                  the rotation filter (rot_bin / rot_three_maxima, ivf_device.h), the quality epilogue (ivf_tracker.h)
 // Which pairs take part (pair_live) is ivf_search.h's, the one test of it for every search of the handle.
@@ -31,89 +31,47 @@ struct BowParams {
     float nnRatio;
 };
 
+// the record of slot s = 2 * pair + side of a pair that takes part, or null
+DEVINL const uint8_t* slot_record(const BowParams& P, const uint8_t* __restrict__ records, const int2* __restrict__ pairs, const int* __restrict__ select, int s)
+{
+    const int p = s >> 1;
+    const int2 pr = pairs[p];
+    if (!pair_live(P.nRecords, pr, select, p)) return nullptr;
+    return records + (size_t)((s & 1) ? pr.y : pr.x) * P.recBytes;
+}
+
 __global__ __launch_bounds__(256) void k_bow_nodes(BowParams P, VocabularyView V, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
                                                   const int* __restrict__ select, int* __restrict__ nodeKey)
 {
-    const int s = blockIdx.y, p = s >> 1, tid = threadIdx.x;
-    const int2 pr = pairs[p];
-    if (!pair_live(P.nRecords, pr, select, p)) return;
-    const uint8_t* rec = records + (size_t)((s & 1) ? pr.y : pr.x) * P.recBytes;
-    const int n = rec_count(rec, P.nf);
-    if ((int)blockIdx.x * 16 >= n) return;
-    const int f = blockIdx.x * 16 + (tid >> 4), sub = tid & 15;
-    const bool live = f < n;
-    const uint4* pf = (const uint4*)(rec_desc(rec, P.nf) + (size_t)(live ? f : 0) * 32);
-    const uint4 a0 = pf[0], a1 = pf[1];
-    int leaf, nid;
-    bow_descend(V.childStart, V.child, V.nodeDesc, a0, a1, sub, P.nidLevel, leaf, nid);
-    // a stopped word (weight 0) adds neither to mBowVec nor to mFeatVec (TemplatedVocabulary.h:1157)
-    if (live && sub == 0) nodeKey[(size_t)s * P.nf + f] = V.wordLive[leaf] ? (P.nidLevel <= 0 ? 0 : nid) : -1;
+    const int s = blockIdx.y;
+    const uint8_t* rec = slot_record(P, records, pairs, select, s);
+    if (!rec) return;
+    bow_descend_slot(V.childStart, V.child, V.nodeDesc, rec_desc(rec, P.nf), rec_count(rec, P.nf), blockIdx.x, P.nidLevel,
+                     [&](int f, int leaf, int nid) { nodeKey[(size_t)s * P.nf + f] = word_live(V, leaf) ? nid : -1; });
 }
 
 __global__ __launch_bounds__(256) void k_bow_featvec(BowParams P, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
                                                     const int* __restrict__ select, TrackerBowScratch B)
 {
-    extern __shared__ unsigned long long s_key[];             // [npad]: node id << 32 | feature index, ~0 = padding / stopped word
+    extern __shared__ unsigned long long s_key[];             // [npad]: node id << 32 | feature index
     __shared__ int part[256];
-    __shared__ int s_m;
-    const int s = blockIdx.x, p = s >> 1, tid = threadIdx.x;
-    const int2 pr = pairs[p];
-    if (!pair_live(P.nRecords, pr, select, p)) return;
-    const uint8_t* rec = records + (size_t)((s & 1) ? pr.y : pr.x) * P.recBytes;
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const uint8_t* rec = slot_record(P, records, pairs, select, s);
+    if (!rec) return;
     const int n = rec_count(rec, P.nf);
-    unsigned npad = 256;
-    while ((int)npad < n) npad <<= 1;                         // <= the power of two the launch sized the LDS for (n <= nf)
-    if (tid == 0) s_m = 0;
-    __syncthreads();
     const int* keyIn = B.nodeKey + (size_t)s * P.nf;
-    int mine = 0;
-    for (unsigned i = tid; i < npad; i += 256) {
-        unsigned long long key = ~0ull;
-        if ((int)i < n) { const int k = keyIn[i]; if (k >= 0) { key = ((unsigned long long)(unsigned)k << 32) | i; mine++; } }
-        s_key[i] = key;
-    }
-    atomicAdd(&s_m, mine);
-    __syncthreads();
-    // the keys are unique: sorting them is the stable sort of the node ids, i.e. std::map order with addFeature's push order inside a node
-    for (unsigned k = 2; k <= npad; k <<= 1)
-        for (unsigned j = k >> 1; j > 0; j >>= 1) {
-            for (unsigned t = tid; t < npad / 2; t += 256) {
-                const unsigned i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                const unsigned long long a = s_key[i], b = s_key[l];
-                if ((a > b) == ((i & k) == 0)) { s_key[i] = b; s_key[l] = a; }
-            }
-            __syncthreads();
-        }
-    const int m = s_m;                                        // features in the vector: the first m sorted keys
-    const int per = (int)(npad >> 8), j0 = tid * per;
-    auto starts = [&](int j) { return j < m && (j == 0 || (unsigned)(s_key[j - 1] >> 32) != (unsigned)(s_key[j] >> 32)); };
-    int cnt = 0;
-    for (int j = j0; j < j0 + per; j++) cnt += starts(j) ? 1 : 0;
-    part[tid] = cnt;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const int v = tid >= off ? part[tid - off] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int k = part[tid] - cnt;
+    // std::map order of the nodes with addFeature's push order inside a node (FeatureVector.cpp:31-45)
+    const KeyRuns R = sort_keys_and_runs(s_key, key_sort_pad(n), n, tid, [&](unsigned i) { const int k = keyIn[i]; return k >= 0 ? sort_key(k, i) : kNoKey; }, part);
+    int k = R.k;
     int* nodeOut = B.fvNode + (size_t)s * P.nf;
     int* startOut = B.fvStart + (size_t)s * (P.nf + 1);
     int* idxOut = B.fvIdx + (size_t)s * P.nf;
-    for (int j = j0; j < j0 + per; j++) {
-        if (j >= m) break;
-        const unsigned long long key = s_key[j];
-        idxOut[j] = (int)(unsigned)key;
-        if (starts(j)) { nodeOut[k] = (int)(unsigned)(key >> 32); startOut[k] = j; k++; }
+    for (int j = R.j0; j < R.j0 + R.per; j++) {
+        if (j >= R.m) break;
+        idxOut[j] = (int)(unsigned)s_key[j];
+        if (R.starts(j)) { nodeOut[k] = (int)R.id(j); startOut[k] = j; k++; }
     }
-    if (tid == 0) { const int total = part[255]; startOut[total] = m; B.fvN[s] = total; }
-}
-
-DEVINL uint4 readlane4(const uint4 v, int k)
-{
-    return make_uint4((unsigned)__builtin_amdgcn_readlane((int)v.x, k), (unsigned)__builtin_amdgcn_readlane((int)v.y, k),
-                      (unsigned)__builtin_amdgcn_readlane((int)v.z, k), (unsigned)__builtin_amdgcn_readlane((int)v.w, k));
+    if (tid == 0) { const int total = R.total(); startOut[total] = R.m; B.fvN[s] = total; }
 }
 
 __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
@@ -148,10 +106,8 @@ __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* 
     __syncthreads();
     // ---- node merge (:186-270): a keyframe node takes part when the frame's ascending list holds the same id
     for (int a = tid; a < nnK; a += 256) {
-        const int id = nodeK[a];
-        int lo = 0, hi = nnF;
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (nodeF[mid] < id) lo = mid + 1; else hi = mid; }
-        if (lo < nnF && nodeF[lo] == id) s_common[atomicAdd(&s_nCommon, 1)] = a | (lo << 12);
+        const int b = sorted_find(nodeF, nnF, nodeK[a]);
+        if (b >= 0) s_common[atomicAdd(&s_nCommon, 1)] = a | (b << 12);
     }
     __syncthreads();
     const int nCommon = s_nCommon;
@@ -186,9 +142,9 @@ __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* 
             while (todo) {
                 const int k = __ffsll((long long)todo) - 1;
                 todo &= todo - 1;
-                const uint4 qa = readlane4(kaL, k), qb = readlane4(kbL, k);
+                const uint4 qa = readlane_u4(kaL, k), qb = readlane_u4(kbL, k);
                 const int i1 = __builtin_amdgcn_readlane(i1L, k);
-                const float angK = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, angL), k));
+                const float angK = readlane_f32(angL, k);
                 // per lane over its strides: the smallest (distance, list position) and the smallest distance among its others
                 unsigned bestKey = 0xffffffffu; int second = 256, bestI = 0; float bestAng = 0.0f;
                 for (int q = 0; q < nFn; q += 64) {
@@ -213,7 +169,7 @@ __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* 
                 if (bestDist1 <= 50 && (float)bestDist1 < P.nnRatio * (float)bestDist2) {           // TH_LOW, mfNNratio (:234-236)
                     const int bestIdxF = __builtin_amdgcn_readlane(bestI, who);
                     int bin = 0;
-                    if (P.checkOri) bin = rot_bin(angK - __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bestAng), who)));
+                    if (P.checkOri) bin = rot_bin(angK - readlane_f32(bestAng, who));
                     if (lane == 0) {
                         s_assign[bestIdxF] = i1 | (bin << 16);                                       // seen by the next keyframe feature of this node
                         if (P.checkOri) atomicAdd(&s_hist[bin], 1);
@@ -257,13 +213,9 @@ int ivf_tracker_search_by_bow(ivf_tracker* t, const ivf_vocabulary* voc, int lev
     if (!(nn_ratio > 0)) return fail(IVF_E_INVALID, "nn_ratio must be positive");
     if ((d_point_quality == nullptr) != (d_key_quality == nullptr)) return fail(IVF_E_INVALID, "d_point_quality and d_key_quality come together");
     VocabularyView V;
-    int rc = vocabulary_view(voc, &V);
-    if (rc != IVF_OK) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
-    rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st);
+    const int rc = tracker_begin_with_vocabulary(t, voc, &V, true, record_bytes, n_records, n_pairs, st);
     if (rc != IVF_OK) return rc;
-    if (V.device != t->cfg.device_id)
-        return fail(IVF_E_INVALID, "the vocabulary lives on device %d, the tracker on device %d", V.device, t->cfg.device_id);
     if (n_pairs == 0) return IVF_OK;
     const int nf = t->P.nf;
     BowParams P;
@@ -271,10 +223,10 @@ int ivf_tracker_search_by_bow(ivf_tracker* t, const ivf_vocabulary* voc, int lev
     P.recBytes = t->P.recBytes; P.nnRatio = nn_ratio;
     const TrackerBowScratch B = t->bow;
     const int2* pairs = (const int2*)d_pairs;
-    size_t npad = 256;
-    while (npad < (size_t)nf) npad <<= 1;                     // nfeatures <= 4096: at most 32 KB of keys
+    size_t keyBytes;
+    key_sort_pad(nf, &keyBytes);
     hipLaunchKernelGGL(k_bow_nodes, dim3((nf + 15) / 16, 2 * n_pairs), dim3(256), 0, st, P, V, d_records, pairs, d_select, B.nodeKey);
-    hipLaunchKernelGGL(k_bow_featvec, dim3(2 * n_pairs), dim3(256), npad * sizeof(unsigned long long), st, P, d_records, pairs, d_select, B);
+    hipLaunchKernelGGL(k_bow_featvec, dim3(2 * n_pairs), dim3(256), keyBytes, st, P, d_records, pairs, d_select, B);
     hipLaunchKernelGGL(k_bow_search, dim3(n_pairs), dim3(256), (size_t)nf * 2 * sizeof(int), st, P, d_records, pairs, d_select, d_point_flags, B,
                        d_point_quality, d_key_quality, d_assign, d_nmatches);
     return tracker_end(t, st);

@@ -12,13 +12,13 @@
 // keyframe enters lKFsSharingWords at the first of the frame's words it holds.
 //
 // Kernels (gfx950, wave = 64; no workgroup waits for another; every loop is bounded by nfeatures, the tree's depth, n_keyframes or 10):
-//   k_dbv_leaves   16 lanes per keypoint: bow_descend (ivf_bow.h) -> the leaf, or -1 for a stopped word, parked in the d_bow_word row
-//   k_dbv_vector   one workgroup per frame: bitonic sort of the unique keys (word id << 32 | keypoint) in LDS, one thread per run of
+//   k_dbv_leaves   every frame slot through bow_descend_slot (ivf_bow.h) -> the leaf, or -1 for a stopped word, parked in the d_bow_word row
+//   k_dbv_vector   one workgroup per frame: sort_keys_and_runs (ivf_bow.h) on the keys word id << 32 | keypoint, one thread per run of
 //                  equal words adds the weights in keypoint order, one wave adds the norm in word order, everybody divides
-//   k_db_common    one workgroup per (frame, tile of 32 keyframes), the frame's words in LDS, one wave per keyframe: its lanes take the
-//                  keyframe's words with a stride and binary-search the frame's list; ballot / popcount = mnRelocWords, the first hit =
-//                  the smallest shared word; atomicMax -> maxCommonWords of the frame
-//   k_db_score     the same shape with the frame's values in LDS too: the terms of a scored keyframe are found 64 at a time and added
+//   k_db_common    one workgroup per (frame, tile of 32 keyframes), the frame's words in LDS, one wave per keyframe: shared_word_rounds
+//                  takes the keyframe's words 64 per round and finds them in the frame's list (sorted_find, ivf_bow.h); ballot /
+//                  popcount = mnRelocWords, the first hit = the smallest shared word; atomicMax -> maxCommonWords of the frame
+//   k_db_score     the same shape and the same rounds with the frame's values in LDS too: the terms of a scored keyframe are added
 //                  in lane order, i.e. in ascending word order
 //   k_db_select    one workgroup per frame: covisibility accumulation per scored keyframe, bestAccScore, retention, the place of every
 //                  distinct pBestKF (atomicMin of the retained entries' order keys), their ranks, the candidate / pair / select rows
@@ -33,20 +33,11 @@ constexpr int kNeigh = 10;                         // GetBestCovisibilityKeyFram
 constexpr unsigned kNoScoreBits = 0x7fc00000u;     // d_scores of a keyframe that was not scored (include/ivfront.h)
 constexpr unsigned long long kNoPlace = ~0ull;
 
-DEVINL double readlane_f64(double v, int k)
-{
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, k), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), k);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
 DEVINL int clamp_count(int n, int nf) { return n < 0 ? 0 : (n > nf ? nf : n); }
-// position of the first element >= w of the ascending list s[0 .. n), words compared as the sort of k_dbv_vector orders them
-DEVINL int lower_bound_u32(const int* s, int n, unsigned w)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if ((unsigned)s[mid] < w) lo = mid + 1; else hi = mid; }
-    return lo;
-}
+// int minCommonWords = maxCommonWords*0.8f (KeyFrameDatabase.cc:235): the product in float, where a double 0.8 would round some counts
+// the other way; a keyframe is scored when it shares MORE words than that (:246), and only scored keyframes are accumulated (:262)
+DEVINL int min_common(int maxCommon) { return (int)((float)maxCommon * 0.8f); }
+DEVINL bool scored(int common, int minCommon) { return common > minCommon; }
 
 // ---- mBowVec ----------------------------------------------------------------------------------------------------------------------
 struct BowVecParams { int nf, nRecords; size_t recBytes; };
@@ -54,85 +45,42 @@ struct BowVecParams { int nf, nRecords; size_t recBytes; };
 __global__ __launch_bounds__(256) void k_dbv_leaves(BowVecParams P, VocabularyView V, const uint8_t* __restrict__ records, const int* __restrict__ frames,
                                                    int* __restrict__ leafOut)
 {
-    const int s = blockIdx.y, tid = threadIdx.x;
+    const int s = blockIdx.y;
     const int r = frames[s];
     if (!rec_ok(P.nRecords, r)) return;
     const uint8_t* rec = records + (size_t)r * P.recBytes;
-    const int n = rec_count(rec, P.nf);
-    if ((int)blockIdx.x * 16 >= n) return;
-    const int f = blockIdx.x * 16 + (tid >> 4), sub = tid & 15;
-    const bool live = f < n;
-    const uint4* pf = (const uint4*)(rec_desc(rec, P.nf) + (size_t)(live ? f : 0) * 32);
-    const uint4 a0 = pf[0], a1 = pf[1];
-    int leaf, nid;
-    bow_descend(V.childStart, V.child, V.nodeDesc, a0, a1, sub, 0, leaf, nid);
-    // a stopped word adds nothing to mBowVec (TemplatedVocabulary.h:1157: `if(w > 0)`)
-    if (live && sub == 0) leafOut[(size_t)s * P.nf + f] = V.nodeWeight[leaf] > 0.0 ? leaf : -1;
+    bow_descend_slot(V.childStart, V.child, V.nodeDesc, rec_desc(rec, P.nf), rec_count(rec, P.nf), blockIdx.x, 0,
+                     [&](int f, int leaf, int) { leafOut[(size_t)s * P.nf + f] = word_live(V, leaf) ? leaf : -1; });
 }
 
 __global__ __launch_bounds__(256) void k_dbv_vector(BowVecParams P, VocabularyView V, const uint8_t* __restrict__ records, const int* __restrict__ frames,
                                                    unsigned npadMax, int* bowWord, double* bowValue, int* __restrict__ bowN)
 {
-    extern __shared__ unsigned long long s_key[];             // [npadMax]: word id << 32 | keypoint, ~0 = padding / stopped word; then the values
+    extern __shared__ unsigned long long s_key[];             // [npadMax]: word id << 32 | keypoint; then the values
     int* s_leaf = (int*)(s_key + npadMax);                    // [nf] the leaf of every keypoint
     __shared__ int part[256];
-    __shared__ int s_m;
     __shared__ double s_norm;
     const int s = blockIdx.x, tid = threadIdx.x;
     const int r = frames[s];
     if (!rec_ok(P.nRecords, r)) { if (tid == 0) bowN[s] = -1; return; }
     const int n = rec_count(records + (size_t)r * P.recBytes, P.nf);
-    unsigned npad = 256;
-    while ((int)npad < n) npad <<= 1;                         // <= npadMax (n <= nf)
     int* word = bowWord + (size_t)s * P.nf;
     double* value = bowValue + (size_t)s * P.nf;
-    if (tid == 0) s_m = 0;
-    __syncthreads();
-    int mine = 0;
-    for (unsigned i = tid; i < npad; i += 256) {
-        unsigned long long key = ~0ull;
-        if ((int)i < n) {
-            const int leaf = word[i];                         // k_dbv_leaves parked it here
-            s_leaf[i] = leaf;
-            if (leaf >= 0) { key = ((unsigned long long)(unsigned)V.nodeWord[leaf] << 32) | i; mine++; }
-        }
-        s_key[i] = key;
-    }
-    atomicAdd(&s_m, mine);
-    __syncthreads();
-    // the keys are unique: sorting them is std::map order of the words with the keypoints of a word in the order the loop of
-    // TemplatedVocabulary.h:1147-1160 meets them
-    for (unsigned k = 2; k <= npad; k <<= 1)
-        for (unsigned j = k >> 1; j > 0; j >>= 1) {
-            for (unsigned t = tid; t < npad / 2; t += 256) {
-                const unsigned i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                const unsigned long long a = s_key[i], b = s_key[l];
-                if ((a > b) == ((i & k) == 0)) { s_key[i] = b; s_key[l] = a; }
-            }
-            __syncthreads();
-        }
-    const int m = s_m;                                        // keypoints in the vector: the first m sorted keys
-    const int per = (int)(npad >> 8), j0 = tid * per;
-    auto starts = [&](int j) { return j < m && (j == 0 || (unsigned)(s_key[j - 1] >> 32) != (unsigned)(s_key[j] >> 32)); };
-    int cnt = 0;
-    for (int j = j0; j < j0 + per; j++) cnt += starts(j) ? 1 : 0;
-    part[tid] = cnt;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const int v = tid >= off ? part[tid - off] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int k = part[tid] - cnt;
-    const int total = part[255];                              // words of the vector
+    // std::map order of the words with the keypoints of a word in the order the loop of TemplatedVocabulary.h:1147-1160 meets them
+    const KeyRuns R = sort_keys_and_runs(s_key, key_sort_pad(n), n, tid, [&](unsigned i) {
+        const int leaf = word[i];                             // k_dbv_leaves parked it here
+        s_leaf[i] = leaf;
+        return leaf >= 0 ? sort_key(V.nodeWord[leaf], i) : kNoKey;
+    }, part);
+    int k = R.k;
+    const int total = R.total();                              // words of the vector
     // BowVector::addWeight (BowVector.cpp:34-46): operator[] makes the entry 0.0, then one `+= weight` per keypoint, in keypoint order
-    for (int j = j0; j < j0 + per; j++) {
-        if (j >= m) break;
-        if (!starts(j)) continue;
-        const unsigned w = (unsigned)(s_key[j] >> 32);
+    for (int j = R.j0; j < R.j0 + R.per; j++) {
+        if (j >= R.m) break;
+        if (!R.starts(j)) continue;
+        const unsigned w = R.id(j);
         double v = 0.0;
-        for (int e = j; e < m && (unsigned)(s_key[e] >> 32) == w; e++) v += V.nodeWeight[s_leaf[(unsigned)s_key[e]]];
+        for (int e = j; e < R.m && R.id(e) == w; e++) v += V.nodeWeight[s_leaf[(unsigned)s_key[e]]];
         word[k] = (int)w; value[k] = v; k++;
     }
     __syncthreads();
@@ -172,6 +120,22 @@ DEVINL int kf_words(const DbParams& P, const DbIn& I, int k, int nW)
     if (nW == 0 || (I.kfLive && I.kfLive[k] == 0)) return 0;
     return clamp_count(I.kfN[k], P.nf);
 }
+// the keyframe's ascending words kw[0 .. nk), 64 per round in the lanes of one wave, looked up in the frame's ascending list
+// s_fw[0 .. nW) (LDS): round(hit, w, pos, x) gets the ballot of the lanes whose word the frame holds (lane order = word order), the
+// lane's word, its position in the frame's list (-1: not there, or a lane past the end, which reads word nk - 1) and x = fetch(j), what
+// the caller keeps beside word j, requested before the search
+template <class Fetch, class Round>
+DEVINL void shared_word_rounds(const int* kw, int nk, const int* s_fw, int nW, int lane, Fetch fetch, Round round)
+{
+    for (int c = 0; c < nk; c += 64) {
+        const bool in = c + lane < nk;
+        const int j = in ? c + lane : nk - 1;
+        const int w = kw[j];
+        const auto x = fetch(j);
+        const int pos = in ? sorted_find(s_fw, nW, w) : -1;
+        round(__ballot(pos >= 0), w, pos, x);
+    }
+}
 
 __global__ __launch_bounds__(256) void k_db_common(DbParams P, DbIn I, DbScratch S)
 {
@@ -188,17 +152,12 @@ __global__ __launch_bounds__(256) void k_db_common(DbParams P, DbIn I, DbScratch
         const int nk = kf_words(P, I, k, nW);
         const int* kw = I.kfWord + (size_t)k * P.nf;
         int cnt = 0, minw = 0;
-        for (int c = 0; c < nk; c += 64) {
-            const bool in = c + lane < nk;
-            const int w = kw[in ? c + lane : nk - 1];
-            bool found = false;
-            if (in) { const int lo = lower_bound_u32(s_fw, nW, (unsigned)w); found = lo < nW && s_fw[lo] == w; }
-            const unsigned long long hit = __ballot(found);
+        shared_word_rounds(kw, nk, s_fw, nW, lane, [](int) { return 0; }, [&](unsigned long long hit, int w, int, int) {
             if (hit) {
                 if (cnt == 0) minw = __builtin_amdgcn_readlane(w, __ffsll((long long)hit) - 1);   // the keyframe's words ascend too
                 cnt += __popcll(hit);
             }
-        }
+        });
         if (lane == 0) { const size_t c = (size_t)f * P.nK + k; S.common[c] = cnt; S.minWord[c] = minw; }
         waveMax = max(waveMax, cnt);
     }
@@ -215,37 +174,27 @@ __global__ __launch_bounds__(256) void k_db_score(DbParams P, DbIn I, DbScratch 
     const double* fv = I.fValue + (size_t)f * P.nf;
     for (int i = tid; i < nW; i += 256) { s_fw[i] = fw[i]; s_fv[i] = fv[i]; }
     __syncthreads();
-    const int minCommon = (int)((float)S.maxCommon[f] * 0.8f);                                     // :235, the product in float
+    const int minCommon = min_common(S.maxCommon[f]);
     for (int q = wave; q < kKfTile; q += 4) {
         const int k = tile * kKfTile + q;
         if (k >= P.nK) break;
         const size_t c = (size_t)f * P.nK + k;
         const int common = S.common[c];
         unsigned bits = kNoScoreBits;
-        if (common > minCommon) {                                                                  // :246
+        if (scored(common, minCommon)) {
             const int nk = kf_words(P, I, k, nW);
             const int* kw = I.kfWord + (size_t)k * P.nf;
             const double* kv = I.kfValue + (size_t)k * P.nf;
             double score = 0.0;
-            for (int c0 = 0; c0 < nk; c0 += 64) {
-                const bool in = c0 + lane < nk;
-                const int j = in ? c0 + lane : nk - 1;
-                const int w = kw[j];
-                const double wi = kv[j];
+            shared_word_rounds(kw, nk, s_fw, nW, lane, [&](int j) { return kv[j]; }, [&](unsigned long long hit, int, int pos, double wi) {
                 double term = 0.0;
-                bool found = false;
-                if (in) {
-                    const int lo = lower_bound_u32(s_fw, nW, (unsigned)w);
-                    found = lo < nW && s_fw[lo] == w;
-                    if (found) { const double vi = s_fv[lo]; term = fabs(vi - wi) - fabs(vi) - fabs(wi); }   // ScoringObject.cpp:41
-                }
-                unsigned long long hit = __ballot(found);
+                if (pos >= 0) { const double vi = s_fv[pos]; term = fabs(vi - wi) - fabs(vi) - fabs(wi); }   // ScoringObject.cpp:41
                 while (hit) {                                                                      // one `score +=` per common word, words ascending
                     const int b = __ffsll((long long)hit) - 1;
                     hit &= hit - 1;
                     score += readlane_f64(term, b);
                 }
-            }
+            });
             score = -score / 2.0;                                                                  // ScoringObject.cpp:65
             bits = __builtin_bit_cast(unsigned, (float)score);                                     // float si = ... (:249)
         }
@@ -269,13 +218,13 @@ __global__ __launch_bounds__(256) void k_db_select(DbParams P, DbIn I, DbScratch
     const size_t base = (size_t)f * P.nK;
     const int* common = S.common + base;
     const float* score = S.score + base;
-    const int minCommon = (int)((float)S.maxCommon[f] * 0.8f);
+    const int minCommon = min_common(S.maxCommon[f]);
     if (tid == 0) { s_best = 0; s_n = 0; }
     __syncthreads();
     // ---- accumulate by covisibility (:262-287): one thread per scored keyframe
     int myBest = 0;                                           // the bits of the largest accScore above 0 (positive floats order like their bits)
     for (int k = tid; k < P.nK; k += 256) {
-        if (!(common[k] > minCommon)) continue;
+        if (!scored(common[k], minCommon)) continue;
         float bestScore = score[k], accScore = bestScore;
         int bestKF = k;
         for (int j = 0; j < kNeigh; j++) {
@@ -285,7 +234,7 @@ __global__ __launch_bounds__(256) void k_db_select(DbParams P, DbIn I, DbScratch
             const int cn = common[nb];
             if (cn == 0) continue;                                                                 // mnRelocQuery != F->mnId (:273)
             // mRelocScore of the neighbour: this query's when it was scored (:250), else what it held before the call
-            const float s = cn > minCommon ? score[nb] : (I.kfReloc ? I.kfReloc[nb] : 0.0f);
+            const float s = scored(cn, minCommon) ? score[nb] : (I.kfReloc ? I.kfReloc[nb] : 0.0f);
             accScore += s;
             if (s > bestScore) { bestKF = nb; bestScore = s; }
         }
@@ -297,7 +246,7 @@ __global__ __launch_bounds__(256) void k_db_select(DbParams P, DbIn I, DbScratch
     const float minScoreToRetain = 0.75f * __builtin_bit_cast(float, s_best);                      // :290
     // ---- the place of every distinct pBestKF: the smallest order key among the retained entries that name it (:294-305)
     for (int k = tid; k < P.nK; k += 256) {
-        if (!(common[k] > minCommon)) continue;
+        if (!scored(common[k], minCommon)) continue;
         if (S.acc[base + k] > minScoreToRetain)
             atomicMin(&S.place[base + S.best[base + k]], ((unsigned long long)(unsigned)S.minWord[base + k] << 32) | (unsigned)k);
     }
@@ -372,20 +321,16 @@ int ivf_tracker_bow_vectors(ivf_tracker* t, const ivf_vocabulary* voc, const uin
         return fail(IVF_E_INVALID, "null argument or n_frames < 0");
     if (((size_t)d_records & 15) != 0) return fail(IVF_E_INVALID, "the record block must be 16-byte aligned");
     VocabularyView V;
-    int rc = vocabulary_view(voc, &V);
-    if (rc != IVF_OK) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
-    rc = tracker_begin(t, true, record_bytes, n_records, 0, st);
+    int rc = tracker_begin_with_vocabulary(t, voc, &V, true, record_bytes, n_records, 0, st);
     if (rc != IVF_OK) return rc;
-    if (V.device != t->cfg.device_id)
-        return fail(IVF_E_INVALID, "the vocabulary lives on device %d, the tracker on device %d", V.device, t->cfg.device_id);
     if (n_frames == 0) return IVF_OK;
     const int nf = t->P.nf;
     BowVecParams P;
     P.nf = nf; P.nRecords = n_records; P.recBytes = t->P.recBytes;
-    unsigned npad = 256;
-    while (npad < (unsigned)nf) npad <<= 1;                   // nfeatures <= 4096: 32 KB of keys and 16 KB of leaves at most
-    const size_t lds = (size_t)npad * sizeof(unsigned long long) + (size_t)nf * sizeof(int);
+    size_t lds;
+    const unsigned npad = key_sort_pad(nf, &lds);
+    lds += (size_t)nf * sizeof(int);                          // the leaves behind the keys: 16 KB more at most
     // the outputs are the only per-frame storage: a list of any length is walked in chunks the grid's second dimension can hold
     for (int c0 = 0; c0 < n_frames; c0 += 32768) {
         const int nc = n_frames - c0 < 32768 ? n_frames - c0 : 32768;
@@ -410,13 +355,9 @@ int ivf_tracker_reloc_candidates(ivf_tracker* t, const ivf_vocabulary* voc, cons
     if (n_frames > 0 && (!d_bow_word || !d_bow_value || !d_bow_n || !d_frame_record || !d_cand || !d_ncand || !d_pairs || !d_select))
         return fail(IVF_E_INVALID, "null frame or output array");
     VocabularyView V;
-    int rc = vocabulary_view(voc, &V);
-    if (rc != IVF_OK) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
-    rc = tracker_begin(t, false, 0, 0, 0, st);
+    int rc = tracker_begin_with_vocabulary(t, voc, &V, false, 0, 0, 0, st);
     if (rc != IVF_OK) return rc;
-    if (V.device != t->cfg.device_id)
-        return fail(IVF_E_INVALID, "the vocabulary lives on device %d, the tracker on device %d", V.device, t->cfg.device_id);
     if (n_frames == 0) return IVF_OK;
     DbParams P;
     P.nf = t->P.nf; P.nK = n_keyframes; P.nF = n_frames; P.maxCand = max_candidates; P.nTiles = (n_keyframes + kKfTile - 1) / kKfTile;

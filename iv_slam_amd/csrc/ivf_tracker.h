@@ -6,7 +6,7 @@
 // (PoseOptimization) and ivf_pnp.hip (Relocalization's PnPsolver).  One definition of struct ivf_tracker, one host statement of the
 // camera and record constants (TrackParams), and the device pieces searches and solvers both read (the query record, the pose algebra,
 // PredictScale, UpdateQualityScores); what only the projection searches repeat is ivf_search.h's, what only the two solvers repeat
-// ivf_solve.h's.
+// ivf_solve.h's, what the BoW units (ivf_track_bow.hip, ivf_track_db.hip and the per-call transform) repeat ivf_bow.h's.
 #pragma once
 #include "ivf_bow.h"
 #include <vector>
@@ -171,11 +171,15 @@ struct ivf_tracker {
 
 namespace ivf {
 // tracker_begin: the argument checks every tracker entry point shares, hipSetDevice and the wait for the handle's previous call;
+// tracker_begin_with_vocabulary: the same for the entry points that take a vocabulary (ivf_track_bow.hip, ivf_track_db.hip) -- its view
+// first, then tracker_begin, then that both live on one device;
 // tracker_end: the event the next call waits for;
 // search_args_ok: what the three projection searches check alike -- the pointers (points: the array of search_local / search_reloc),
 // the 16-byte alignment of what the kernels read as uint4 and, in a call of n_items != 0, that the quality arrays come together;
 // tracker_grow_queries: the candidate scratch (dQ, dLRad, dCount, dLists) for at least `cap` queries per frame / pair
 int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n_records, int n_items, hipStream_t st);
+int tracker_begin_with_vocabulary(ivf_tracker* t, const ivf_vocabulary* voc, VocabularyView* V, bool reads_records, size_t record_bytes, int n_records,
+                                  int n_items, hipStream_t st);
 int tracker_end(ivf_tracker* t, hipStream_t st);
 int search_args_ok(const ivf_tracker* t, const void* records, const void* items, bool has_points, const void* points, const void* assign,
                    const void* nmatches, int n_items, const float* point_quality, const float* key_quality);

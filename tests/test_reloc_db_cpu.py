@@ -92,3 +92,11 @@ def test_the_float_product_of_the_threshold_cannot_be_told_from_the_double_one()
     for sc in SCENES:
         for f in range(len(sc["frame_vecs"])):
             assert answer(D.run(sc, f)) == answer(D.run(sc, f, "double08"))
+
+
+def test_lookup_size_cases_are_not_vacuous():
+    """the hand-packed databases of tests/test_gpu_bow_sizes.py under the restatement alone: every (frame, keyframe) word-count pair is
+    met and a scored keyframe's shared words lie in two 64-word rounds of its list"""
+    import test_gpu_bow_sizes as Z
+    for nK in Z.N_KEYFRAMES:
+        Z.assert_lookup_not_vacuous(nK)

@@ -112,3 +112,14 @@ def test_new_entry_points_are_exported_bound_and_documented():
         assert m and "Tracking.cc:" in m.group(1), "%s: the header comment cites the reference" % name
     assert len(_lib._SIGS["ivf_tracker_search_by_bow"][1]) == 17 and len(_lib._SIGS["ivf_tracker_points_from_keyframe"][1]) == 9
     assert callable(track.BatchTracker.search_by_bow) and callable(track.BatchTracker.points_from_keyframe)
+
+
+@pytest.mark.parametrize("name", ["large", "small"])
+def test_size_sweep_inputs_are_not_vacuous(name):
+    """the records of tests/test_gpu_bow_sizes.py under the oracle alone: a record with more than 64 words, a word that five keypoints
+    reach, a keypoint lost to a stopped word; every (keyframe, frame) pair with 16 or more keypoints on both sides has a match, with the
+    nodes one level below the root and with every feature in node 0"""
+    import test_gpu_bow_sizes as Z
+    Z.assert_sweep_not_vacuous(name)
+    for kind in ("level1", "root"):
+        Z.assert_pairs_not_vacuous(name, kind)
