@@ -760,6 +760,87 @@ int  ivf_tracker_reloc_candidates(ivf_tracker* t, const ivf_vocabulary* voc, con
                                   const double* d_bow_value, const int32_t* d_bow_n, const int32_t* d_frame_record, int n_frames,
                                   int max_candidates, int32_t* d_cand, int32_t* d_ncand, int32_t* d_pairs, int32_t* d_select,
                                   float* d_scores, int32_t* d_common, void* hip_stream);
+
+/* ---- Tracking::UpdateLocalMap and the tail of TrackLocalMap from a device-resident map ---------------------------------------------
+ * The map as flat device arrays the caller keeps between calls, in the style of the keyframe database above: keyframe index = position
+ * in the caller's tables, map-point index = position in `points`, -1 = none.  Every index read from one of these tables is checked
+ * against its range before it is used: an out-of-range entry is skipped as if it were -1, a CSR row whose offsets are negative,
+ * decreasing or past the table's length is an empty row.  No kernel reads outside the arrays, whatever the tables hold. */
+typedef struct ivf_map_view {
+    const ivf_local_point* points;   /* [n_points] the record the searches read; flags bit 0 = isBad(), bit 1 = Observations() > 0 */
+    const int32_t* obs_offsets;      /* [n_points + 1] CSR into obs_kf */
+    const int32_t* obs_kf;           /* [n_obs] MapPoint::GetObservations() as keyframe indices */
+    const int32_t* kf_point_offsets; /* [n_keyframes + 1] CSR into kf_points; a row holds at most nfeatures entries (the keyframe's
+                                      * keypoints), a longer one is read up to nfeatures */
+    const int32_t* kf_points;        /* [n_kf_points] KeyFrame::GetMapPointMatches() as map-point indices or -1, in keypoint order */
+    const uint8_t* kf_live;          /* [n_keyframes] 0 = isBad(); NULL = all live */
+    const int32_t* kf_neigh;         /* [n_keyframes][10] GetBestCovisibilityKeyFrames(10), -1 padded (ivf_tracker_reloc_candidates' table) */
+    const int32_t* kf_child_offsets; /* [n_keyframes + 1] CSR into kf_children */
+    const int32_t* kf_children;      /* [n_children] GetChilds() in the order the caller's std::set iterates */
+    const int32_t* kf_parent;        /* [n_keyframes] GetParent() or -1 */
+    const int32_t* kf_order;         /* [n_keyframes] the keyframe indices in the order the host's std::map<KeyFrame*, int> iterates
+                                      * them (by pointer value, which only the host knows): a permutation; NULL = identity.  The table is
+                                      * walked by position: an out-of-range entry is skipped, a keyframe it does not name is never voted in */
+    int32_t n_points, n_keyframes, n_obs, n_kf_points, n_children;
+} ivf_map_view;
+/* ivf_tracker_update_local_map: Tracking::UpdateLocalMap (ORB/src/Tracking.cc:2134-2270) = UpdateLocalKeyFrames then UpdateLocalPoints,
+ * for n_frames frames against one map, between the first ivf_tracker_optimize_pose and ivf_tracker_search_local.  No records are read.
+ * d_frame_points [n_frames][nfeatures] (in/out) = mCurrentFrame.mvpMapPoints as map-point indices or -1; entries past the frame's
+ * keypoint count are -1 by contract.  Per frame:
+ *   the vote (:2170-2185): every held point that is not bad adds one to every keyframe of its observations; a bad held point becomes -1
+ *   in d_frame_points;
+ *   no vote at all (:2187): the reference returns and UpdateLocalPoints runs on the previous mvpLocalKeyFrames.  d_local_kf
+ *   [n_frames][max_local_keyframes] and d_n_local_kf [n_frames] are in/out like that member: the row is kept as it came in, its count is
+ *   clamped to [0, max_local_keyframes] and written back, its entries are range-checked when the points are collected, d_ref_kf[f] is
+ *   left alone;
+ *   otherwise the voted, live keyframes in kf_order (:2197-2212); d_ref_kf[f] = pKFmax, the first in that order with a strictly larger
+ *   count, written only when there is one (:2266-2269);
+ *   the expansion (:2216-2264) over the K voted entries only (the end iterator is taken before the loop): leave when the list holds more
+ *   than 80; append the first of the ten neighbours that is live and not yet included; append the first child, in the given order, that
+ *   is live and not yet included; if there is a parent that is not yet included, append it WITHOUT a liveness test and leave the whole
+ *   expansion (the break of :2261 ends the outer loop);
+ *   d_n_local_kf[f] = the true length of the list; the row holds its first max_local_keyframes entries and -1 beyond the count;
+ *   the points (:2143-2166): the keyframes of the row in order, each keyframe's matches in keypoint order, -1 and bad points skipped,
+ *   every point once, at its first appearance.
+ * Outputs in the layout ivf_tracker_search_local takes: d_points [n_frames][max_points_per_frame], copies of the map's records with
+ * flags bit 0 additionally set on a point the frame already holds (mnLastFrameSeen == mnId, :2099-2100, :2114); d_point_ids, laid out
+ * the same way, the map-point index of each; d_point_offsets [n_frames + 1] = f * max_points_per_frame; padding past the count has
+ * flags = 1, id -1 and zeros elsewhere, so the search skips it; d_n_local_points [n_frames] = the true count, the first
+ * max_points_per_frame in order being kept; d_occupied [n_frames][nfeatures] = 1 where the keypoint holds a point with
+ * Observations() > 0 (ivf_tracker_search_local's d_occupied).
+ * Not done here: IncreaseVisible / IncreaseFound / mnLastFrameSeen on the map.  They are map state shared by the frames of a batch;
+ * the caller folds them in from d_frame_points and the search's outputs if it keeps them.
+ * IVF_E_INVALID: a null pointer (kf_live and kf_order excepted), a negative table length, n_frames outside [0, max_pairs], a cap < 1,
+ * arrays read as 16-byte pieces that are not 16-byte aligned; IVF_E_CAPACITY: n_frames * max_points_per_frame or max_local_keyframes *
+ * nfeatures beyond 2^31 - 1 (or a hash set beyond 2^30 slots).  Two launches and one memset; integer atomics only, two runs are byte-identical.  The scratch sits on
+ * the handle and grows on demand like ivf_tracker_reloc_candidates': a vote row of n_keyframes ints per frame when n_keyframes exceeds
+ * what LDS holds (8192), and per frame a hash set of 8 bytes x the power of two >= 2 * min(max_local_keyframes * nfeatures, n_points).
+ * Asynchronous on hip_stream; obeys the handle's one-call-at-a-time rule. */
+int  ivf_tracker_update_local_map(ivf_tracker* t, const ivf_map_view* map, int32_t* d_frame_points, int n_frames, int max_local_keyframes,
+                                  int max_points_per_frame, int32_t* d_local_kf, int32_t* d_n_local_kf, int32_t* d_ref_kf,
+                                  ivf_local_point* d_points, int32_t* d_point_ids, int32_t* d_point_offsets, int32_t* d_n_local_points,
+                                  uint8_t* d_occupied, void* hip_stream);
+/* What ivf_tracker_update_local_map switches on and allocates, for tests and measurements: the largest n_keyframes whose vote rows
+ * live in LDS, and the bytes of the hash sets of one call (cleared by its memset), 0 for arguments the call would refuse. */
+int    ivf_tracker_local_map_lds_keyframes(void);
+size_t ivf_tracker_local_map_set_bytes(int nfeatures, int n_points, int n_frames, int max_local_keyframes);
+/* The tail of Tracking::TrackLocalMap (ORB/src/Tracking.cc:1636-1691) without a host read; n_frames <= max_pairs, asynchronous, the
+ * handle's one-call-at-a-time rule; IVF_E_INVALID for a null required pointer or n_points < 0.
+ * merge_local: d_frame_points[f][i] = d_point_ids[d_point_offsets[f] + d_assign[f][i]] where ivf_tracker_search_local's d_assign is
+ * inside the frame's range (ORBmatcher.cc:124: the keypoint receives the point, replacing what it held); other entries are kept.
+ * points_from_map: the input of ivf_tracker_optimize_pose over ALL held points: d_xw / d_has_point as ivf_tracker_points_from_local
+ * writes them, from d_points[d_frame_points[f][i]].pos of the map; d_quality [n_frames][nfeatures] (nullable) = d_point_quality
+ * [n_points] of the held point, 1.0f where d_point_quality is NULL or the keypoint holds none.
+ * close_local_map (:1648-1677): d_ninliers[f] = the keypoints that hold a point and are not in d_outlier (ivf_tracker_optimize_pose's),
+ * with only_tracking == 0 only those whose point has Observations() > 0 (flags bit 1); with stereo != 0 an outlier keypoint's entry
+ * of d_frame_points becomes -1 (:1673-1674).  The 30 / 50 decision (:1684-1691) stays with the caller, who knows mnLastRelocFrameId. */
+int  ivf_tracker_merge_local(ivf_tracker* t, const int32_t* d_point_ids, const int32_t* d_point_offsets, const int32_t* d_assign, int n_frames,
+                             int32_t* d_frame_points, void* hip_stream);
+int  ivf_tracker_points_from_map(ivf_tracker* t, const ivf_local_point* d_map_points, int n_points, const float* d_point_quality,
+                                 const int32_t* d_frame_points, int n_frames, float* d_xw, uint8_t* d_has_point, float* d_quality,
+                                 void* hip_stream);
+int  ivf_tracker_close_local_map(ivf_tracker* t, const ivf_local_point* d_map_points, int n_points, const uint8_t* d_outlier, int n_frames,
+                                 int only_tracking, int stereo, int32_t* d_frame_points, int32_t* d_ninliers, void* hip_stream);
 /* MapPoint::ComputeDistinctiveDescriptors (ORB/src/MapPoint.cc:247-312): desc = the n observed descriptors (rows of
  * vDescriptors, in mObservations order); *best_index = the row to copy into mDescriptor, *best_median (nullable) its median. */
 int  ivf_distinctive_descriptor(const uint8_t* desc, int n, int* best_index, int* best_median, int device_id);

@@ -40,6 +40,13 @@ LOCAL_POINT_DTYPE = np.dtype([("pos", np.float32, 3), ("normal", np.float32, 3),
 assert LOCAL_POINT_DTYPE.itemsize == 80
 
 
+# ivf_map_view (include/ivfront.h): the map as flat device arrays, what ivf_tracker_update_local_map reads
+class MapViewC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("points", "obs_offsets", "obs_kf", "kf_point_offsets", "kf_points", "kf_live", "kf_neigh",
+                                          "kf_child_offsets", "kf_children", "kf_parent", "kf_order")] + \
+               [(n, C.c_int32) for n in ("n_points", "n_keyframes", "n_obs", "n_kf_points", "n_children")]
+
+
 class TrackConfig(C.Structure):
     _fields_ = [("nfeatures", C.c_int32), ("nlevels", C.c_int32), ("scale_factors", C.c_float * MAX_LEVELS),
                 ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float), ("b", C.c_float),
@@ -171,6 +178,12 @@ _SIGS = {
                                         vp, vp, vp, vp, vp, vp, vp]),
     "ivf_tracker_bow_vectors": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
     "ivf_tracker_reloc_candidates": (C.c_int, [vp, vp] + [vp] * 7 + [C.c_int] + [vp] * 4 + [C.c_int, C.c_int] + [vp] * 6 + [vp]),
+    "ivf_tracker_update_local_map": (C.c_int, [vp, C.POINTER(MapViewC), vp, C.c_int, C.c_int, C.c_int] + [vp] * 8 + [vp]),
+    "ivf_tracker_local_map_lds_keyframes": (C.c_int, []),
+    "ivf_tracker_local_map_set_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ivf_tracker_merge_local": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp]),
+    "ivf_tracker_points_from_map": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
+    "ivf_tracker_close_local_map": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "ivf_fcn_create": (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
     "ivf_fcn_destroy": (None, [vp]),
     "ivf_fcn_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),

@@ -1,11 +1,15 @@
 // ivf_track_points.hip -- the points a batched search hands to a solver (ivf_pose.hip, ivf_pnp.hip), on the tracker handle
-// (ivf_tracker.h): for every keypoint of a frame the world position of what the search assigned to it, and a flag.
+// (ivf_tracker.h): for every keypoint of a frame the world position of what the search assigned to it, and a flag; and the tail of
+// Tracking::TrackLocalMap (ORB/src/Tracking.cc:1636-1691) around them, on a frame's map-point indices (ivf_tracker_update_local_map).
 //
 //   k_points_from_pairs     xw[p][i2] = Frame::UnprojectStereo (ORB/src/Frame.cc:958-972) of keypoint assign[p][i2] of the LAST record of pair p
 //                           under its last pose (ivf_tracker_run's assignment): unproject_stereo, the arithmetic k_track_prepare projected with
 //   k_points_from_local     GetWorldPos() of the local map point every keypoint was assigned by ivf_tracker_search_local
 //   k_points_from_keyframe  xw[p][i] = GetWorldPos() of the map point that keyframe keypoint assign[p][i] holds (ivf_tracker_search_by_bow;
 //                           Tracking.cc:1173: mvpMapPoints = vpMapPointMatches)
+//   k_merge_local           framePoints[f][i] = the map-point index of the local point ivf_tracker_search_local gave keypoint i (ORBmatcher.cc:124)
+//   k_points_from_map       GetWorldPos() and the quality score of the map point every keypoint holds: PoseOptimization over all of them
+//   k_close_local_map       mnMatchesInliers and the stereo outliers' release (Tracking.cc:1648-1677)
 #include "ivf_tracker.h"
 
 using namespace ivf;
@@ -74,6 +78,55 @@ __global__ __launch_bounds__(256) void k_points_from_keyframe(int nf, int nRecor
     pt.store(xw, hasPoint, o);
 }
 
+__global__ __launch_bounds__(256) void k_merge_local(int nf, const int* __restrict__ pointIds, const int* __restrict__ offsets, const int* __restrict__ assign,
+                                                    int* __restrict__ framePoints)
+{
+    const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nf) return;
+    const size_t o = (size_t)f * nf + i;
+    const int m0 = offsets[f], M = offsets[f + 1] - m0, a = assign[o];
+    if (m0 >= 0 && a >= 0 && a < M) framePoints[o] = pointIds[(size_t)m0 + a];
+}
+
+__global__ __launch_bounds__(256) void k_points_from_map(int nf, const ivf_local_point* __restrict__ mapPoints, int nPoints, const float* __restrict__ pointQuality,
+                                                        const int* __restrict__ framePoints, float* __restrict__ xw, uint8_t* __restrict__ hasPoint,
+                                                        float* __restrict__ quality)
+{
+    const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nf) return;
+    const size_t o = (size_t)f * nf + i;
+    const int m = framePoints[o];
+    Point pt;
+    float q = 1.0f;
+    if ((unsigned)m < (unsigned)nPoints) {
+        pt.set(mapPoints[m].pos);
+        if (pointQuality) q = pointQuality[m];
+    }
+    pt.store(xw, hasPoint, o);
+    if (quality) quality[o] = q;
+}
+
+// one workgroup per frame: the count is a sum of integers, the same in every run
+__global__ __launch_bounds__(256) void k_close_local_map(int nf, const ivf_local_point* __restrict__ mapPoints, int nPoints, const uint8_t* __restrict__ outlier,
+                                                        int onlyTracking, int stereo, int* __restrict__ framePoints, int* __restrict__ ninliers)
+{
+    __shared__ int s_n;
+    const int f = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    int n = 0;
+    for (int i = tid; i < nf; i += 256) {
+        const size_t o = (size_t)f * nf + i;
+        const int m = framePoints[o];
+        if ((unsigned)m >= (unsigned)nPoints) continue;
+        if (!outlier[o]) n += (onlyTracking || (mapPoints[m].flags & 2)) ? 1 : 0;                  // :1660-1666
+        else if (stereo) framePoints[o] = -1;                                                      // :1673-1674
+    }
+    if (n) atomicAdd(&s_n, n);
+    __syncthreads();
+    if (tid == 0) ninliers[f] = s_n;
+}
+
 }  // namespace
 
 extern "C" {
@@ -118,6 +171,48 @@ int ivf_tracker_points_from_keyframe(ivf_tracker* t, const int32_t* d_pairs, int
     if (rc != IVF_OK) return rc;
     hipLaunchKernelGGL(k_points_from_keyframe, dim3((t->P.nf + 255) / 256, n_pairs), dim3(256), 0, st, t->P.nf, n_records, (const int2*)d_pairs, d_kf_xw,
                        d_assign, d_xw, d_has_point);
+    return tracker_end(t, st);
+}
+
+int ivf_tracker_merge_local(ivf_tracker* t, const int32_t* d_point_ids, const int32_t* d_point_offsets, const int32_t* d_assign, int n_frames,
+                            int32_t* d_frame_points, void* hip_stream)
+{
+    if (!t || !d_point_ids || !d_point_offsets || !d_assign || !d_frame_points) return fail(IVF_E_INVALID, "null argument");
+    if (n_frames == 0) return IVF_OK;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int rc = tracker_begin(t, false, 0, 0, n_frames, st);
+    if (rc != IVF_OK) return rc;
+    hipLaunchKernelGGL(k_merge_local, dim3((t->P.nf + 255) / 256, n_frames), dim3(256), 0, st, t->P.nf, d_point_ids, d_point_offsets, d_assign, d_frame_points);
+    return tracker_end(t, st);
+}
+
+int ivf_tracker_points_from_map(ivf_tracker* t, const ivf_local_point* d_map_points, int n_points, const float* d_point_quality,
+                                const int32_t* d_frame_points, int n_frames, float* d_xw, uint8_t* d_has_point, float* d_quality, void* hip_stream)
+{
+    if (!t || !d_frame_points || !d_xw || !d_has_point || (n_points > 0 && !d_map_points)) return fail(IVF_E_INVALID, "null argument");
+    if (n_points < 0) return fail(IVF_E_INVALID, "n_points must be >= 0");
+    if (((size_t)d_map_points & 15) != 0) return fail(IVF_E_INVALID, "the point array must be 16-byte aligned");
+    if (n_frames == 0) return IVF_OK;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int rc = tracker_begin(t, false, 0, 0, n_frames, st);
+    if (rc != IVF_OK) return rc;
+    hipLaunchKernelGGL(k_points_from_map, dim3((t->P.nf + 255) / 256, n_frames), dim3(256), 0, st, t->P.nf, d_map_points, n_points, d_point_quality,
+                       d_frame_points, d_xw, d_has_point, d_quality);
+    return tracker_end(t, st);
+}
+
+int ivf_tracker_close_local_map(ivf_tracker* t, const ivf_local_point* d_map_points, int n_points, const uint8_t* d_outlier, int n_frames,
+                                int only_tracking, int stereo, int32_t* d_frame_points, int32_t* d_ninliers, void* hip_stream)
+{
+    if (!t || !d_outlier || !d_frame_points || !d_ninliers || (n_points > 0 && !d_map_points)) return fail(IVF_E_INVALID, "null argument");
+    if (n_points < 0) return fail(IVF_E_INVALID, "n_points must be >= 0");
+    if (((size_t)d_map_points & 15) != 0) return fail(IVF_E_INVALID, "the point array must be 16-byte aligned");
+    if (n_frames == 0) return IVF_OK;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int rc = tracker_begin(t, false, 0, 0, n_frames, st);
+    if (rc != IVF_OK) return rc;
+    hipLaunchKernelGGL(k_close_local_map, dim3(n_frames), dim3(256), 0, st, t->P.nf, d_map_points, n_points, d_outlier, only_tracking, stereo,
+                       d_frame_points, d_ninliers);
     return tracker_end(t, st);
 }
 

@@ -1,8 +1,9 @@
-// ivf_tracker.h -- the batched tracker handle and what its eight translation units share (not part of the public C-ABI):
+// ivf_tracker.h -- the batched tracker handle and what its nine translation units share (not part of the public C-ABI):
 // ivf_track.hip (the handle's life cycle and the TrackWithMotionModel search), ivf_track_local.hip (SearchLocalPoints),
 // ivf_track_bow.hip (TrackReferenceKeyFrame), ivf_track_reloc.hip (Relocalization's SearchByProjection and the set bookkeeping around
 // it), ivf_track_db.hip (Relocalization's first two lines: mBowVec and KeyFrameDatabase::DetectRelocalizationCandidates),
-// ivf_track_points.hip (the points a search hands to a solver), ivf_pose.hip
+// ivf_track_map.hip (UpdateLocalMap: the local keyframes and points of a frame from a device-resident map),
+// ivf_track_points.hip (the points a search hands to a solver and the tail of TrackLocalMap), ivf_pose.hip
 // (PoseOptimization) and ivf_pnp.hip (Relocalization's PnPsolver).  One definition of struct ivf_tracker, one host statement of the
 // camera and record constants (TrackParams), and the device pieces searches and solvers both read (the query record, the pose algebra,
 // PredictScale, UpdateQualityScores); what only the projection searches repeat is ivf_search.h's, what only the two solvers repeat
@@ -31,6 +32,11 @@ struct DbScratch {
     int *common, *minWord; float* score; float* acc; int* best; unsigned long long* place; int* list; unsigned long long* listKey; int* maxCommon;
     size_t cap; int frameCap;
 };
+
+// The handle's scratch of ivf_tracker_update_local_map (ivf_track_map.hip), grown on demand: the vote rows [n_frames][n_keyframes] of the
+// calls whose n_keyframes exceeds the LDS row (voteCap ints), and per frame the hash set of the de-duplication, `slots` point ids
+// followed by `slots` first positions (hashCap words of 4 bytes in all)
+struct MapScratch { int* vote; unsigned* hash; size_t voteCap, hashCap; };
 
 struct TrackParams {                               // uniform kernel arguments
     int nf, nlevels;
@@ -148,6 +154,7 @@ struct ivf_tracker {
     ivf::TrackerBowScratch bow{nullptr, nullptr, nullptr, nullptr, nullptr};   // ivf_tracker_search_by_bow: [2 * max_pairs] slots
     ivf::PnpScratch pnp{nullptr, nullptr, nullptr, nullptr};
     ivf::DbScratch db{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    ivf::MapScratch map{nullptr, nullptr, 0, 0};
     size_t ldsBytes = 0;
     hipEvent_t evDone = nullptr;          // end of the previous call: the scratch above belongs to ONE call at a time
     bool ran = false;

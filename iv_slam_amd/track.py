@@ -268,6 +268,77 @@ class BatchTracker:
                                                   int(n_rounds), poses.data_ptr(), outlier.data_ptr(), ninliers.data_ptr(),
                                                   None if chi2 is None else chi2.data_ptr(), stream_ptr))
 
+    def update_local_map(self, map_view, frame_points, local_kf, n_local_kf, ref_kf, points, point_ids, point_offsets, n_local_points,
+                         occupied, stream_ptr=None):
+        """Tracking::UpdateLocalMap (ORB/src/Tracking.cc:2134-2270) for n_frames frames against one device-resident map, between the first
+        optimize_pose() and search_local().  map_view: a MapView; frame_points: torch.int32 [n_frames, nfeatures] in/out, the map-point
+        index every keypoint holds or -1 (a bad held point becomes -1); local_kf: torch.int32 [n_frames, max_local_keyframes] and
+        n_local_kf: torch.int32 [n_frames], in/out like mvpLocalKeyFrames (kept for a frame without a vote); ref_kf: torch.int32
+        [n_frames], written where there is a pKFmax; points: torch.uint8 view of LOCAL_POINT_DTYPE records [n_frames,
+        max_points_per_frame] (max_points_per_frame = point_ids.shape[1]), point_ids: torch.int32 [n_frames, max_points_per_frame],
+        point_offsets: torch.int32 [n_frames + 1] and occupied: torch.uint8 [n_frames, nfeatures], what search_local() takes;
+        n_local_points: torch.int32 [n_frames], the true count.  Asynchronous on the given stream, no host read."""
+        nf = self.nfeatures
+        assert isinstance(map_view, MapView), "map_view is an iv_slam_amd.track.MapView"
+        assert frame_points.dim() == 2 and frame_points.shape[1] == nf, "frame_points is [n_frames, nfeatures]"
+        n_frames = int(frame_points.shape[0])
+        assert local_kf.dim() == 2 and local_kf.shape[0] == n_frames and local_kf.shape[1] >= 1, "local_kf is [n_frames, max_local_keyframes]"
+        assert point_ids.dim() == 2 and point_ids.shape[0] == n_frames and point_ids.shape[1] >= 1, "point_ids is [n_frames, max_points_per_frame]"
+        max_lk, max_pts = int(local_kf.shape[1]), int(point_ids.shape[1])
+        for x in (frame_points, local_kf, n_local_kf, ref_kf, point_ids, point_offsets, n_local_points):
+            assert x.element_size() == 4 and x.is_contiguous() and not x.dtype.is_floating_point
+        assert n_local_kf.numel() >= n_frames and ref_kf.numel() >= n_frames and n_local_points.numel() >= n_frames
+        assert point_offsets.numel() >= n_frames + 1
+        assert points.is_contiguous() and points.numel() * points.element_size() >= n_frames * max_pts * 80
+        assert occupied.element_size() == 1 and occupied.is_contiguous() and occupied.numel() >= n_frames * nf
+        check(self._lib.ivf_tracker_update_local_map(self._h, C.byref(map_view.c), frame_points.data_ptr(), n_frames, max_lk, max_pts,
+                                                     local_kf.data_ptr(), n_local_kf.data_ptr(), ref_kf.data_ptr(), points.data_ptr(),
+                                                     point_ids.data_ptr(), point_offsets.data_ptr(), n_local_points.data_ptr(),
+                                                     occupied.data_ptr(), stream_ptr))
+
+    def merge_local(self, point_ids, point_offsets, assign, frame_points, stream_ptr=None):
+        """ORBmatcher.cc:124 after search_local(): frame_points[f, i] = point_ids[point_offsets[f] + assign[f, i]] where assign >= 0.
+        point_ids / point_offsets as update_local_map() wrote them; frame_points: torch.int32 [n_frames, nfeatures] in/out.  Asynchronous."""
+        n_frames = frame_points.numel() // self.nfeatures
+        assert frame_points.element_size() == 4 and frame_points.is_contiguous() and frame_points.numel() == n_frames * self.nfeatures
+        assert point_offsets.element_size() == 4 and point_offsets.is_contiguous() and point_offsets.numel() >= n_frames + 1
+        assert point_ids.element_size() == 4 and point_ids.is_contiguous()
+        assert assign.element_size() == 4 and assign.is_contiguous() and assign.numel() >= n_frames * self.nfeatures
+        check(self._lib.ivf_tracker_merge_local(self._h, point_ids.data_ptr(), point_offsets.data_ptr(), assign.data_ptr(), n_frames,
+                                                frame_points.data_ptr(), stream_ptr))
+
+    def points_from_map(self, map_view, frame_points, xw, has_point, quality=None, point_quality=None, stream_ptr=None):
+        """optimize_pose()'s input over ALL the points a frame holds: xw[f, i] = GetWorldPos() of map point frame_points[f, i],
+        has_point = 1 where there is one; quality: torch.float32 [n_frames, nfeatures] or None, the held point's entry of point_quality
+        (torch.float32 [n_points], None = 1).  Asynchronous."""
+        nf = self.nfeatures
+        assert isinstance(map_view, MapView), "map_view is an iv_slam_amd.track.MapView"
+        n_frames = frame_points.numel() // nf
+        assert frame_points.element_size() == 4 and frame_points.is_contiguous() and frame_points.numel() == n_frames * nf
+        assert xw.element_size() == 4 and xw.is_contiguous() and xw.numel() >= n_frames * nf * 3
+        assert has_point.element_size() == 1 and has_point.numel() >= n_frames * nf
+        assert quality is None or (quality.is_contiguous() and quality.element_size() == 4 and quality.numel() >= n_frames * nf)
+        assert point_quality is None or (point_quality.is_contiguous() and point_quality.element_size() == 4 and point_quality.numel() >= map_view.c.n_points)
+        check(self._lib.ivf_tracker_points_from_map(self._h, map_view.c.points, map_view.c.n_points,
+                                                    None if point_quality is None else point_quality.data_ptr(), frame_points.data_ptr(),
+                                                    n_frames, xw.data_ptr(), has_point.data_ptr(),
+                                                    None if quality is None else quality.data_ptr(), stream_ptr))
+
+    def close_local_map(self, map_view, outlier, frame_points, ninliers, only_tracking=False, stereo=True, stream_ptr=None):
+        """The statistics loop of TrackLocalMap (ORB/src/Tracking.cc:1648-1677): ninliers[f] = held points optimize_pose() did not flag
+        (with only_tracking False only those with Observations() > 0); with stereo an outlier's entry of frame_points becomes -1.
+        outlier: torch.uint8 [n_frames, nfeatures]; frame_points: torch.int32 [n_frames, nfeatures] in/out; ninliers: torch.int32
+        [n_frames].  The 30 / 50 decision is the caller's.  Asynchronous."""
+        nf = self.nfeatures
+        assert isinstance(map_view, MapView), "map_view is an iv_slam_amd.track.MapView"
+        n_frames = frame_points.numel() // nf
+        assert frame_points.element_size() == 4 and frame_points.is_contiguous() and frame_points.numel() == n_frames * nf
+        assert outlier.element_size() == 1 and outlier.is_contiguous() and outlier.numel() >= n_frames * nf
+        assert ninliers.element_size() == 4 and ninliers.is_contiguous() and ninliers.numel() >= n_frames
+        check(self._lib.ivf_tracker_close_local_map(self._h, map_view.c.points, map_view.c.n_points, outlier.data_ptr(), n_frames,
+                                                    int(bool(only_tracking)), int(bool(stereo)), frame_points.data_ptr(), ninliers.data_ptr(),
+                                                    stream_ptr))
+
     def solve_pnp(self, records, frames, xw, has_point, draws, poses, inlier, ninliers, max_iterations=300, probability=0.99, min_inliers=10,
                   epsilon=0.5, th2=5.991, iterations=None, hyp_poses=None, hyp_ninliers=None, stream_ptr=None):
         """PnPsolver (ORB/src/PnPsolver.cc) as Tracking::Relocalization runs it (ORB/src/Tracking.cc:2315-2339) for n_frames frames at once:
@@ -297,6 +368,42 @@ class BatchTracker:
                                               None if iterations is None else iterations.data_ptr(),
                                               None if hyp_poses is None else hyp_poses.data_ptr(),
                                               None if hyp_ninliers is None else hyp_ninliers.data_ptr(), stream_ptr))
+
+
+def local_map_lds_keyframes():
+    """update_local_map keeps a frame's vote row in LDS up to this many keyframes and in the handle's scratch beyond: the library's own limit"""
+    return int(_lib.load().ivf_tracker_local_map_lds_keyframes())
+
+
+class MapView:
+    """ivf_map_view (include/ivfront.h) from tensors the caller keeps on the tracker's device: the map UpdateLocalMap walks, as flat
+    tables.  points: torch.uint8 view of LOCAL_POINT_DTYPE records [n_points] (flags bit 0 = isBad(), bit 1 = Observations() > 0);
+    obs_offsets [n_points + 1] / obs_kf: CSR of MapPoint::GetObservations() as keyframe indices; kf_point_offsets [n_keyframes + 1] /
+    kf_points: CSR of KeyFrame::GetMapPointMatches() as map-point indices or -1; kf_neigh [n_keyframes, 10]:
+    GetBestCovisibilityKeyFrames(10), -1 padded; kf_child_offsets [n_keyframes + 1] / kf_children: GetChilds(); kf_parent
+    [n_keyframes]; kf_live: torch.uint8 [n_keyframes] or None (all live); kf_order: torch.int32 [n_keyframes] or None (identity), the
+    order the host's std::map<KeyFrame*, int> iterates the keyframes in.  All index tensors are torch.int32 and contiguous.  The view
+    keeps the tensors alive; an edit of the map (add, erase, SetBadFlag) is an edit of these tensors, or a new view after a resize."""
+
+    def __init__(self, points, obs_offsets, obs_kf, kf_point_offsets, kf_points, kf_neigh, kf_child_offsets, kf_children, kf_parent,
+                 kf_live=None, kf_order=None):
+        n_points, n_kf = obs_offsets.numel() - 1, kf_parent.numel()
+        for x in (obs_offsets, obs_kf, kf_point_offsets, kf_points, kf_neigh, kf_child_offsets, kf_children, kf_parent, kf_order):
+            assert x is None or (x.element_size() == 4 and x.is_contiguous() and not x.dtype.is_floating_point), "index tables are contiguous int32"
+        assert n_points >= 0 and points.is_contiguous() and points.numel() * points.element_size() == n_points * 80, "points / obs_offsets disagree"
+        assert kf_point_offsets.numel() == n_kf + 1 and kf_child_offsets.numel() == n_kf + 1, "offset tables are [n_keyframes + 1]"
+        assert kf_neigh.numel() == n_kf * 10, "kf_neigh is [n_keyframes, 10]"
+        assert kf_live is None or (kf_live.element_size() == 1 and kf_live.is_contiguous() and kf_live.numel() == n_kf)
+        assert kf_order is None or kf_order.numel() == n_kf, "kf_order is [n_keyframes]"
+        self._keep = (points, obs_offsets, obs_kf, kf_point_offsets, kf_points, kf_neigh, kf_child_offsets, kf_children, kf_parent, kf_live, kf_order)
+        c = _lib.MapViewC()
+        for name, x in zip(("points", "obs_offsets", "obs_kf", "kf_point_offsets", "kf_points", "kf_neigh", "kf_child_offsets", "kf_children",
+                            "kf_parent", "kf_live", "kf_order"), self._keep):
+            setattr(c, name, None if x is None or x.numel() == 0 else x.data_ptr())
+        c.n_points, c.n_keyframes = n_points, n_kf
+        c.n_obs, c.n_kf_points, c.n_children = obs_kf.numel(), kf_points.numel(), kf_children.numel()
+        self.c = c
+        self.n_points, self.n_keyframes = n_points, n_kf
 
 
 def pnp_draws(n_frames, max_iterations, seed):
