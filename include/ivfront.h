@@ -841,6 +841,65 @@ int  ivf_tracker_points_from_map(ivf_tracker* t, const ivf_local_point* d_map_po
                                  void* hip_stream);
 int  ivf_tracker_close_local_map(ivf_tracker* t, const ivf_local_point* d_map_points, int n_points, const uint8_t* d_outlier, int n_frames,
                                  int only_tracking, int stereo, int32_t* d_frame_points, int32_t* d_ninliers, void* hip_stream);
+/* ---- LocalMapping::CreateNewMapPoints (ORB/src/LocalMapping.cc:273-525), stereo / RGB-D branch, for n_kf current keyframes at once ----
+ * Keyframe slot k = record d_kf[k] with up to max_neigh neighbours d_neigh[k][r] = GetBestCovisibilityKeyFrames(10) in that order, -1
+ * padded.  Per neighbour, in rank order: the baseline gate (:311-319), ComputeF12 (:609-626), the epipole (ORB/src/ORBmatcher.cc:670-676),
+ * KeyFrame::ComputeBoW reduced to mFeatVec (as ivf_tracker_search_by_bow computes it, at level L - levelsup),
+ * ORBmatcher(0.6, false).SearchForTriangulation(..., false) (ORBmatcher.cc:663-829), and per match :352-497: the parallax decision, the
+ * linear triangulation or Frame::UnprojectStereo, z1 <= 0, z2 <= 0, the reprojection gates (5.991 / 7.8 times mvLevelSigma2), dist == 0
+ * and the scale-consistency gate with ratioFactor = 1.5f * scale_factors[1]; then the new point: MapPoint(x3D, current keyframe),
+ * ComputeDistinctiveDescriptors and UpdateNormalAndDepth for its two observations (ORB/src/MapPoint.cc:247-376) and
+ * SetQualityScore(min(mvKeyQualScore[idx1], mvKeyQualScore[idx2])) (:512-517).  No host read; asynchronous on hip_stream.
+ * Inputs (device): d_records / record_bytes / n_records as every tracker call takes them (keypoints, descriptors, uRight and the depth
+ * behind it, as ivf_tracker_points_from_pairs reads them); d_poses [n_records][12] = Tcw of every record, row-major 3x4; d_has_point
+ * [n_records][nfeatures] = GetMapPoint(i) != NULL on entry, read only; d_key_quality [n_records][nfeatures] (nullable: the quality is 1)
+ * = mvKeyQualScore; d_F12 [n_kf][max_neigh][9] (nullable) replaces the computed fundamental matrix: a host that holds the reference's
+ * own F12 passes it; d_kf_order [n_records] (nullable = identity) = the record indices in the order the host's
+ * std::map<KeyFrame*, size_t> iterates the keyframes (ivf_map_view.kf_order's meaning; a record it does not name comes behind the named
+ * ones, in index order): with two observations both medians of ComputeDistinctiveDescriptors are 0 and the strict `<` keeps the
+ * descriptor of the keyframe that comes first.
+ * Within a keyframe the ranks are serial: a keypoint that received a point from neighbour r is skipped by the search of the ranks behind
+ * it (AddMapPoint, then ORBmatcher.cc:708), one whose match failed a gate stays free.  The call works on a copy of the keyframe's row of
+ * d_has_point.  SLOTS ARE INDEPENDENT: every slot sees d_has_point as on entry, also for a record that is a neighbour in one slot and
+ * current in another; ordering keyframes against each other is the caller's job (separate calls).  Every idx1 searches independently
+ * (vbMatched2 is tested and never set): several may take the same idx2, each gets its own point; a later equal distance replaces the
+ * earlier one (`dist>bestDist`, :744).  CheckNewKeyFrames()' early return does not exist here: a batch runs all ranks.
+ * Arithmetic: cv::Mat products, dot and norm as everywhere in the tracker (double accumulation, one narrowing);
+ * F12 = K1^-T [t12]x R12 K2^-1 in closed form in f64 from the float poses and the handle's intrinsics, narrowed once -- NOT the
+ * reference's float cv::Mat chain, from which it differs by a few ulps (d_F12 feeds the reference's own values); cos(2 atan2(b/2, z)) as
+ * (z^2 - h^2) / (z^2 + h^2) in f64; the triangulation's singular vector from a cyclic one-sided Jacobi in f64 (fixed pair order, the
+ * sweep limit of ivf_tracker_solve_pnp), narrowed to float -- more accurate than cv::SVD on CV_32F, so a match within that difference
+ * of a gate may decide differently than the reference.
+ * Outputs, dense by keypoint of the current keyframe (an idx1 creates at most one point per call): d_new_point [n_kf][nfeatures]
+ * (16-byte aligned; flags = 2; zeros where no point was made), d_new_neigh (the neighbour's rank or -1), d_new_idx2 (or -1),
+ * d_new_order (the point's rank in creation order -- neighbour rank, then idx1 ascending -- the order mlpRecentAddedMapPoints and the
+ * map receive it in, or -1; of the points that share an idx2 the neighbour finally holds the last), d_new_quality (0 where none),
+ * d_n_new [n_kf] = nnew.  Nullable diagnostics [n_kf][max_neigh][nfeatures]: d_matches = vMatchedIndices by idx1, -1 elsewhere;
+ * d_stage = IVF_CREATE_* of every matched idx1 (IVF_CREATE_BASELINE on every keypoint of a neighbour skipped for its baseline).
+ * A d_kf index outside [0, n_records) gives d_n_new = -1; a neighbour index outside it (-1) skips the neighbour.  IVF_E_CAPACITY:
+ * n_kf * max_neigh > max_pairs; IVF_E_INVALID: a null required pointer, max_neigh < 1, levelsup < 0, a vocabulary on another device.
+ * Obeys the handle's one-call-at-a-time rule; shares the feature-vector scratch of ivf_tracker_search_by_bow. */
+#define IVF_CREATE_NONE           0   /* no match */
+#define IVF_CREATE_BASELINE       1   /* neighbour skipped: baseline < mb */
+#define IVF_CREATE_LOW_PARALLAX   2   /* no stereo and very low parallax (:414-415) */
+#define IVF_CREATE_W_ZERO         3   /* :399 */
+#define IVF_CREATE_Z1             4
+#define IVF_CREATE_Z2             5
+#define IVF_CREATE_CHI2_1_MONO    6
+#define IVF_CREATE_CHI2_1_STEREO  7
+#define IVF_CREATE_CHI2_2_MONO    8
+#define IVF_CREATE_CHI2_2_STEREO  9
+#define IVF_CREATE_DIST_ZERO      10
+#define IVF_CREATE_RATIO_LOW      11
+#define IVF_CREATE_RATIO_HIGH     12
+#define IVF_CREATE_BY_SVD         13  /* created: linear triangulation */
+#define IVF_CREATE_BY_STEREO1     14  /* created: UnprojectStereo of the current keyframe */
+#define IVF_CREATE_BY_STEREO2     15  /* created: UnprojectStereo of the neighbour */
+int  ivf_tracker_create_map_points(ivf_tracker* t, const ivf_vocabulary* voc, int levelsup, const uint8_t* d_records, size_t record_bytes,
+                                   int n_records, const int32_t* d_kf, int n_kf, const int32_t* d_neigh, int max_neigh, const float* d_poses,
+                                   const uint8_t* d_has_point, const float* d_key_quality, const float* d_F12, const int32_t* d_kf_order,
+                                   ivf_local_point* d_new_point, int32_t* d_new_neigh, int32_t* d_new_idx2, int32_t* d_new_order,
+                                   float* d_new_quality, int32_t* d_n_new, int32_t* d_matches, uint8_t* d_stage, void* hip_stream);
 /* MapPoint::ComputeDistinctiveDescriptors (ORB/src/MapPoint.cc:247-312): desc = the n observed descriptors (rows of
  * vDescriptors, in mObservations order); *best_index = the row to copy into mDescriptor, *best_median (nullable) its median. */
 int  ivf_distinctive_descriptor(const uint8_t* desc, int n, int* best_index, int* best_median, int device_id);

@@ -144,5 +144,22 @@ DEVINL int sorted_find(const int* s, int n, int v)
 // frame).  nodeKey [slots][nf]: node id per keypoint (-1: stopped word); the feature vector in CSR form: fvNode [slots][nf] ascending,
 // fvStart [slots][nf + 1], fvIdx [slots][nf] ascending inside a node, fvN [slots] nodes.
 struct TrackerBowScratch { int *nodeKey, *fvNode, *fvStart, *fvIdx, *fvN; };
+// slot s of that scratch from its nodeKey row, by one 256-thread workgroup: the n keypoints of the slot's record sorted into std::map
+// order of the nodes with addFeature's push order inside a node (FeatureVector.cpp:31-45).  s_key [key_sort_pad(n)] and part [256] in LDS.
+DEVINL void featvec_of_slot(const TrackerBowScratch& B, int s, int nf, int n, unsigned long long* s_key, int* part, int tid)
+{
+    const int* keyIn = B.nodeKey + (size_t)s * nf;
+    const KeyRuns R = sort_keys_and_runs(s_key, key_sort_pad(n), n, tid, [&](unsigned i) { const int k = keyIn[i]; return k >= 0 ? sort_key(k, i) : kNoKey; }, part);
+    int k = R.k;
+    int* nodeOut = B.fvNode + (size_t)s * nf;
+    int* startOut = B.fvStart + (size_t)s * (nf + 1);
+    int* idxOut = B.fvIdx + (size_t)s * nf;
+    for (int j = R.j0; j < R.j0 + R.per; j++) {
+        if (j >= R.m) break;
+        idxOut[j] = (int)(unsigned)s_key[j];
+        if (R.starts(j)) { nodeOut[k] = (int)R.id(j); startOut[k] = j; k++; }
+    }
+    if (tid == 0) { const int total = R.total(); startOut[total] = R.m; B.fvN[s] = total; }
+}
 
 }  // namespace ivf

@@ -24,10 +24,8 @@ using namespace ivf;
 
 namespace {
 
-constexpr int kSweeps = 30;                                           // cap of the Jacobi sweeps (convergence takes 6..10)
 constexpr int kRefThreads = 256;
 constexpr int kSumCap = 80;                                           // the widest reduction: the 78 sums of MtM's upper triangle
-constexpr double kEps = 0x1p-52;                                      // DBL_EPSILON
 
 struct PnpParams {
     int nf, nRecords;
@@ -86,11 +84,9 @@ DEVINL void jacobi_svd(double* A, int m, int n, double* V, double* w, int* ord, 
             for (int q = p + 1; q < n; q++) {
                 double a = 0.0, b = 0.0, g = 0.0;
                 for (int k = 0; k < m; k++) { const double x = A[k * n + p], y = A[k * n + q]; a = a + x * x; b = b + y * y; g = g + x * y; }
-                if (!(fabs(g) > kEps * sqrt(a * b))) continue;         // orthogonal already (or NaN): the same answer in every lane
+                double c, s;
+                if (!jacobi_rotation(a, b, g, c, s)) continue;         // orthogonal already (or NaN): the same answer in every lane
                 rotated = true;
-                const double zeta = (b - a) / (2.0 * g);
-                const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + tn * tn), s = c * tn;
                 double x = 0.0, y = 0.0;
                 if (row) { x = row[p]; y = row[q]; }
                 __syncthreads();                                       // every lane has read both columns

@@ -74,6 +74,12 @@ DEVINL void first_min_in_window(const GridGeom G, const ivf_keypoint* __restrict
               [&](bool ok, int i2, int d) { first_min_in_list(ok, d, i2, lane, admits, bestDist, bestIdx); });
 }
 
+// ---- the LAST minimum of a list of up to 4096 candidates, the other rule: SearchForTriangulation's `dist>bestDist` (ORBmatcher.cc:744)
+// lets a later equal distance replace the earlier one, so the candidate kept is the minimum of (distance << 12 | 4095 - position) over
+// the candidates that pass every gate; a lane folds its strides with min(), the wave with wave_min_u32
+DEVINL unsigned last_min_key(bool ok, int dist, int pos) { return ok ? ((unsigned)dist << 12) | (unsigned)(4095 - pos) : 0xffffffffu; }
+DEVINL int last_min_position(unsigned best) { return 4095 - (int)(best & 4095u); }
+
 // ---- the greedy walk over the lists of queries 0 .. n - 1 (C [n] counts, Lp [n][kListCap] entries), in order, by one wave:
 // body(i, cnt, ent, aux) runs for every query with cnt != 0; ent = this lane's entry of the list, aux() = loadAux(i), one 4-byte word
 // per query that travels with the lists (a call, so that a body which needs it on one path only pays for it there).  The next group of

@@ -1,6 +1,7 @@
 // ivf_solve.h -- what the two solvers of the batched tracker share, ivf_pose.hip (PoseOptimization) and ivf_pnp.hip (PnPsolver), and
-// the searches do not need: the fixed-tree sums, the ordered compaction, a frame's pointer set, the octave clamp, the pose I/O and
-// the level sigma2 table.
+// the searches do not need: the fixed-tree sums, the ordered compaction, a frame's pointer set, the octave clamp, the pose I/O, the
+// Jacobi rotation and the level sigma2 table.  ivf_track_create.hip (CreateNewMapPoints) takes the compaction, the clamp, the rotation
+// and the table.
 #pragma once
 #include "ivf_tracker.h"
 
@@ -78,6 +79,21 @@ DEVINL void load_hyp(const double* hp, double* R, double* t)
         for (int j = 0; j < 3; j++) R[3 * i + j] = hp[4 * i + j];
         t[i] = hp[4 * i + 3];
     }
+}
+
+// ---- the cyclic one-sided Jacobi SVD both of its forms share: ivf_pnp.hip's (the matrix in LDS, a rotation spread over lanes) and
+// ivf_track_create.hip's (a 4x4 per lane in registers).  The pairs (p, q), p < q, are visited in ascending order, at most kSweeps
+// sweeps; a sweep that turns nothing ends the iteration.
+constexpr int kSweeps = 30;                                           // cap of the Jacobi sweeps (convergence takes 6..10)
+constexpr double kEps = 0x1p-52;                                      // DBL_EPSILON
+// the rotation that makes columns p and q orthogonal, from a = |p|^2, b = |q|^2, g = p.q: false when they are already (or on a NaN)
+DEVINL bool jacobi_rotation(double a, double b, double g, double& c, double& s)
+{
+    if (!(fabs(g) > kEps * sqrt(a * b))) return false;
+    const double zeta = (b - a) / (2.0 * g);
+    const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+    c = 1.0 / sqrt(1.0 + tn * tn); s = c * tn;
+    return true;
 }
 
 // mvLevelSigma2 (ORBextractor.cc:419-431) of the handle's scale factors; mvInvLevelSigma2 is 1.0f / s2[l]

@@ -58,20 +58,7 @@ __global__ __launch_bounds__(256) void k_bow_featvec(BowParams P, const uint8_t*
     const int s = blockIdx.x, tid = threadIdx.x;
     const uint8_t* rec = slot_record(P, records, pairs, select, s);
     if (!rec) return;
-    const int n = rec_count(rec, P.nf);
-    const int* keyIn = B.nodeKey + (size_t)s * P.nf;
-    // std::map order of the nodes with addFeature's push order inside a node (FeatureVector.cpp:31-45)
-    const KeyRuns R = sort_keys_and_runs(s_key, key_sort_pad(n), n, tid, [&](unsigned i) { const int k = keyIn[i]; return k >= 0 ? sort_key(k, i) : kNoKey; }, part);
-    int k = R.k;
-    int* nodeOut = B.fvNode + (size_t)s * P.nf;
-    int* startOut = B.fvStart + (size_t)s * (P.nf + 1);
-    int* idxOut = B.fvIdx + (size_t)s * P.nf;
-    for (int j = R.j0; j < R.j0 + R.per; j++) {
-        if (j >= R.m) break;
-        idxOut[j] = (int)(unsigned)s_key[j];
-        if (R.starts(j)) { nodeOut[k] = (int)R.id(j); startOut[k] = j; k++; }
-    }
-    if (tid == 0) { const int total = R.total(); startOut[total] = R.m; B.fvN[s] = total; }
+    featvec_of_slot(B, s, P.nf, rec_count(rec, P.nf), s_key, part, tid);
 }
 
 __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,

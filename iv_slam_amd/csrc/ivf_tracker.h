@@ -1,9 +1,10 @@
-// ivf_tracker.h -- the batched tracker handle and what its nine translation units share (not part of the public C-ABI):
+// ivf_tracker.h -- the batched tracker handle and what its ten translation units share (not part of the public C-ABI):
 // ivf_track.hip (the handle's life cycle and the TrackWithMotionModel search), ivf_track_local.hip (SearchLocalPoints),
 // ivf_track_bow.hip (TrackReferenceKeyFrame), ivf_track_reloc.hip (Relocalization's SearchByProjection and the set bookkeeping around
 // it), ivf_track_db.hip (Relocalization's first two lines: mBowVec and KeyFrameDatabase::DetectRelocalizationCandidates),
 // ivf_track_map.hip (UpdateLocalMap: the local keyframes and points of a frame from a device-resident map),
-// ivf_track_points.hip (the points a search hands to a solver and the tail of TrackLocalMap), ivf_pose.hip
+// ivf_track_points.hip (the points a search hands to a solver and the tail of TrackLocalMap), ivf_track_create.hip
+// (LocalMapping::CreateNewMapPoints: new map points for a batch of keyframes), ivf_pose.hip
 // (PoseOptimization) and ivf_pnp.hip (Relocalization's PnPsolver).  One definition of struct ivf_tracker, one host statement of the
 // camera and record constants (TrackParams), and the device pieces searches and solvers both read (the query record, the pose algebra,
 // PredictScale, UpdateQualityScores); what only the projection searches repeat is ivf_search.h's, what only the two solvers repeat

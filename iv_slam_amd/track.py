@@ -296,6 +296,45 @@ class BatchTracker:
                                                      point_ids.data_ptr(), point_offsets.data_ptr(), n_local_points.data_ptr(),
                                                      occupied.data_ptr(), stream_ptr))
 
+    def create_map_points(self, vocabulary, records, kf, neigh, poses, has_point, new_point, new_neigh, new_idx2, new_order, new_quality, n_new,
+                          levelsup=4, key_quality=None, F12=None, kf_order=None, matches=None, stage=None, stream_ptr=None):
+        """LocalMapping::CreateNewMapPoints (ORB/src/LocalMapping.cc:273-525), stereo / RGB-D branch, for n_kf keyframes at once: per
+        neighbour in rank order the baseline gate, ComputeF12 (:609-626), ORBmatcher(0.6, false).SearchForTriangulation
+        (ORB/src/ORBmatcher.cc:663-829) on feature vectors computed in the call, the triangulation and its gates (:352-497), and the new
+        point's record (ORB/src/MapPoint.cc:247-376, min of the two key qualities :512-517).  vocabulary: an ORBVocabulary on the
+        tracker's device; kf: torch.int32 [n_kf] record indices; neigh: torch.int32 [n_kf, max_neigh] (max_neigh = neigh.shape[1]),
+        GetBestCovisibilityKeyFrames(10) in order, -1 padded, n_kf * max_neigh <= max_pairs; poses: torch.float32 [n_records, 12];
+        has_point: torch.uint8 [n_records, nfeatures], read only; key_quality: torch.float32 [n_records, nfeatures] or None (= 1);
+        F12: torch.float32 [n_kf, max_neigh, 9] or None (computed); kf_order: torch.int32 [n_records] or None (identity).  Outputs by
+        keypoint of the current keyframe: new_point: torch.uint8 view of LOCAL_POINT_DTYPE records [n_kf, nfeatures]; new_neigh,
+        new_idx2, new_order: torch.int32 [n_kf, nfeatures]; new_quality: torch.float32 [n_kf, nfeatures]; n_new: torch.int32 [n_kf];
+        matches: torch.int32 and stage: torch.uint8 [n_kf, max_neigh, nfeatures] or None.  Slots are independent: each sees has_point
+        as on entry.  Asynchronous on the given stream, no host read."""
+        nf = self.nfeatures
+        n_rec = records.numel() // self.record_bytes
+        assert neigh.dim() == 2 and neigh.shape[1] >= 1, "neigh is [n_kf, max_neigh]"
+        n_kf, max_neigh = int(neigh.shape[0]), int(neigh.shape[1])
+        for x in (kf, neigh, new_neigh, new_idx2, new_order, n_new, kf_order, matches):
+            assert x is None or (x.element_size() == 4 and x.is_contiguous() and not x.dtype.is_floating_point)
+        assert kf.numel() == n_kf and n_new.numel() >= n_kf
+        assert poses.is_contiguous() and poses.element_size() == 4 and poses.numel() == n_rec * 12, "poses are per RECORD: [n_records, 12]"
+        assert has_point.element_size() == 1 and has_point.is_contiguous() and has_point.numel() >= n_rec * nf
+        assert key_quality is None or (key_quality.is_contiguous() and key_quality.element_size() == 4 and key_quality.numel() >= n_rec * nf)
+        assert F12 is None or (F12.is_contiguous() and F12.element_size() == 4 and F12.numel() == n_kf * max_neigh * 9), "F12 is [n_kf, max_neigh, 9]"
+        assert kf_order is None or kf_order.numel() == n_rec, "kf_order is [n_records]"
+        assert new_point.is_contiguous() and new_point.numel() * new_point.element_size() >= n_kf * nf * 80
+        for x in (new_neigh, new_idx2, new_order):
+            assert x.numel() >= n_kf * nf
+        assert new_quality.is_contiguous() and new_quality.element_size() == 4 and new_quality.numel() >= n_kf * nf
+        assert matches is None or matches.numel() >= n_kf * max_neigh * nf
+        assert stage is None or (stage.element_size() == 1 and stage.is_contiguous() and stage.numel() >= n_kf * max_neigh * nf)
+        opt = lambda x: None if x is None else x.data_ptr()
+        check(self._lib.ivf_tracker_create_map_points(self._h, vocabulary._h, int(levelsup), records.data_ptr(), self.record_bytes, n_rec,
+                                                      kf.data_ptr(), n_kf, neigh.data_ptr(), max_neigh, poses.data_ptr(), has_point.data_ptr(),
+                                                      opt(key_quality), opt(F12), opt(kf_order), new_point.data_ptr(), new_neigh.data_ptr(),
+                                                      new_idx2.data_ptr(), new_order.data_ptr(), new_quality.data_ptr(), n_new.data_ptr(),
+                                                      opt(matches), opt(stage), stream_ptr))
+
     def merge_local(self, point_ids, point_offsets, assign, frame_points, stream_ptr=None):
         """ORBmatcher.cc:124 after search_local(): frame_points[f, i] = point_ids[point_offsets[f] + assign[f, i]] where assign >= 0.
         point_ids / point_offsets as update_local_map() wrote them; frame_points: torch.int32 [n_frames, nfeatures] in/out.  Asynchronous."""
