@@ -701,6 +701,50 @@ int  ivf_tracker_solve_pnp(ivf_tracker* t, const uint8_t* d_records, size_t reco
                            const float* d_xw, const uint8_t* d_has_point, const uint32_t* d_draws, int max_iterations, double probability,
                            int min_inliers, float epsilon, float th2, float* d_poses, uint8_t* d_inlier, int32_t* d_ninliers,
                            int32_t* d_iterations, float* d_hyp_poses, int32_t* d_hyp_ninliers, void* hip_stream);
+/* Batched Sim3Solver (ORB/src/Sim3Solver.cc), the step of LoopClosing::ComputeSim3 (ORB/src/LoopClosing.cc:279-306) between
+ * SearchByBoW(mpCurrentKF, pKF, vvpMapPointMatches[i]) and SearchBySim3: Horn's closed form on three 3D-3D correspondences inside a
+ * RANSAC loop, for pair p = (KF1 = current keyframe record d_pairs[p][0], KF2 = candidate record d_pairs[p][1]).  d_select as in
+ * ivf_tracker_search_by_bow; d_poses [n_records][12] = Tcw of every record (row-major 3x4) as ivf_tracker_create_map_points takes it;
+ * d_kf_xw [n_records][nfeatures][3] = GetWorldPos() as ivf_tracker_points_from_keyframe takes it; d_point_flags
+ * [n_records][nfeatures], bit 0 = the keypoint holds a live map point; d_match12 [n_pairs][nfeatures] = vpMatched12 as indices: the
+ * KF2 keypoint whose point KF1 keypoint i1 is matched to, or -1 (what ivf_search_by_bow_keyframes returns).
+ * The constructor (Sim3Solver.cc:40-115): for i1 ascending below KF1's count a correspondence is collected when d_match12[p][i1] = i2
+ * >= 0, i2 is below KF2's count and both keypoints hold a live point (:67-76); GetIndexInKeyFrame (:78-82) is taken to be i1 / i2, the
+ * keypoint that holds the point.  mvX3Dc = Rcw * Xw + tcw per side (:97-101); mvnMaxError = 9.210 * mvLevelSigma2[octave] computed in
+ * double and TRUNCATED to an integer, a vector<size_t> (:87-91): 9 at level 0, not 9.21; FromCameraToImage (:408-426) divides by z
+ * without a test of its sign.  SetRansacParameters (:117-141) with (probability, min_inliers, max_iterations; LoopClosing.cc:280 passes
+ * 0.99, 20, 300): epsilon = (float)min_inliers / N, mRansacMaxIts = clamp(ceil(log(1 - p) / log(1 - epsilon^3)), 1, max_iterations),
+ * 1 when min_inliers == N.  iterate (:143-210): N < min_inliers returns nothing (:149-153; so does N < 3, where the reference has no
+ * sample to draw); per iteration three DUtils::Random::RandomInt draws with the swap-with-back removal (:166-180), ComputeSim3
+ * (:229-340), CheckInliers (:343-367: both reprojections, err = dist.dot(dist) compared as float against the integer bound); the best
+ * is replaced on mnInliersi >= mnBestInliers (:186) and the call succeeds on mnInliersi > min_inliers, strictly (:195).  Only a success
+ * returns a transform: the best failed hypothesis is not returned (:209).
+ * One call runs from the state on entry to the first success or to mRansacMaxIts: the loop condition of :161 is an AND, and
+ * LoopClosing.cc:291-346 goes on calling iterate(5, ...) on a solver whose OptimizeSim3 failed, so d_state [n_pairs][2] =
+ * {mnIterations, mnBestInliers} is in/out (NULL: {0, 0}, nothing written back); a second call with the state the first one left
+ * continues where the reference's next iterate would, with the draws of those iterations.  d_iterations lets a caller rebuild the
+ * round-robin order over candidates: the winner is the smallest ceil(iterations / 5), then candidate order.
+ * d_draws [n_pairs][max_iterations][3]: the values rand() returned for the three samples of iteration it = mnIterations before its
+ * increment (bit 31 is ignored); RandomInt is Thirdparty/DBoW2/DUtils/Random.cpp:47-50.  max_iterations in [1, 300].
+ * Arithmetic: cv::Mat CV_32F products, dot, norm and reduce accumulate in double and narrow once; M and N are float
+ * matrices (:246-268); cv::eigen is a cyclic two-sided Jacobi in f64 with a fixed pair order and sweep cap, the vector of the largest
+ * eigenvalue narrowed to float (its sign is arbitrary: q and -q give one R); atan2, norm and cv::Rodrigues (:281-287) in double,
+ * narrowed once; ms12i = (float)(nom / den) (:297-311), 1.0f with fix_scale (:314); mT21i as :333-339 form it.  A degenerate sample
+ * whose imaginary part vanishes gives NaN (:283), hence no inlier.
+ * Outputs: d_sim3 [n_pairs][16] = mR12i (9, row-major), mt12i (3), ms12i, 3 zeros, written only on success; d_inlier
+ * [n_pairs][nfeatures] = vbInliers by i1, cleared for every written pair; d_ninliers [n_pairs] = nInliers, 0 = cv::Mat(), -1 = a record
+ * index outside [0, n_records), -2 = not selected: nothing else of such a pair is written; d_iterations [n_pairs] (nullable) =
+ * mnIterations on return; d_hyp_sim3 [n_pairs][max_iterations][16] and d_hyp_ninliers [n_pairs][max_iterations] (nullable) = the
+ * transform and mnInliersi of every iteration from mnIterations on entry to mRansacMaxIts (the hypotheses are independent and computed at
+ * once, also those behind the success), the others untouched.  IVF_E_INVALID: a null required pointer,
+ * max_iterations outside [1, 300], probability outside (0, 1), min_inliers < 0, n_pairs > max_pairs.  Every loop has a compile-time
+ * bound: NaN input cannot hang the call.  Two runs are bit-identical.  Asynchronous on hip_stream, no host synchronisation; the
+ * scratch is allocated at the first call for max_pairs pairs and obeys the handle's one-call-at-a-time rule. */
+int  ivf_tracker_solve_sim3(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_pairs, int n_pairs,
+                            const int32_t* d_select, const float* d_poses, const float* d_kf_xw, const uint8_t* d_point_flags,
+                            const int32_t* d_match12, const uint32_t* d_draws, int max_iterations, double probability, int min_inliers,
+                            int fix_scale, int32_t* d_state, float* d_sim3, uint8_t* d_inlier, int32_t* d_ninliers, int32_t* d_iterations,
+                            float* d_hyp_sim3, int32_t* d_hyp_ninliers, void* hip_stream);
 /* The first two lines of Tracking::Relocalization (ORB/src/Tracking.cc:2274-2285), on the device: with them the chain runs from a lost
  * frame's gather record to its restart pose without the host reading anything.
  *

@@ -1,7 +1,7 @@
 // ivf_solve.h -- what the two solvers of the batched tracker share, ivf_pose.hip (PoseOptimization) and ivf_pnp.hip (PnPsolver), and
 // the searches do not need: the fixed-tree sums, the ordered compaction, a frame's pointer set, the octave clamp, the pose I/O, the
 // Jacobi rotation and the level sigma2 table.  ivf_track_create.hip (CreateNewMapPoints) takes the compaction, the clamp, the rotation
-// and the table.
+// and the table; ivf_sim3.hip (Sim3Solver) the compaction, the clamp, the sweep cap and the table.
 #pragma once
 #include "ivf_tracker.h"
 

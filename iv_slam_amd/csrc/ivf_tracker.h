@@ -1,13 +1,13 @@
-// ivf_tracker.h -- the batched tracker handle and what its ten translation units share (not part of the public C-ABI):
+// ivf_tracker.h -- the batched tracker handle and what its eleven translation units share (not part of the public C-ABI):
 // ivf_track.hip (the handle's life cycle and the TrackWithMotionModel search), ivf_track_local.hip (SearchLocalPoints),
 // ivf_track_bow.hip (TrackReferenceKeyFrame), ivf_track_reloc.hip (Relocalization's SearchByProjection and the set bookkeeping around
 // it), ivf_track_db.hip (Relocalization's first two lines: mBowVec and KeyFrameDatabase::DetectRelocalizationCandidates),
 // ivf_track_map.hip (UpdateLocalMap: the local keyframes and points of a frame from a device-resident map),
 // ivf_track_points.hip (the points a search hands to a solver and the tail of TrackLocalMap), ivf_track_create.hip
 // (LocalMapping::CreateNewMapPoints: new map points for a batch of keyframes), ivf_pose.hip
-// (PoseOptimization) and ivf_pnp.hip (Relocalization's PnPsolver).  One definition of struct ivf_tracker, one host statement of the
+// (PoseOptimization), ivf_pnp.hip (Relocalization's PnPsolver) and ivf_sim3.hip (loop closing's Sim3Solver).  One definition of struct ivf_tracker, one host statement of the
 // camera and record constants (TrackParams), and the device pieces searches and solvers both read (the query record, the pose algebra,
-// PredictScale, UpdateQualityScores); what only the projection searches repeat is ivf_search.h's, what only the two solvers repeat
+// PredictScale, UpdateQualityScores); what only the projection searches repeat is ivf_search.h's, what only the solvers repeat
 // ivf_solve.h's, what the BoW units (ivf_track_bow.hip, ivf_track_db.hip and the per-call transform) repeat ivf_bow.h's.
 #pragma once
 #include "ivf_bow.h"
@@ -19,11 +19,17 @@ constexpr int kListCap = 64;                      // candidates listed per query
 constexpr int kPrefetch = 16;                     // queries whose lists are in registers ahead of the greedy walk
 constexpr int kMaxTrackFeatures = 4096;           // LDS state of k_track_greedy: 20 B per keypoint
 constexpr int kPnpMaxIterations = 300;            // ivf_tracker_solve_pnp: the cap of max_iterations (Tracking.cc:2317 passes 300)
+constexpr int kSim3MaxIterations = 300;           // ivf_tracker_solve_sim3: the cap of max_iterations (LoopClosing.cc:280 passes 300)
 
 // The handle's scratch of ivf_tracker_solve_pnp (ivf_pnp.hip), allocated at its first call for max_pairs frames: the compacted
 // correspondences [max_pairs][nfeatures] (32 B each), per frame {N, mRansacMinInliers, mRansacMaxIts}, and the f64 pose and inlier count
 // of every hypothesis [max_pairs][kPnpMaxIterations]
 struct PnpScratch { void* corr; void* head; double* hypPose; int* hypN; };
+
+// The handle's scratch of ivf_tracker_solve_sim3 (ivf_sim3.hip), allocated at its first call for max_pairs pairs: the compacted
+// correspondences [max_pairs][nfeatures] (48 B each) and their KF1 keypoint, per pair {N, mRansacMaxIts, mnIterations and mnBestInliers on
+// entry}, and (mR12i, mt12i, ms12i) as 16 floats and the inlier count of every hypothesis [max_pairs][kSim3MaxIterations]
+struct Sim3Scratch { void* corr; unsigned short* idx; void* head; float* hyp; int* hypN; };
 
 // The handle's scratch of ivf_tracker_reloc_candidates (ivf_track_db.hip), grown on demand to cap >= n_frames * n_keyframes cells and
 // frameCap >= n_frames: per (frame, keyframe) mnRelocWords, the smallest shared word, this query's score, accScore, pBestKF, the place
@@ -154,6 +160,7 @@ struct ivf_tracker {
     ivf::Query* dQ = nullptr; float* dLRad = nullptr; int* dCount = nullptr; unsigned* dLists = nullptr; int queryCap = 0;
     ivf::TrackerBowScratch bow{nullptr, nullptr, nullptr, nullptr, nullptr};   // ivf_tracker_search_by_bow: [2 * max_pairs] slots
     ivf::PnpScratch pnp{nullptr, nullptr, nullptr, nullptr};
+    ivf::Sim3Scratch sim3{nullptr, nullptr, nullptr, nullptr, nullptr};
     ivf::DbScratch db{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
     ivf::MapScratch map{nullptr, nullptr, 0, 0};
     size_t ldsBytes = 0;

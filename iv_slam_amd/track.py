@@ -408,6 +408,47 @@ class BatchTracker:
                                               None if hyp_poses is None else hyp_poses.data_ptr(),
                                               None if hyp_ninliers is None else hyp_ninliers.data_ptr(), stream_ptr))
 
+    def solve_sim3(self, records, pairs, poses, kf_xw, point_flags, match12, draws, sim3, inlier, ninliers, max_iterations=300, probability=0.99,
+                   min_inliers=20, fix_scale=True, select=None, state=None, iterations=None, hyp_sim3=None, hyp_ninliers=None, stream_ptr=None):
+        """Sim3Solver (ORB/src/Sim3Solver.cc) as LoopClosing::ComputeSim3 runs it (ORB/src/LoopClosing.cc:279-306) for n_pairs (current
+        keyframe, candidate) record pairs at once: Horn's closed form on three point pairs inside RANSAC, from the state on entry to the
+        first success or to mRansacMaxIts.  pairs: torch.int32 [n_pairs, 2] = (KF1, KF2) record indices; poses: torch.float32
+        [n_records, 12] (Tcw); kf_xw: torch.float32 [n_records, nfeatures, 3] as points_from_keyframe() takes it; point_flags: torch.uint8
+        [n_records, nfeatures], bit 0 = the keypoint holds a live map point; match12: torch.int32 [n_pairs, nfeatures] = the KF2 keypoint
+        matched to KF1 keypoint i1 or -1 (vpMatched12); draws: torch.uint32-sized [n_pairs, max_iterations, 3], the rand() values of the
+        three samples of every iteration (sim3_draws()); probability, min_inliers, max_iterations: SetRansacParameters' (0.99, 20, 300 at
+        LoopClosing.cc:280), max_iterations 1..300; fix_scale: mbFixScale (true for stereo / RGB-D); select: torch.int32 [n_pairs] or None,
+        0 leaves a pair out (ninliers -2); state: torch.int32 [n_pairs, 2] = {mnIterations, mnBestInliers} in/out or None ({0, 0}): a second
+        call with the state of the first continues where the reference's next iterate() would.  sim3: torch.float32 [n_pairs, 16] = R12
+        (9), t12 (3), s12, 3 zeros, written only on success; inlier: torch.uint8 [n_pairs, nfeatures] by i1 (vbInliers); ninliers:
+        torch.int32 [n_pairs] (0: no transform, -1: bad record index, -2: not selected); iterations: torch.int32 [n_pairs] or None
+        (mnIterations on return); hyp_sim3: torch.float32 [n_pairs, max_iterations, 16] and hyp_ninliers: torch.int32
+        [n_pairs, max_iterations] or None: every hypothesis from the state's iteration to mRansacMaxIts.  (s12 R12, t12) is what ivf_search_by_sim3 takes next.
+        Asynchronous on the given stream."""
+        n_rec = records.numel() // self.record_bytes
+        n_pairs = pairs.shape[0]
+        nf = self.nfeatures
+        mi = int(max_iterations)
+        for x in (pairs, match12, ninliers, select, state, iterations, hyp_ninliers):
+            assert x is None or (x.element_size() == 4 and x.is_contiguous() and not x.dtype.is_floating_point)
+        assert poses.is_contiguous() and poses.element_size() == 4 and poses.numel() == n_rec * 12, "poses are per RECORD: [n_records, 12]"
+        assert kf_xw.is_contiguous() and kf_xw.element_size() == 4 and kf_xw.numel() == n_rec * nf * 3, "kf_xw is [n_records, nfeatures, 3]"
+        assert point_flags.element_size() == 1 and point_flags.is_contiguous() and point_flags.numel() >= n_rec * nf
+        assert match12.numel() >= n_pairs * nf and ninliers.numel() >= n_pairs
+        assert draws.is_contiguous() and draws.element_size() == 4 and draws.numel() >= n_pairs * mi * 3, "draws are [n_pairs, max_iterations, 3]"
+        assert sim3.is_contiguous() and sim3.element_size() == 4 and sim3.numel() == n_pairs * 16, "sim3 is [n_pairs, 16]"
+        assert inlier.element_size() == 1 and inlier.is_contiguous() and inlier.numel() >= n_pairs * nf
+        assert select is None or select.numel() >= n_pairs
+        assert state is None or state.numel() == n_pairs * 2, "state is [n_pairs, 2]"
+        assert iterations is None or iterations.numel() >= n_pairs
+        assert hyp_sim3 is None or (hyp_sim3.is_contiguous() and hyp_sim3.element_size() == 4 and hyp_sim3.numel() >= n_pairs * mi * 16)
+        assert hyp_ninliers is None or hyp_ninliers.numel() >= n_pairs * mi
+        opt = lambda x: None if x is None else x.data_ptr()
+        check(self._lib.ivf_tracker_solve_sim3(self._h, records.data_ptr(), self.record_bytes, n_rec, pairs.data_ptr(), n_pairs, opt(select),
+                                               poses.data_ptr(), kf_xw.data_ptr(), point_flags.data_ptr(), match12.data_ptr(), draws.data_ptr(), mi,
+                                               float(probability), int(min_inliers), int(bool(fix_scale)), opt(state), sim3.data_ptr(),
+                                               inlier.data_ptr(), ninliers.data_ptr(), opt(iterations), opt(hyp_sim3), opt(hyp_ninliers), stream_ptr))
+
 
 def local_map_lds_keyframes():
     """update_local_map keeps a frame's vote row in LDS up to this many keyframes and in the handle's scratch beyond: the library's own limit"""
@@ -449,3 +490,9 @@ def pnp_draws(n_frames, max_iterations, seed):
     """The sampling input of BatchTracker.solve_pnp: uint32 [n_frames, max_iterations, 4] values in [0, RAND_MAX] from numpy's generator
     (a host that wants the reference's own stream passes glibc rand() values instead)."""
     return np.random.default_rng(seed).integers(0, 2 ** 31, size=(int(n_frames), int(max_iterations), 4), dtype=np.uint32)
+
+
+def sim3_draws(n_pairs, max_iterations, seed):
+    """The sampling input of BatchTracker.solve_sim3: uint32 [n_pairs, max_iterations, 3] values in [0, RAND_MAX] from numpy's generator
+    (a host that wants the reference's own stream passes glibc rand() values instead)."""
+    return np.random.default_rng(seed).integers(0, 2 ** 31, size=(int(n_pairs), int(max_iterations), 3), dtype=np.uint32)
