@@ -669,6 +669,13 @@ int  ivf_tracker_search_reloc(ivf_tracker* t, const uint8_t* d_records, size_t r
  * n_frames <= max_pairs.  Asynchronous on hip_stream. */
 int  ivf_tracker_filter_assign(ivf_tracker* t, int32_t* d_assign, int n_frames, const uint8_t* d_mask, int keep_when_set, uint8_t* d_found,
                                void* hip_stream);
+/* The draws of the two RANSAC solvers below, ivf_tracker_solve_pnp (K = 4 points per sample) and ivf_tracker_solve_sim3 (K = 3).
+ * d_draws [n][max_iterations][K], n = n_frames / n_pairs, max_iterations in [1, 300]: the values rand() returned for the K samples of
+ * iteration it = mnIterations before its increment, each in [0, RAND_MAX = 2^31 - 1]; bit 31 is ignored.  The call applies the
+ * reference's sampling to them: vAvailableIndices = mvAllIndices (0 .. N - 1), then K times randi = DUtils::Random::RandomInt(0, size - 1)
+ * = (int)((double)r / 2^31 * size) (Thirdparty/DBoW2/DUtils/Random.cpp:47-50), sample vAvailableIndices[randi], overwrite that position
+ * with the back and drop the back.  The sampling is therefore the caller's: reproducible (iv_slam_amd.track.ransac_draws), or glibc's
+ * stream to follow the reference exactly. */
 /* Batched PnPsolver (ORB/src/PnPsolver.cc), the step of Tracking::Relocalization (ORB/src/Tracking.cc:2272-2421) between
  * SearchByBoW(pKF, mCurrentFrame, ...) and PoseOptimization: EPnP inside a RANSAC loop, in double as the reference runs it, for frame
  * slot f = record d_frames[f].  The correspondences are those the constructor collects (PnPsolver.cc:71-114): mvKeysUn[i] and
@@ -685,9 +692,7 @@ int  ivf_tracker_filter_assign(ivf_tracker* t, int32_t* d_assign, int n_frames, 
  * float / double mix.  cvSVD, cvInvert and cvSolve(CV_SVD) are a cyclic Jacobi SVD with a fixed pair order and sweep cap: a 4-point
  * hypothesis leaves a four-dimensional null space whose basis rounding chooses, so single hypotheses are not comparable between
  * implementations; Refine's pose is.
- * d_draws [n_frames][max_iterations][4]: the values rand() returned for the four samples of every iteration (bit 31 is ignored); the
- * call applies DUtils::Random::RandomInt (Thirdparty/DBoW2/DUtils/Random.cpp:47-50) and the swap-with-back removal of :192-205.  The
- * sampling is therefore the caller's: reproducible, or glibc's stream to follow the reference exactly.  max_iterations in [1, 300].
+ * d_draws [n_frames][max_iterations][4]: the draws contract above with K = 4, the sampling of :192-205.
  * Outputs: d_poses [n_frames][12] (row-major 3x4, the f64 mRi / mti narrowed to float, :221-227 / :298-304) is written only where a
  * pose is returned; d_inlier [n_frames][nfeatures] = vbInliers by keypoint; d_ninliers [n_frames] = nInliers, 0 = cv::Mat() (also for
  * N < mRansacMinInliers, :177-181), -1 = record index outside [0, n_records): nothing else of that frame is written;
@@ -724,8 +729,7 @@ int  ivf_tracker_solve_pnp(ivf_tracker* t, const uint8_t* d_records, size_t reco
  * {mnIterations, mnBestInliers} is in/out (NULL: {0, 0}, nothing written back); a second call with the state the first one left
  * continues where the reference's next iterate would, with the draws of those iterations.  d_iterations lets a caller rebuild the
  * round-robin order over candidates: the winner is the smallest ceil(iterations / 5), then candidate order.
- * d_draws [n_pairs][max_iterations][3]: the values rand() returned for the three samples of iteration it = mnIterations before its
- * increment (bit 31 is ignored); RandomInt is Thirdparty/DBoW2/DUtils/Random.cpp:47-50.  max_iterations in [1, 300].
+ * d_draws [n_pairs][max_iterations][3]: the draws contract above (before ivf_tracker_solve_pnp) with K = 3, the sampling of :166-180.
  * Arithmetic: cv::Mat CV_32F products, dot, norm and reduce accumulate in double and narrow once; M and N are float
  * matrices (:246-268); cv::eigen is a cyclic two-sided Jacobi in f64 with a fixed pair order and sweep cap, the vector of the largest
  * eigenvalue narrowed to float (its sign is arbitrary: q and -q give one R); atan2, norm and cv::Rodrigues (:281-287) in double,

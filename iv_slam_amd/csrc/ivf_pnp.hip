@@ -17,7 +17,8 @@
 // compute_pose is one text for both sizes (template on the thread count).  The sums over points go through xor-butterflies in the wave and
 // through LDS in wave order: the tree is fixed, two runs are bit-identical.  The 12x12 MtM, its vectors and every small matrix live in
 // LDS; a Jacobi rotation is spread over lanes (one matrix row each).  Every loop has a compile-time bound: NaN cannot spin a kernel.
-// The sums, the ordered compaction, the frame's pointer set and the pose I/O are ivf_solve.h's, shared with ivf_pose.hip.
+// The sums, the ordered compaction, the frame's pointer set and the pose I/O are ivf_solve.h's, shared with ivf_pose.hip; so are the
+// sampler and the iteration count, shared with ivf_sim3.hip (their cap, argument checks and scratch allocation: ivf_tracker.h).
 #include "ivf_solve.h"
 
 using namespace ivf;
@@ -512,13 +513,7 @@ __global__ __launch_bounds__(256) void k_pnp_prepare(PnpParams P, const uint8_t*
         int its = 0;
         if (N >= nMin) {                                               // else :177-181: no pose, no iteration
             if (eps < (float)nMin / (float)N) eps = (float)nMin / (float)N;
-            if (nMin == N) its = 1;
-            else {
-                const double x = ceil(log(1 - P.probability) / log(1 - pow((double)eps, 3.0)));
-                its = !(x < (double)P.maxIterations) ? P.maxIterations : (x < 1.0 ? 1 : (int)x);
-            }
-            if (its > P.maxIterations) its = P.maxIterations;
-            if (its < 1) its = 1;
+            its = ransac_iterations(P.probability, eps, nMin == N, P.maxIterations);
         }
         head[f] = make_int4(N, nMin, its, 0);
         if (its == 0) { nInliers[f] = 0; if (iterations) iterations[f] = 0; }
@@ -540,20 +535,10 @@ __global__ __launch_bounds__(64) void k_pnp_hyp(PnpParams P, const Corr* __restr
     const Corr* corr = corrAll + (size_t)f * P.nf;
     const size_t slot = (size_t)f * P.maxIterations + it;
     if (tid == 0) {
-        // vAvailableIndices = mvAllIndices, then four times RandomInt(0, size - 1) and the swap with the back (:192-205); the vector is the
-        // identity but for the at most three positions a removal rewrote
-        const uint32_t* dr = draws + slot * 4;
-        int size = N, pos[4], val[4];
+        int smp[4];
+        ransac_sample<4>(draws + slot * 4, N, smp);                    // :192-205
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t r = dr[k] & 0x7fffffffu;                    // a value rand() can return
-            const int randi = (int)(((double)r / 2147483648.0) * size);
-            int idx = randi, back = size - 1;
-#pragma unroll
-            for (int j = 0; j < k; j++) { if (pos[j] == randi) idx = val[j]; if (pos[j] == size - 1) back = val[j]; }
-            s_list[k] = (unsigned short)idx;
-            pos[k] = randi; val[k] = back; size--;
-        }
+        for (int k = 0; k < 4; k++) s_list[k] = (unsigned short)smp[k];
     }
     __syncthreads();
     compute_pose<64>(S, P, corr, s_list, 4, tid);
@@ -592,7 +577,7 @@ __global__ __launch_bounds__(kRefThreads) void k_pnp_replay(PnpParams P, const C
         if (tid == 0) { store_pose(T, R, t); nInliers[f] = n; }
     };
 #pragma unroll 1
-    for (int it = 0; it < kPnpMaxIterations; it++) {
+    for (int it = 0; it < kRansacMaxIterations; it++) {
         if (it >= maxIts) break;
         const size_t slot = (size_t)f * P.maxIterations + it;
         const int ni = hypN[slot];
@@ -625,22 +610,19 @@ int ivf_tracker_solve_pnp(ivf_tracker* t, const uint8_t* d_records, size_t recor
                           float* d_hyp_poses, int32_t* d_hyp_ninliers, void* hip_stream)
 {
     if (!t || !d_records || !d_frames || !d_xw || !d_has_point || !d_draws || !d_poses || !d_inlier || !d_ninliers) return fail(IVF_E_INVALID, "null argument");
-    if (((size_t)d_records & 15) != 0) return fail(IVF_E_INVALID, "the record block must be 16-byte aligned");
-    if (max_iterations < 1 || max_iterations > kPnpMaxIterations) return fail(IVF_E_INVALID, "max_iterations %d outside [1,%d]", max_iterations, kPnpMaxIterations);
-    if (!(probability > 0.0 && probability < 1.0)) return fail(IVF_E_INVALID, "probability %g outside (0,1)", probability);
+    const int ra = ransac_args_ok(d_records, max_iterations, probability, min_inliers);
+    if (ra != IVF_OK) return ra;
     if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(IVF_E_INVALID, "epsilon %g outside [0,1]", (double)epsilon);
-    if (min_inliers < 0 || !(th2 > 0.0f)) return fail(IVF_E_INVALID, "min_inliers must be >= 0 and th2 positive");
+    if (!(th2 > 0.0f)) return fail(IVF_E_INVALID, "min_inliers must be >= 0 and th2 positive");
     if (n_frames == 0) return IVF_OK;
     hipStream_t st = (hipStream_t)hip_stream;
     const int rc = tracker_begin(t, true, record_bytes, n_records, n_frames, st);
     if (rc != IVF_OK) return rc;
     if (!t->pnp.corr) {                                                // first use: the scratch of ONE call, sized by max_pairs
         const size_t np = (size_t)t->cfg.max_pairs, nf = (size_t)t->P.nf;
-        if (!(t->alloc(t->pnp.corr, np * nf * sizeof(Corr)) && t->alloc(t->pnp.head, np * sizeof(int4)) &&
-              t->alloc(t->pnp.hypPose, np * kPnpMaxIterations * 12 * sizeof(double)) && t->alloc(t->pnp.hypN, np * kPnpMaxIterations * sizeof(int)))) {
-            t->release(t->pnp.corr); t->release(t->pnp.head); t->release(t->pnp.hypPose); t->release(t->pnp.hypN);
+        if (!t->alloc_all(t->pnp.corr, np * nf * sizeof(Corr), t->pnp.head, np * sizeof(int4), t->pnp.hypPose,
+                          np * kRansacMaxIterations * 12 * sizeof(double), t->pnp.hypN, np * kRansacMaxIterations * sizeof(int)))
             return fail(IVF_E_NO_DEVICE, "device allocation failed for the PnP scratch of %d frames x %d features", t->cfg.max_pairs, t->P.nf);
-        }
     }
     PnpParams P;
     P.nf = t->P.nf; P.nRecords = n_records; P.recBytes = t->P.recBytes;

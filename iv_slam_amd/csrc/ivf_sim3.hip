@@ -16,7 +16,8 @@
 //                   the same bits), written by i1, with the state the next call resumes from.
 // cv::eigen of the symmetric 4x4 N is a cyclic two-sided Jacobi in f64 (jacobi_eigen4): fixed pair order, at most kSweeps sweeps, so a
 // NaN cannot spin a kernel; a degenerate sample (norm(vec) == 0, e.g. a pure translation whose N is diagonal) gives NaN, no inlier, and
-// falls through like any other hypothesis.  The ordered compaction, the pose I/O and the level table are ivf_solve.h's.
+// falls through like any other hypothesis.  The ordered compaction, the pose I/O and the level table are ivf_solve.h's; so are the
+// sampler and the iteration count, shared with ivf_pnp.hip (their cap, argument checks and scratch allocation: ivf_tracker.h).
 #include "ivf_solve.h"
 
 using namespace ivf;
@@ -282,17 +283,8 @@ __global__ __launch_bounds__(256) void k_sim3_prepare(Sim3Params P, const uint8_
     if (tid == 0) {
         const int it0 = state ? state[2 * p] : 0, best0 = state ? state[2 * p + 1] : 0;
         int its = 0;
-        if (N >= P.minInliers && N >= 3) {                             // else :149-153 (below three points the reference has no sample to draw)
-            // SetRansacParameters (:128-138)
-            if (P.minInliers == N) its = 1;
-            else {
-                const float eps = (float)P.minInliers / (float)N;
-                const double x = ceil(log(1 - P.probability) / log(1 - pow((double)eps, 3.0)));
-                its = !(x < (double)P.maxIterations) ? P.maxIterations : (x < 1.0 ? 1 : (int)x);
-            }
-            if (its > P.maxIterations) its = P.maxIterations;
-            if (its < 1) its = 1;
-        }
+        if (N >= P.minInliers && N >= 3)                               // else :149-153 (below three points the reference has no sample to draw)
+            its = ransac_iterations(P.probability, (float)P.minInliers / (float)N, P.minInliers == N, P.maxIterations);   // :128-138
         head[p] = make_int4(N, its, it0 < 0 ? 0 : it0, best0);
         if (its == 0) { nInliers[p] = 0; if (iterations) iterations[p] = it0; }   // mnIterations is not advanced, the state stays
     }
@@ -309,20 +301,8 @@ __global__ __launch_bounds__(64) void k_sim3_hyp(Sim3Params P, const Corr3* __re
     const int N = h.x;
     const Corr3* corr = corrAll + (size_t)p * P.nf;
     const size_t slot = (size_t)p * P.maxIterations + it;
-    // vAvailableIndices = mvAllIndices, then three times RandomInt(0, size - 1) and the swap with the back (:166-180); the vector is the
-    // identity but for the at most two positions a removal rewrote
-    const uint32_t* dr = draws + slot * 3;
-    int size = N, pos[3], val[3], smp[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const uint32_t r = dr[k] & 0x7fffffffu;                        // a value rand() can return
-        const int randi = (int)(((double)r / 2147483648.0) * size);
-        int idx = randi, back = size - 1;
-#pragma unroll
-        for (int j = 0; j < k; j++) { if (pos[j] == randi) idx = val[j]; if (pos[j] == size - 1) back = val[j]; }
-        smp[k] = idx;
-        pos[k] = randi; val[k] = back; size--;
-    }
+    int smp[3];
+    ransac_sample<3>(draws + slot * 3, N, smp);                        // :166-180, the same in every lane
     float p1[3][3], p2[3][3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -357,7 +337,7 @@ __global__ __launch_bounds__(64) void k_sim3_replay(Sim3Params P, const Corr3* _
     if (maxIts < 1) return;                                            // k_sim3_prepare has answered
     int best = h.w, done = it0, won = -1;
 #pragma unroll 1
-    for (int it = 0; it < kSim3MaxIterations; it++) {                  // while (mnIterations < mRansacMaxIts ...) (:161)
+    for (int it = 0; it < kRansacMaxIterations; it++) {                  // while (mnIterations < mRansacMaxIts ...) (:161)
         if (it < it0) continue;
         if (it >= maxIts) break;
         done = it + 1;
@@ -396,22 +376,17 @@ int ivf_tracker_solve_sim3(ivf_tracker* t, const uint8_t* d_records, size_t reco
 {
     if (!t || !d_records || !d_pairs || !d_poses || !d_kf_xw || !d_point_flags || !d_match12 || !d_draws || !d_sim3 || !d_inlier || !d_ninliers)
         return fail(IVF_E_INVALID, "null argument");
-    if (((size_t)d_records & 15) != 0) return fail(IVF_E_INVALID, "the record block must be 16-byte aligned");
-    if (max_iterations < 1 || max_iterations > kSim3MaxIterations) return fail(IVF_E_INVALID, "max_iterations %d outside [1,%d]", max_iterations, kSim3MaxIterations);
-    if (!(probability > 0.0 && probability < 1.0)) return fail(IVF_E_INVALID, "probability %g outside (0,1)", probability);
-    if (min_inliers < 0) return fail(IVF_E_INVALID, "min_inliers must be >= 0");
+    const int ra = ransac_args_ok(d_records, max_iterations, probability, min_inliers);
+    if (ra != IVF_OK) return ra;
     if (n_pairs == 0) return IVF_OK;
     hipStream_t st = (hipStream_t)hip_stream;
     const int rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st);
     if (rc != IVF_OK) return rc;
     if (!t->sim3.corr) {                                               // first use: the scratch of ONE call, sized by max_pairs
         const size_t np = (size_t)t->cfg.max_pairs, nf = (size_t)t->P.nf;
-        if (!(t->alloc(t->sim3.corr, np * nf * sizeof(Corr3)) && t->alloc(t->sim3.idx, np * nf * sizeof(unsigned short)) &&
-              t->alloc(t->sim3.head, np * sizeof(int4)) && t->alloc(t->sim3.hyp, np * kSim3MaxIterations * 16 * sizeof(float)) &&
-              t->alloc(t->sim3.hypN, np * kSim3MaxIterations * sizeof(int)))) {
-            t->release(t->sim3.corr); t->release(t->sim3.idx); t->release(t->sim3.head); t->release(t->sim3.hyp); t->release(t->sim3.hypN);
+        if (!t->alloc_all(t->sim3.corr, np * nf * sizeof(Corr3), t->sim3.idx, np * nf * sizeof(unsigned short), t->sim3.head, np * sizeof(int4),
+                          t->sim3.hyp, np * kRansacMaxIterations * 16 * sizeof(float), t->sim3.hypN, np * kRansacMaxIterations * sizeof(int)))
             return fail(IVF_E_NO_DEVICE, "device allocation failed for the Sim3 scratch of %d pairs x %d features", t->cfg.max_pairs, t->P.nf);
-        }
     }
     Sim3Params P;
     P.nf = t->P.nf; P.nRecords = n_records; P.recBytes = t->P.recBytes;

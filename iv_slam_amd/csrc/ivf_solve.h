@@ -1,7 +1,8 @@
 // ivf_solve.h -- what the two solvers of the batched tracker share, ivf_pose.hip (PoseOptimization) and ivf_pnp.hip (PnPsolver), and
 // the searches do not need: the fixed-tree sums, the ordered compaction, a frame's pointer set, the octave clamp, the pose I/O, the
 // Jacobi rotation and the level sigma2 table.  ivf_track_create.hip (CreateNewMapPoints) takes the compaction, the clamp, the rotation
-// and the table; ivf_sim3.hip (Sim3Solver) the compaction, the clamp, the sweep cap and the table.
+// and the table; ivf_sim3.hip (Sim3Solver) the compaction, the clamp, the sweep cap and the table.  ivf_pnp.hip and ivf_sim3.hip share the
+// RANSAC sampler and iteration count below; their cap, argument checks and scratch allocation (alloc_all) are ivf_tracker.h's.
 #pragma once
 #include "ivf_tracker.h"
 
@@ -94,6 +95,37 @@ DEVINL bool jacobi_rotation(double a, double b, double g, double& c, double& s)
     const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
     c = 1.0 / sqrt(1.0 + tn * tn); s = c * tn;
     return true;
+}
+
+// ---- RANSAC, ivf_pnp.hip (K = 4) and ivf_sim3.hip (K = 3): the K sample indices of one iteration from its rand() values dr[K], N >= K
+// (PnPsolver.cc:192-205, Sim3Solver.cc:166-180).  vAvailableIndices = mvAllIndices, then K times DUtils::Random::RandomInt(0, size - 1) and
+// the swap with the back; the vector is the identity but for the at most K - 1 positions a removal rewrote (pos[] / val[]), in registers
+template <int K>
+DEVINL void ransac_sample(const uint32_t* dr, int N, int* smp)
+{
+    int size = N, pos[K], val[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const uint32_t r = dr[k] & 0x7fffffffu;                       // a value rand() can return
+        const int randi = (int)(((double)r / 2147483648.0) * size);
+        int idx = randi, back = size - 1;
+#pragma unroll
+        for (int j = 0; j < k; j++) { if (pos[j] == randi) idx = val[j]; if (pos[j] == size - 1) back = val[j]; }
+        smp[k] = idx;
+        pos[k] = randi; val[k] = back; size--;
+    }
+}
+// mRansacMaxIts, the tail of SetRansacParameters (PnPsolver.cc:148-156, Sim3Solver.cc:130-138): one iteration when nMin == N, else
+// ceil(log(1 - p) / log(1 - eps^3)), not above the caller's maxIterations (a NaN or an infinity ends there too) and not below 1
+DEVINL int ransac_iterations(double probability, float eps, bool allInliers, int maxIterations)
+{
+    int its = 1;
+    if (!allInliers) {
+        const double x = ceil(log(1 - probability) / log(1 - pow((double)eps, 3.0)));
+        its = !(x < (double)maxIterations) ? maxIterations : (x < 1.0 ? 1 : (int)x);
+    }
+    if (its > maxIterations) its = maxIterations;
+    return its < 1 ? 1 : its;
 }
 
 // mvLevelSigma2 (ORBextractor.cc:419-431) of the handle's scale factors; mvInvLevelSigma2 is 1.0f / s2[l]

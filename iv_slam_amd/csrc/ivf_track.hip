@@ -25,7 +25,7 @@
 // The grid itself -- grid_build / grid_walk, here with unsigned short indices (nfeatures <= 4096) -- is ivf_grid.h's, shared with the
 // device-resident ivf_frame (ivf_match.hip); the pieces the three projection searches repeat (liveness, the ordered list, the gates, the
 // first minimum) are ivf_search.h's.  This file also owns the candidate scratch all three use, one call at a time
-// (tracker_grow_queries), and their shared argument checks (search_args_ok).
+// (tracker_grow_queries), their shared argument checks (search_args_ok) and those of the two RANSAC solvers (ransac_args_ok).
 #include "ivf_search.h"
 #include <climits>
 #include <cstring>
@@ -403,6 +403,14 @@ int search_args_ok(const ivf_tracker* t, const void* records, const void* items,
         return fail(IVF_E_INVALID, has_points ? "the record block and the point array must be 16-byte aligned" : "the record block must be 16-byte aligned");
     if (n_items != 0 && (point_quality == nullptr) != (key_quality == nullptr))
         return fail(IVF_E_INVALID, "d_point_quality and d_key_quality come together");
+    return IVF_OK;
+}
+int ransac_args_ok(const void* records, int max_iterations, double probability, int min_inliers)
+{
+    if (((size_t)records & 15) != 0) return fail(IVF_E_INVALID, "the record block must be 16-byte aligned");
+    if (max_iterations < 1 || max_iterations > kRansacMaxIterations) return fail(IVF_E_INVALID, "max_iterations %d outside [1,%d]", max_iterations, kRansacMaxIterations);
+    if (!(probability > 0.0 && probability < 1.0)) return fail(IVF_E_INVALID, "probability %g outside (0,1)", probability);
+    if (min_inliers < 0) return fail(IVF_E_INVALID, "min_inliers must be >= 0");
     return IVF_OK;
 }
 int tracker_grow_queries(ivf_tracker* t, int cap)

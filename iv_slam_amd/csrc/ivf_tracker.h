@@ -8,7 +8,8 @@
 // (PoseOptimization), ivf_pnp.hip (Relocalization's PnPsolver) and ivf_sim3.hip (loop closing's Sim3Solver).  One definition of struct ivf_tracker, one host statement of the
 // camera and record constants (TrackParams), and the device pieces searches and solvers both read (the query record, the pose algebra,
 // PredictScale, UpdateQualityScores); what only the projection searches repeat is ivf_search.h's, what only the solvers repeat
-// ivf_solve.h's, what the BoW units (ivf_track_bow.hip, ivf_track_db.hip and the per-call transform) repeat ivf_bow.h's.
+// ivf_solve.h's, what the BoW units (ivf_track_bow.hip, ivf_track_db.hip and the per-call transform) repeat ivf_bow.h's.  Of the two
+// RANSAC solvers: the cap kRansacMaxIterations, the checks ransac_args_ok, the scratch allocation alloc_all; the rest is ivf_solve.h's.
 #pragma once
 #include "ivf_bow.h"
 #include <vector>
@@ -18,17 +19,16 @@ namespace ivf {
 constexpr int kListCap = 64;                      // candidates listed per query (one per lane of the greedy wave)
 constexpr int kPrefetch = 16;                     // queries whose lists are in registers ahead of the greedy walk
 constexpr int kMaxTrackFeatures = 4096;           // LDS state of k_track_greedy: 20 B per keypoint
-constexpr int kPnpMaxIterations = 300;            // ivf_tracker_solve_pnp: the cap of max_iterations (Tracking.cc:2317 passes 300)
-constexpr int kSim3MaxIterations = 300;           // ivf_tracker_solve_sim3: the cap of max_iterations (LoopClosing.cc:280 passes 300)
+constexpr int kRansacMaxIterations = 300;         // ivf_tracker_solve_pnp / _sim3: the cap of max_iterations (Tracking.cc:2317, LoopClosing.cc:280 pass 300)
 
 // The handle's scratch of ivf_tracker_solve_pnp (ivf_pnp.hip), allocated at its first call for max_pairs frames: the compacted
 // correspondences [max_pairs][nfeatures] (32 B each), per frame {N, mRansacMinInliers, mRansacMaxIts}, and the f64 pose and inlier count
-// of every hypothesis [max_pairs][kPnpMaxIterations]
+// of every hypothesis [max_pairs][kRansacMaxIterations]
 struct PnpScratch { void* corr; void* head; double* hypPose; int* hypN; };
 
 // The handle's scratch of ivf_tracker_solve_sim3 (ivf_sim3.hip), allocated at its first call for max_pairs pairs: the compacted
 // correspondences [max_pairs][nfeatures] (48 B each) and their KF1 keypoint, per pair {N, mRansacMaxIts, mnIterations and mnBestInliers on
-// entry}, and (mR12i, mt12i, ms12i) as 16 floats and the inlier count of every hypothesis [max_pairs][kSim3MaxIterations]
+// entry}, and (mR12i, mt12i, ms12i) as 16 floats and the inlier count of every hypothesis [max_pairs][kRansacMaxIterations]
 struct Sim3Scratch { void* corr; unsigned short* idx; void* head; float* hyp; int* hypN; };
 
 // The handle's scratch of ivf_tracker_reloc_candidates (ivf_track_db.hip), grown on demand to cap >= n_frames * n_keyframes cells and
@@ -182,6 +182,12 @@ struct ivf_tracker {
             if (p && owned[i] == p) { (void)hipFree(p); owned.erase(owned.begin() + i); break; }
         p = nullptr;
     }
+    // several buffers at once, as (pointer, bytes) pairs, all null on entry: every one is allocated and owned, or none is and all stay null
+    bool alloc_all() { return true; }
+    template <class T, class... Rest> bool alloc_all(T*& p, size_t bytes, Rest&&... rest)
+    {
+        return (alloc(p, bytes) && alloc_all(rest...)) || (release(p), false);
+    }
 };
 
 namespace ivf {
@@ -191,6 +197,7 @@ namespace ivf {
 // tracker_end: the event the next call waits for;
 // search_args_ok: what the three projection searches check alike -- the pointers (points: the array of search_local / search_reloc),
 // the 16-byte alignment of what the kernels read as uint4 and, in a call of n_items != 0, that the quality arrays come together;
+// ransac_args_ok: what ivf_pnp.hip and ivf_sim3.hip check alike -- the record block's alignment, max_iterations, probability, min_inliers;
 // tracker_grow_queries: the candidate scratch (dQ, dLRad, dCount, dLists) for at least `cap` queries per frame / pair
 int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n_records, int n_items, hipStream_t st);
 int tracker_begin_with_vocabulary(ivf_tracker* t, const ivf_vocabulary* voc, VocabularyView* V, bool reads_records, size_t record_bytes, int n_records,
@@ -198,5 +205,6 @@ int tracker_begin_with_vocabulary(ivf_tracker* t, const ivf_vocabulary* voc, Voc
 int tracker_end(ivf_tracker* t, hipStream_t st);
 int search_args_ok(const ivf_tracker* t, const void* records, const void* items, bool has_points, const void* points, const void* assign,
                    const void* nmatches, int n_items, const float* point_quality, const float* key_quality);
+int ransac_args_ok(const void* records, int max_iterations, double probability, int min_inliers);
 int tracker_grow_queries(ivf_tracker* t, int cap);
 }  // namespace ivf

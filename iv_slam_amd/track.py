@@ -486,13 +486,17 @@ class MapView:
         self.n_points, self.n_keyframes = n_points, n_kf
 
 
+def ransac_draws(n, max_iterations, k, seed):
+    """The sampling input of a RANSAC solver that draws k points per iteration: uint32 [n, max_iterations, k] values in [0, RAND_MAX] from
+    numpy's generator (a host that wants the reference's own stream passes glibc rand() values instead)."""
+    return np.random.default_rng(seed).integers(0, 2 ** 31, size=(int(n), int(max_iterations), int(k)), dtype=np.uint32)
+
+
 def pnp_draws(n_frames, max_iterations, seed):
-    """The sampling input of BatchTracker.solve_pnp: uint32 [n_frames, max_iterations, 4] values in [0, RAND_MAX] from numpy's generator
-    (a host that wants the reference's own stream passes glibc rand() values instead)."""
-    return np.random.default_rng(seed).integers(0, 2 ** 31, size=(int(n_frames), int(max_iterations), 4), dtype=np.uint32)
+    """The sampling input of BatchTracker.solve_pnp: ransac_draws() with the four points of an EPnP hypothesis"""
+    return ransac_draws(n_frames, max_iterations, 4, seed)
 
 
 def sim3_draws(n_pairs, max_iterations, seed):
-    """The sampling input of BatchTracker.solve_sim3: uint32 [n_pairs, max_iterations, 3] values in [0, RAND_MAX] from numpy's generator
-    (a host that wants the reference's own stream passes glibc rand() values instead)."""
-    return np.random.default_rng(seed).integers(0, 2 ** 31, size=(int(n_pairs), int(max_iterations), 3), dtype=np.uint32)
+    """The sampling input of BatchTracker.solve_sim3: ransac_draws() with the three point pairs of a Horn hypothesis"""
+    return ransac_draws(n_pairs, max_iterations, 3, seed)

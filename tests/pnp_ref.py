@@ -11,10 +11,11 @@ import math
 
 import numpy as np
 
+from ransac_ref import RAND_MAX, draws_for, iteration_count, level_sigma2, random_int, sample_indices as _sample_indices  # noqa: F401  (R.random_int, ...)
+
 D = np.float64
 F = np.float32
 EPS = 2.0 ** -52
-RAND_MAX = 2147483647
 
 
 # ---- the SVD back ends: svd(A) -> (U, w, V) with A = U diag(w) V^T, w descending, V orthonormal --------------------------------------
@@ -81,28 +82,12 @@ def ransac_parameters(N, probability=0.99, min_inliers=10, max_iterations=300, e
         return n_min, 0, None
     if eps < F(n_min) / F(N):
         eps = F(n_min) / F(N)
-    if n_min == N:
-        return n_min, 1, None
-    x = math.log(1 - probability) / math.log(1 - math.pow(float(eps), 3))
-    return n_min, max(1, min(int(math.ceil(x)), int(max_iterations))), x
+    return (n_min,) + iteration_count(probability, eps, n_min == N, max_iterations)
 
 
-def random_int(r, lo, hi):
-    """DUtils::Random::RandomInt on the value r that rand() returned"""
-    d = hi - lo + 1
-    return int((float(int(r) & RAND_MAX) / (RAND_MAX + 1.0)) * d) + lo
-
-
-def sample_indices(N, draws4, min_set=4):
-    """:192-205, transcribed: the vector of available indices, RandomInt, swap with the back, pop"""
-    avail = list(range(N))
-    out = []
-    for i in range(min_set):
-        randi = random_int(draws4[i], 0, len(avail) - 1)
-        out.append(avail[randi])
-        avail[randi] = avail[-1]
-        avail.pop()
-    return out
+def sample_indices(N, draws4, min_set=4, mis=()):
+    """:192-205 (ransac_ref.sample_indices with the four points of minSet)"""
+    return _sample_indices(N, draws4, min_set, mis)
 
 
 # ---- CheckInliers -------------------------------------------------------------------------------------------------------------------------
@@ -127,11 +112,6 @@ def check_inliers(R, t, X, uv, max_err, cam):
 
 def max_error(sigma2, th2):
     return (np.asarray(sigma2, F) * F(th2)).astype(F)
-
-
-def level_sigma2(scale):
-    s = np.asarray(scale, F)
-    return (s * s).astype(F)
 
 
 # ---- EPnP ---------------------------------------------------------------------------------------------------------------------------------

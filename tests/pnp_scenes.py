@@ -67,7 +67,47 @@ def correspondences(fr):
 
 def R_draws(seed, n_frames, max_iterations):
     """the same array iv_slam_amd.track.pnp_draws returns (checked in tests/test_pnp_cpu.py)"""
-    return np.random.default_rng(seed).integers(0, 2 ** 31, size=(n_frames, max_iterations, 4), dtype=np.uint32)
+    from iv_slam_amd import track
+    return track.ransac_draws(n_frames, max_iterations, 4, seed)
+
+
+def sampler_scene():
+    """The scene that shows WHICH four points a hypothesis drew, without comparing poses: 13 frames with the same 12 correspondences and
+    the same draws; frame 0 is clean, frame 1 + j has one coordinate of correspondence j's world point set to NaN.  compute_pose on a sample
+    that holds the NaN point returns a non-finite pose and on any other a finite one, so the frames whose hypothesis `it` is non-finite name
+    the sample of iteration `it`.  epsilon = 0.1 and min_inliers = 4 give mRansacMinInliers = 4, eps = 4 / 12 and 123 iterations, capped by
+    max_iterations = 64.  The first rows of the draws are planted (`rows`: name, the draws, whether a draw reads a position an earlier
+    removal rewrote), the rest come from ransac_draws.
+    -> the scenario dict of scenarios() with draws [13, 64, 4], rows, and the sample a row was planted for (None: raw values)"""
+    from iv_slam_amd import track
+    N, RM = 12, R.RAND_MAX
+    p = dict(DEFAULTS, epsilon=0.1, min_inliers=4, max_iterations=64)
+    base = make_frame(701, 40, N, 1.0, params=p)
+    idx = np.nonzero(base["has"])[0]
+    frames = [base]
+    for j in range(N):
+        fr = dict(base, xw=base["xw"].copy())
+        fr["xw"][idx[j], j % 3] = np.nan
+        frames.append(fr)
+    wanted = [("back_then_zero", [11, 0, 5, 7], False),                # the back first (it replaces itself), then index 0
+              ("second_on_first", [2, 11, 4, 6], True),                # position 2 holds 11 after the first removal
+              ("third_on_first", [2, 5, 11, 6], True),
+              ("fourth_on_first", [2, 5, 7, 11], True),
+              ("third_on_second", [2, 5, 10, 6], True),                # position 5 holds 10 after the second removal
+              ("fourth_on_second", [2, 5, 7, 10], True),
+              ("fourth_on_third", [2, 5, 7, 9], True),                 # position 7 holds 9 after the third removal
+              ("last_after_rewrite", [9, 0, 11, 10], True),            # position 9 holds 11 and is the last one when the third draw reads it
+              ("rewritten_back_moves", [10, 3, 11, 9], True)]          # position 10 holds 11, which the second removal moves on to position 3
+    rows = [(name, R.draws_for(N, w), rew, w) for name, w, rew in wanted]
+    rows += [("all_zero", np.zeros(4, np.uint32), True, None), ("all_rand_max", np.full(4, RM, np.uint32), False, None)]
+    plain = R.draws_for(N, [3, 9, 0, 6])
+    rows += [("bit31_clear", plain, False, [3, 9, 0, 6]), ("bit31_set", plain | np.uint32(0x80000000), False, [3, 9, 0, 6])]
+    draws = track.ransac_draws(1, p["max_iterations"], 4, 18)[0]
+    for it, row in enumerate(rows):
+        draws[it] = row[1]
+    assert base["max_its"] >= len(rows) + 36, "mRansacMaxIts covers the planted rows and three dozen random ones"
+    return dict(nf=64, max_pairs=N + 1, bad=[], seed=18, params=p, degenerate=True, frames=frames, rows=rows,
+                draws=np.repeat(draws[None], N + 1, 0))
 
 
 def scenarios():

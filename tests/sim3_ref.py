@@ -14,10 +14,11 @@ import math
 
 import numpy as np
 
+from ransac_ref import RAND_MAX, draws_for, iteration_count, level_sigma2, random_int, sample_indices as _sample_indices  # noqa: F401  (R.random_int, ...)
+
 D = np.float64
 F = np.float32
 EPS = 2.0 ** -52
-RAND_MAX = 2147483647
 SWEEPS = 30
 
 NO_MATCH, NO_POINT1, NO_POINT2, BAD, INLIER, FAIL_ERR1, FAIL_ERR2 = range(7)
@@ -34,11 +35,6 @@ MISREADINGS = {
     "t21_not_inverted": "mT21i = mT12i (:333-339)",
     "state_not_resumed": "mnIterations and mnBestInliers start from 0 in every call (:41, :161)",
 }
-
-
-def level_sigma2(scale):
-    s = np.asarray(scale, F)
-    return (s * s).astype(F)
 
 
 def max_error(sigma2, mis=()):
@@ -109,51 +105,12 @@ def ransac_iterations(N, probability=0.99, min_inliers=20, max_iterations=300):
     number whose ceil is taken (None where there is none)"""
     if N < min_inliers or N < 3:
         return 0, None
-    if min_inliers == N:
-        return 1, None
-    eps = F(min_inliers) / F(N)
-    with np.errstate(all="ignore"):
-        x = D(math.log(1 - probability)) / np.log(D(1) - D(math.pow(float(eps), 3)))
-    if not x < max_iterations:
-        return int(max_iterations), float(x)
-    if x < 1.0:
-        return 1, float(x)
-    return max(1, min(int(math.ceil(x)), int(max_iterations))), float(x)
-
-
-def random_int(r, lo, hi):
-    """DUtils::Random::RandomInt on the value r that rand() returned"""
-    d = hi - lo + 1
-    return int((float(int(r) & RAND_MAX) / (RAND_MAX + 1.0)) * d) + lo
+    return iteration_count(probability, F(min_inliers) / F(N), min_inliers == N, max_iterations)
 
 
 def sample_indices(N, draws3, mis=()):
-    avail = list(range(N))
-    out = []
-    for i in range(3):
-        randi = random_int(draws3[i], 0, len(avail) - 1)
-        out.append(avail[randi])
-        if "no_swap" in mis:
-            avail.pop(randi)
-        else:
-            avail[randi] = avail[-1]
-            avail.pop()
-    return out
-
-
-def draws_for(N, wanted):
-    """the rand() values under which sample_indices(N, .) returns `wanted` (three distinct indices): the middle of each RandomInt bin"""
-    avail = list(range(N))
-    out = []
-    for w in wanted:
-        randi = avail.index(w)
-        size = len(avail)
-        r = int((randi + 0.5) * (RAND_MAX + 1.0) / size)
-        assert random_int(r, 0, size - 1) == randi
-        out.append(r)
-        avail[randi] = avail[-1]
-        avail.pop()
-    return np.array(out, np.uint32)
+    """:166-180 (ransac_ref.sample_indices with the three point pairs of a hypothesis)"""
+    return _sample_indices(N, draws3, 3, mis)
 
 
 # ---- ComputeSim3 (:229-340) ----------------------------------------------------------------------------------------------------------------

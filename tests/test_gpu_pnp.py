@@ -13,8 +13,8 @@ than that narrowing can move it (band(), a bound worked out from the float forma
 between the count without and with those points and equal the count where there are none, and where such a point belongs to a hypothesis
 that raises mnBestInliers the replay follows every inlier set consistent with the device's count.
 
-The sampler (draws -> indices) is not exposed by the call: it is checked on the CPU (tests/test_pnp_cpu.py, against a transcription of
-:192-205) and here only through the replay, which fails on a sample that repeats a point (EPnP on three distinct points has no pose)."""
+The sampler (draws -> indices) is not exposed by the call: the restatement's is checked on the CPU (tests/test_pnp_cpu.py, against a
+transcription of :192-205), the device's on a scene whose NaN-tagged world points name the sample of every iteration (sampler_scene)."""
 import json
 import os
 import sys
@@ -26,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pnp_ref as R
 import pnp_scenes as S
 import pose_opt_ref as PR
+import ransac_ref as RR
 from test_gpu_track import iv  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
@@ -52,7 +53,7 @@ def run_pnp(iv, sc, order=None, stream=False, tracker=None, hyp=True):
     block = torch.from_numpy(ivd.pack_records([dict(kps=f["kps"], desc=f["desc"], uright=f["uright"], depth=f["depth"]) for f in frames], nf).reshape(-1)).to(dev)
     tr = tracker or make_tracker(iv, nf, sc["max_pairs"])
     xw = np.zeros((n, nf, 3), F); has = np.zeros((n, nf), np.uint8)
-    draws = S.R_draws(sc["seed"], n, mi)
+    draws = sc["draws"] if "draws" in sc else S.R_draws(sc["seed"], n, mi)
     for j, k in enumerate(order):
         f = frames[k]
         xw[j, :f["n"]] = f["xw"]; has[j, :f["n"]] = f["has"]
@@ -258,6 +259,24 @@ def test_runs_are_bit_identical_on_any_stream_and_in_any_frame_order(iv):
         assert a[key].tobytes() == d[key].tobytes(), "%s differs under another frame order" % key
         if not key.startswith("hyp"):
             assert a[key].tobytes() == e[key].tobytes(), "%s differs without the hypothesis outputs" % key
+
+
+def test_sampler_draws_the_four_points_of_the_restatement(iv):
+    """tests/pnp_scenes.py:sampler_scene: frame 1 + j carries a NaN in the world point of correspondence j, so the frames whose hypothesis
+    `it` is non-finite are the four points k_pnp_hyp sampled in iteration `it` (tests/test_pnp_cpu.py shows that compute_pose behaves so and
+    that the no_swap and the stride-3 misreadings give other sets).  Every iteration, the planted rows among them: the back drawn first,
+    positions an earlier removal rewrote, all-0 and all-RAND_MAX rows, bit 31 set"""
+    sc = S.sampler_scene()
+    got = run_pnp(iv, sc)
+    N, its, draws = sc["frames"][0]["N"], sc["frames"][0]["max_its"], sc["draws"][0]
+    bad = ~np.isfinite(got["hyp_pose"][:, :its]).all(2)                        # [13, its]
+    assert not bad[0].any(), "the clean frame has a finite pose in every iteration"
+    for it in range(its):
+        want = set(RR.sample_indices(N, draws[it], 4))
+        tagged = set(int(j) for j in np.nonzero(bad[1:, it])[0])
+        name = sc["rows"][it][0] if it < len(sc["rows"]) else "random"
+        assert tagged == want, "iteration %d (%s): the device sampled %r, the restatement %r" % (it, name, sorted(tagged), sorted(want))
+    assert (got["hyp_n"][:, :its][bad] == 0).all(), "a non-finite hypothesis has no inlier"
 
 
 def test_arguments_are_checked(iv):

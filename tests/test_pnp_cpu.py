@@ -23,6 +23,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pnp_ref as R
 import pnp_scenes as S
 import pose_opt_ref as PR
+import ransac_ref as RR
+import sim3_ref as R3
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NOISE_PATH = os.path.join(ROOT, "tests", "golden", "pnp_noise.json")
@@ -70,10 +72,10 @@ def test_argument_validation_without_gpu():
 
 
 # ---- hand-made values --------------------------------------------------------------------------------------------------------------------
-def transcribed_sample(N, draws):
-    """a direct transcription of PnPsolver.cc:192-205 with RandomInt spelled out in integers"""
+def transcribed_sample(N, draws, k=4):
+    """a direct transcription of PnPsolver.cc:192-205 (k = 4) and Sim3Solver.cc:166-180 (k = 3) with RandomInt spelled out in integers"""
     v = list(range(N)); out = []
-    for i in range(4):
+    for i in range(k):
         size = len(v)
         randi = int(int(draws[i]) / 2147483648.0 * size)
         out.append(v[randi]); v[randi] = v[-1]; v.pop()
@@ -95,6 +97,8 @@ def test_sampler_known_answers():
                 d[rng.integers(0, 4)] = rng.choice([0, RM])
             got = R.sample_indices(N, d)
             assert got == transcribed_sample(N, d) and len(set(got)) == 4 and max(got) < N
+            got3 = R3.sample_indices(N, d[:3])
+            assert got3 == transcribed_sample(N, d, 3) == RR.sample_indices(N, d, 3) and got == RR.sample_indices(N, d, 4)
 
 
 def test_iteration_count_known_answers():
@@ -107,6 +111,40 @@ def test_iteration_count_known_answers():
     assert R.ransac_parameters(1000, max_iterations=20)[:2] == (500, 20)
     assert R.ransac_parameters(257, epsilon=0.3, max_iterations=40)[:2] == (77, 40) and R.ransac_parameters(257, epsilon=0.3)[:2] == (77, 169)
     assert R.ransac_parameters(6, min_inliers=2)[:2] == (4, 14)                # minSet = 4 bounds mRansacMinInliers; eps = 4/6 as for N = 15
+
+
+def test_sampler_scene_tags_the_sample_and_catches_both_misreadings():
+    """tests/pnp_scenes.py:sampler_scene, the CPU twin of tests/test_gpu_pnp.py's sampler test.  Under both back ends compute_pose is finite
+    on every 4-sample the draws select from the clean frame and all-NaN on the frame whose NaN point the sample holds: the non-finite
+    hypotheses of the 12 tagged frames name the sample.  The sets the device test expects differ from those of the no_swap misreading on
+    every planted row that reads a rewritten position, and from those of draws read with stride 3 on more than half of the rows (row 0
+    is the same under any stride; a random row coincides with probability 1 / 495): either mistake fails that test."""
+    sc = S.sampler_scene()
+    fr0 = sc["frames"][0]
+    N, its, draws = fr0["N"], fr0["max_its"], sc["draws"][0]
+    assert (N, fr0["n_min"], its) == (12, 4, 64) and all((d == draws).all() for d in sc["draws"])
+    want = [RR.sample_indices(N, draws[it], 4) for it in range(its)]
+    for it, (name, row, rewritten, smp) in enumerate(sc["rows"]):
+        assert smp is None or want[it] == smp, name
+        no_swap = RR.sample_indices(N, draws[it], 4, {"no_swap"})
+        assert not rewritten or set(no_swap) != set(want[it]), name
+    by_name = {row[0]: it for it, row in enumerate(sc["rows"])}
+    assert want[by_name["all_zero"]] == [0, 11, 10, 9] and want[by_name["all_rand_max"]] == [11, 10, 9, 8]
+    assert want[by_name["bit31_set"]] == want[by_name["bit31_clear"]] and (draws[by_name["bit31_set"]] >> 31).all()
+    flat = draws.reshape(-1)
+    stride3 = [RR.sample_indices(N, flat[3 * it:3 * it + 4], 4) for it in range(its)]
+    assert sum(set(a) != set(b) for a, b in zip(stride3, want)) > its // 2
+    _, X0, uv, _ = S.correspondences(fr0)
+    for backend in ("numpy", "jacobi"):
+        for it in range(its):
+            smp = want[it]
+            Rm, t, _ = R.compute_pose(X0[smp], uv[smp], S.CAM, backend)
+            assert np.isfinite(Rm).all() and np.isfinite(t).all(), (backend, it, smp)
+            for j in smp:
+                _, Xj, _, _ = S.correspondences(sc["frames"][1 + j])
+                assert np.isnan(Xj[j]).sum() == 1 and np.isfinite(np.delete(Xj, j, 0)).all()
+                Rm, t, _ = R.compute_pose(Xj[smp], uv[smp], S.CAM, backend)
+                assert np.isnan(Rm).all() and np.isnan(t).all(), (backend, it, j)
 
 
 # ---- the restatement against itself and the planted truth ----------------------------------------------------------------------------------
