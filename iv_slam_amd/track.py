@@ -3,15 +3,60 @@ the matcher part of Tracking::TrackWithMotionModel (ORB/src/Tracking.cc:1303-133
 ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, false) (ORB/src/ORBmatcher.cc:1372-1518), the retry with the wider
 window -- in one launch sequence on the device.  torch tensors are only the device-memory plumbing."""
 import ctypes as C
+from functools import partial
 
 import numpy as np
+import torch
 
 from . import _lib
 from ._lib import Bounds, TrackConfig, check
 
+LOCAL_POINT_BYTES = _lib.LOCAL_POINT_DTYPE.itemsize                      # sizeof(ivf_local_point); _lib asserts the dtype's size
+KF_NEIGH = 10                                                            # the neighbours a kf_neigh row holds: GetBestCovisibilityKeyFrames(10)
+KF_NEIGH_IS = "kf_neigh is [n_keyframes, %d]" % KF_NEIGH
+
+# The kinds of tensor a pointer argument can be: (name, element size, floating point; None = either).
+I32, F32, F64, U8 = ("int32", 4, False), ("float32", 4, True), ("float64", 8, True), ("uint8", 1, False)
+ANY4 = ("4-byte", 4, None)                                               # draws: uint32 values in whatever 4-byte dtype holds them
+BYTES = ("uint8 (bytes of records)", 1, False)                           # views of ivf_local_point / gather records: counted in bytes
+
 
 def record_bytes(nfeatures):
     return int(_lib.load().ivf_track_record_bytes(int(nfeatures)))
+
+
+def _given(x):
+    if isinstance(x, torch.Tensor):
+        return "%s %s on %s%s" % (x.dtype, tuple(x.shape), x.device, "" if x.is_contiguous() else ", not contiguous")
+    return type(x).__name__ + (" on %s" % x.device if isinstance(x, MapView) else "")
+
+
+def _require(ok, message, x):
+    """an `assert` on the argument x that python -O keeps"""
+    if not ok:
+        raise AssertionError("%s, given %s" % (message, _given(x)))
+
+
+def _tensor(name, x, ndim=None, what="a torch tensor"):
+    """x for a method's shape arithmetic: a tensor, of ndim dimensions where that is given"""
+    if not (isinstance(x, torch.Tensor) and ndim in (None, x.dim())):
+        raise AssertionError("%s is %s, given %s" % (name, what, _given(x)))
+    return x
+
+
+def _ptr(device, name, x, kind, count=0, exact=False, optional=False, what=None):
+    """The address the library receives for the argument `name`, and the one check before it: x is a tensor on `device`, contiguous,
+    of the kind's element size and float / integer class, with at least `count` elements (exactly `count` where that count is a
+    dimension the call states).  None passes as None where the argument is optional.  Looks at x's metadata only: no value is read,
+    nothing synchronises; a size that only the device knows stays the library's to check."""
+    if x is None and optional:
+        return None
+    kind_name, size, is_float = kind
+    if (isinstance(x, torch.Tensor) and x.device == device and x.is_contiguous() and x.element_size() == size
+            and is_float in (None, x.dtype.is_floating_point) and (x.numel() == count if exact else x.numel() >= count)):
+        return x.data_ptr()
+    raise AssertionError("%s: expected a contiguous %s tensor on %s with %s %d elements%s, given %s"
+                         % (name, kind_name, device, "exactly" if exact else "at least", count, " (%s)" % what if what else "", _given(x)))
 
 
 class BatchTracker:
@@ -38,11 +83,27 @@ class BatchTracker:
         check(self._lib.ivf_tracker_create(C.byref(cfg), C.byref(h)))
         self._h = h
         self.nfeatures, self.max_pairs, self.record_bytes = nfeatures, max_pairs, record_bytes(nfeatures)
+        self.device_id, self.device = device_id, torch.device("cuda", device_id)      # where every tensor of every call must live
 
     def __del__(self):
         if getattr(self, "_h", None):
             self._lib.ivf_tracker_destroy(self._h)
             self._h = None
+
+    def _records(self, records):
+        """(address, n_records) of a block of gather records"""
+        n_rec = _tensor("records", records).numel() // self.record_bytes
+        return _ptr(self.device, "records", records, BYTES, n_rec * self.record_bytes), n_rec
+
+    def _pairs(self, pairs):
+        """(address, n_pairs) of a pair table"""
+        n_pairs = _tensor("pairs", pairs, 2, "[n_pairs, 2]").shape[0]
+        return _ptr(self.device, "pairs", pairs, I32, n_pairs * 2, exact=True, what="pairs is [n_pairs, 2]"), n_pairs
+
+    def _view(self, map_view):
+        """the ivf_map_view of a MapView that lives where the tracker does"""
+        _require(isinstance(map_view, MapView) and map_view.device == self.device, "map_view is an iv_slam_amd.track.MapView on the tracker's device", map_view)
+        return map_view.c
 
     def run(self, records, pairs, assign, nmatches, poses=None, point_flags=None, point_quality=None, key_quality=None, stream_ptr=None):
         """records: torch.uint8 [n_records * record_bytes] (a packed block or the all-gathered buffer); pairs: torch.int32
@@ -50,19 +111,14 @@ class BatchTracker:
         poses: torch.float32 [n_pairs, 2, 12] = per pair {LastFrame.mTcw, CurrentFrame.mTcw prior}, row-major 3x4, or None = zero
         motion; point_flags: torch.uint8 [n_records, nfeatures] or None; point_quality / key_quality: torch.float32
         [n_pairs, nfeatures] in/out (UpdateQualityScores on the device) or None.  Asynchronous on the given stream."""
-        n_rec = records.numel() // self.record_bytes
-        n_pairs = pairs.shape[0]
-        assert pairs.dtype.is_floating_point is False and pairs.element_size() == 4 and pairs.is_contiguous()
-        assert assign.element_size() == 4 and assign.numel() >= n_pairs * self.nfeatures and nmatches.numel() >= n_pairs
-        assert poses is None or (poses.is_contiguous() and poses.numel() == n_pairs * 24), "poses are per PAIR: [n_pairs, 2, 12]"
-        for q in (point_quality, key_quality):
-            assert q is None or (q.is_contiguous() and q.element_size() == 4 and q.numel() >= n_pairs * self.nfeatures)
-        check(self._lib.ivf_tracker_run(self._h, records.data_ptr(), self.record_bytes, n_rec, pairs.data_ptr(), n_pairs,
-                                        None if poses is None else poses.data_ptr(),
-                                        None if point_flags is None else point_flags.data_ptr(),
-                                        None if point_quality is None else point_quality.data_ptr(),
-                                        None if key_quality is None else key_quality.data_ptr(),
-                                        assign.data_ptr(), nmatches.data_ptr(), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        (records_p, n_rec), (pairs_p, n_pairs) = self._records(records), self._pairs(pairs)
+        check(self._lib.ivf_tracker_run(
+            self._h, records_p, self.record_bytes, n_rec, pairs_p, n_pairs,
+            p("poses", poses, F32, n_pairs * 24, exact=True, optional=True, what="poses are per PAIR: [n_pairs, 2, 12]"),
+            p("point_flags", point_flags, U8, n_rec * nf, optional=True), p("point_quality", point_quality, F32, n_pairs * nf, optional=True),
+            p("key_quality", key_quality, F32, n_pairs * nf, optional=True), p("assign", assign, I32, n_pairs * nf),
+            p("nmatches", nmatches, I32, n_pairs), stream_ptr))
 
     def search_local(self, records, frames, points, point_offsets, max_points_per_frame, assign, nmatches, poses=None, occupied=None,
                      th=1.0, nn_ratio=0.8, cos_limit=0.5, point_quality=None, key_quality=None, stream_ptr=None):
@@ -73,39 +129,34 @@ class BatchTracker:
         assign: torch.int32 [n_frames, nfeatures] (index within the frame's point range or -1); nmatches: torch.int32 [n_frames];
         point_quality: torch.float32 indexed like points, key_quality: torch.float32 [n_frames, nfeatures] (both in/out) or None.
         Asynchronous on the given stream."""
-        n_rec = records.numel() // self.record_bytes
-        n_frames = frames.numel()
-        assert frames.element_size() == 4 and point_offsets.element_size() == 4 and point_offsets.numel() >= n_frames + 1
-        assert assign.element_size() == 4 and assign.numel() >= n_frames * self.nfeatures and nmatches.numel() >= n_frames
-        assert poses is None or (poses.is_contiguous() and poses.numel() == n_frames * 12), "poses are per frame SLOT: [n_frames, 12]"
-        check(self._lib.ivf_tracker_search_local(self._h, records.data_ptr(), self.record_bytes, n_rec, frames.data_ptr(), n_frames,
-                                                 None if poses is None else poses.data_ptr(), points.data_ptr(), point_offsets.data_ptr(),
-                                                 int(max_points_per_frame), None if occupied is None else occupied.data_ptr(),
-                                                 float(th), float(nn_ratio), float(cos_limit),
-                                                 None if point_quality is None else point_quality.data_ptr(),
-                                                 None if key_quality is None else key_quality.data_ptr(),
-                                                 assign.data_ptr(), nmatches.data_ptr(), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        (records_p, n_rec), n_frames = self._records(records), _tensor("frames", frames).numel()
+        # points and point_quality hold point_offsets[n_frames] entries, which only the device knows: their size stays the library's to check
+        check(self._lib.ivf_tracker_search_local(
+            self._h, records_p, self.record_bytes, n_rec, p("frames", frames, I32, n_frames), n_frames,
+            p("poses", poses, F32, n_frames * 12, exact=True, optional=True, what="poses are per frame SLOT: [n_frames, 12]"),
+            p("points", points, BYTES), p("point_offsets", point_offsets, I32, n_frames + 1), int(max_points_per_frame),
+            p("occupied", occupied, U8, n_frames * nf, optional=True), float(th), float(nn_ratio), float(cos_limit),
+            p("point_quality", point_quality, F32, optional=True), p("key_quality", key_quality, F32, n_frames * nf, optional=True),
+            p("assign", assign, I32, n_frames * nf), p("nmatches", nmatches, I32, n_frames), stream_ptr))
 
     def points_from_pairs(self, records, pairs, assign, xw, has_point, poses=None, stream_ptr=None):
         """The map points behind run()'s assignments: xw[p, i2] = Frame::UnprojectStereo(assign[p, i2]) of the LAST record of pair p under
         its last pose (ORB/src/Frame.cc:958-972), has_point[p, i2] = 1 where there is one.  pairs / poses / assign as run() took and
         wrote them; xw: torch.float32 [n_pairs, nfeatures, 3], has_point: torch.uint8 [n_pairs, nfeatures].  Asynchronous."""
-        n_rec = records.numel() // self.record_bytes
-        n_pairs = pairs.shape[0]
-        assert pairs.element_size() == 4 and pairs.is_contiguous() and assign.element_size() == 4 and assign.numel() >= n_pairs * self.nfeatures
-        assert poses is None or (poses.is_contiguous() and poses.numel() == n_pairs * 24), "poses are per PAIR: [n_pairs, 2, 12]"
-        assert xw.element_size() == 4 and xw.numel() >= n_pairs * self.nfeatures * 3 and has_point.element_size() == 1 and has_point.numel() >= n_pairs * self.nfeatures
-        check(self._lib.ivf_tracker_points_from_pairs(self._h, records.data_ptr(), self.record_bytes, n_rec, pairs.data_ptr(), n_pairs,
-                                                      None if poses is None else poses.data_ptr(), assign.data_ptr(), xw.data_ptr(),
-                                                      has_point.data_ptr(), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        (records_p, n_rec), (pairs_p, n_pairs) = self._records(records), self._pairs(pairs)
+        check(self._lib.ivf_tracker_points_from_pairs(
+            self._h, records_p, self.record_bytes, n_rec, pairs_p, n_pairs,
+            p("poses", poses, F32, n_pairs * 24, exact=True, optional=True, what="poses are per PAIR: [n_pairs, 2, 12]"),
+            p("assign", assign, I32, n_pairs * nf), p("xw", xw, F32, n_pairs * nf * 3), p("has_point", has_point, U8, n_pairs * nf), stream_ptr))
 
     def points_from_local(self, points, point_offsets, assign, xw, has_point, stream_ptr=None):
         """The map points behind search_local()'s assignments: xw[f, i] = points[point_offsets[f] + assign[f, i]].pos.  Asynchronous."""
-        n_frames = point_offsets.numel() - 1
-        assert point_offsets.element_size() == 4 and assign.element_size() == 4 and assign.numel() >= n_frames * self.nfeatures
-        assert xw.element_size() == 4 and xw.numel() >= n_frames * self.nfeatures * 3 and has_point.element_size() == 1 and has_point.numel() >= n_frames * self.nfeatures
-        check(self._lib.ivf_tracker_points_from_local(self._h, points.data_ptr(), point_offsets.data_ptr(), assign.data_ptr(), n_frames,
-                                                      xw.data_ptr(), has_point.data_ptr(), stream_ptr))
+        p, nf, n_frames = partial(_ptr, self.device), self.nfeatures, _tensor("point_offsets", point_offsets).numel() - 1
+        check(self._lib.ivf_tracker_points_from_local(                             # points: sized on the device, as in search_local()
+            self._h, p("points", points, BYTES), p("point_offsets", point_offsets, I32, n_frames + 1), p("assign", assign, I32, n_frames * nf),
+            n_frames, p("xw", xw, F32, n_frames * nf * 3), p("has_point", has_point, U8, n_frames * nf), stream_ptr))
 
     def search_by_bow(self, vocabulary, records, pairs, assign, nmatches, levelsup=4, select=None, point_flags=None, nn_ratio=0.7,
                       check_orientation=True, point_quality=None, key_quality=None, stream_ptr=None):
@@ -118,33 +169,24 @@ class BatchTracker:
         point_quality (by keyframe keypoint) / key_quality (by frame keypoint): torch.float32 [n_pairs, nfeatures] in/out or None;
         assign: torch.int32 [n_pairs, nfeatures] = the keyframe keypoint whose point the frame keypoint receives or -1; nmatches:
         torch.int32 [n_pairs].  Asynchronous on the given stream."""
-        n_rec = records.numel() // self.record_bytes
-        n_pairs = pairs.shape[0]
-        assert pairs.dtype.is_floating_point is False and pairs.element_size() == 4 and pairs.is_contiguous()
-        assert assign.element_size() == 4 and assign.numel() >= n_pairs * self.nfeatures and nmatches.numel() >= n_pairs
-        assert select is None or (select.element_size() == 4 and select.is_contiguous() and select.numel() >= n_pairs)
-        assert point_flags is None or (point_flags.element_size() == 1 and point_flags.numel() >= n_rec * self.nfeatures)
-        for q in (point_quality, key_quality):
-            assert q is None or (q.is_contiguous() and q.element_size() == 4 and q.numel() >= n_pairs * self.nfeatures)
-        check(self._lib.ivf_tracker_search_by_bow(self._h, vocabulary._h, int(levelsup), records.data_ptr(), self.record_bytes, n_rec,
-                                                  pairs.data_ptr(), n_pairs, None if select is None else select.data_ptr(),
-                                                  None if point_flags is None else point_flags.data_ptr(), float(nn_ratio),
-                                                  int(bool(check_orientation)),
-                                                  None if point_quality is None else point_quality.data_ptr(),
-                                                  None if key_quality is None else key_quality.data_ptr(),
-                                                  assign.data_ptr(), nmatches.data_ptr(), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        (records_p, n_rec), (pairs_p, n_pairs) = self._records(records), self._pairs(pairs)
+        check(self._lib.ivf_tracker_search_by_bow(
+            self._h, vocabulary._h, int(levelsup), records_p, self.record_bytes, n_rec, pairs_p, n_pairs,
+            p("select", select, I32, n_pairs, optional=True), p("point_flags", point_flags, U8, n_rec * nf, optional=True),
+            float(nn_ratio), int(bool(check_orientation)), p("point_quality", point_quality, F32, n_pairs * nf, optional=True),
+            p("key_quality", key_quality, F32, n_pairs * nf, optional=True), p("assign", assign, I32, n_pairs * nf),
+            p("nmatches", nmatches, I32, n_pairs), stream_ptr))
 
     def points_from_keyframe(self, pairs, kf_xw, assign, xw, has_point, stream_ptr=None):
         """The map points behind search_by_bow()'s assignments: xw[p, i] = kf_xw[keyframe record of pair p, assign[p, i]], has_point = 1
         where there is one.  kf_xw: torch.float32 [n_records, nfeatures, 3] = GetWorldPos() of the point each keypoint of each record
         holds; pairs / assign as search_by_bow() took and wrote them.  Asynchronous."""
-        n_pairs = pairs.shape[0]
-        n_rec = kf_xw.numel() // (self.nfeatures * 3)
-        assert pairs.element_size() == 4 and pairs.is_contiguous() and assign.element_size() == 4 and assign.numel() >= n_pairs * self.nfeatures
-        assert kf_xw.is_contiguous() and kf_xw.element_size() == 4 and kf_xw.numel() == n_rec * self.nfeatures * 3
-        assert xw.element_size() == 4 and xw.numel() >= n_pairs * self.nfeatures * 3 and has_point.element_size() == 1 and has_point.numel() >= n_pairs * self.nfeatures
-        check(self._lib.ivf_tracker_points_from_keyframe(self._h, pairs.data_ptr(), n_pairs, n_rec, kf_xw.data_ptr(), assign.data_ptr(),
-                                                         xw.data_ptr(), has_point.data_ptr(), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        (pairs_p, n_pairs), n_rec = self._pairs(pairs), _tensor("kf_xw", kf_xw).numel() // (nf * 3)
+        check(self._lib.ivf_tracker_points_from_keyframe(
+            self._h, pairs_p, n_pairs, n_rec, p("kf_xw", kf_xw, F32, n_rec * nf * 3, exact=True, what="kf_xw is [n_records, nfeatures, 3]"),
+            p("assign", assign, I32, n_pairs * nf), p("xw", xw, F32, n_pairs * nf * 3), p("has_point", has_point, U8, n_pairs * nf), stream_ptr))
 
     def bow_vectors(self, vocabulary, records, frames, bow_word, bow_value, bow_n, stream_ptr=None):
         """Frame::ComputeBoW's mBowVec (ORB/src/Frame.cc:683-694; TemplatedVocabulary.h:1126-1204 with TF_IDF / L1_NORM) for n_frames
@@ -153,15 +195,11 @@ class BatchTracker:
         [n_frames, nfeatures], the words ascending, -1 beyond the count; bow_value: torch.float64 [n_frames, nfeatures]; bow_n:
         torch.int32 [n_frames], -1 for a record index outside the block.  Bit for bit what ORBVocabulary.transform gives on the same
         descriptors.  Asynchronous on the given stream."""
-        n_rec = records.numel() // self.record_bytes
-        n_frames = frames.numel()
-        nf = self.nfeatures
-        assert frames.element_size() == 4 and frames.is_contiguous() and not frames.dtype.is_floating_point
-        assert bow_word.element_size() == 4 and bow_word.is_contiguous() and bow_word.numel() >= n_frames * nf
-        assert bow_value.element_size() == 8 and bow_value.dtype.is_floating_point and bow_value.is_contiguous() and bow_value.numel() >= n_frames * nf
-        assert bow_n.element_size() == 4 and bow_n.is_contiguous() and bow_n.numel() >= n_frames
-        check(self._lib.ivf_tracker_bow_vectors(self._h, vocabulary._h, records.data_ptr(), self.record_bytes, n_rec, frames.data_ptr(), n_frames,
-                                                bow_word.data_ptr(), bow_value.data_ptr(), bow_n.data_ptr(), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        (records_p, n_rec), n_frames = self._records(records), _tensor("frames", frames).numel()
+        check(self._lib.ivf_tracker_bow_vectors(
+            self._h, vocabulary._h, records_p, self.record_bytes, n_rec, p("frames", frames, I32, n_frames), n_frames,
+            p("bow_word", bow_word, I32, n_frames * nf), p("bow_value", bow_value, F64, n_frames * nf), p("bow_n", bow_n, I32, n_frames), stream_ptr))
 
     def reloc_candidates(self, vocabulary, kf_bow_word, kf_bow_value, kf_bow_n, kf_neigh, kf_record, bow_word, bow_value, bow_n, frame_record,
                          cand, ncand, pairs, select, kf_live=None, kf_reloc_score=None, scores=None, common=None, stream_ptr=None):
@@ -177,31 +215,19 @@ class BatchTracker:
         and solve_pnp() start from (n_frames * max_candidates <= max_pairs there); scores: torch.float32 [n_frames, n_keyframes] or None,
         the score of every scored keyframe and the NaN 0x7fc00000 elsewhere; common: torch.int32 [n_frames, n_keyframes] or None
         (mnRelocWords).  Asynchronous on the given stream, no host read."""
-        nf = self.nfeatures
-        n_kf = kf_bow_n.numel()
-        n_frames = bow_n.numel()
-        assert cand.dim() == 2 and cand.shape[0] == n_frames and cand.shape[1] >= 1, "cand is [n_frames, max_candidates]"
-        max_cand = int(cand.shape[1])
-        for w, v, n, m in ((kf_bow_word, kf_bow_value, kf_bow_n, n_kf), (bow_word, bow_value, bow_n, n_frames)):
-            assert w.element_size() == 4 and w.is_contiguous() and w.numel() >= m * nf and n.element_size() == 4 and n.is_contiguous()
-            assert v.element_size() == 8 and v.dtype.is_floating_point and v.is_contiguous() and v.numel() >= m * nf
-        assert kf_neigh.element_size() == 4 and kf_neigh.is_contiguous() and kf_neigh.numel() == n_kf * 10, "kf_neigh is [n_keyframes, 10]"
-        assert kf_record.element_size() == 4 and kf_record.is_contiguous() and kf_record.numel() >= n_kf
-        assert kf_live is None or (kf_live.element_size() == 1 and kf_live.is_contiguous() and kf_live.numel() >= n_kf)
-        assert kf_reloc_score is None or (kf_reloc_score.element_size() == 4 and kf_reloc_score.dtype.is_floating_point and kf_reloc_score.is_contiguous() and kf_reloc_score.numel() >= n_kf)
-        assert frame_record.element_size() == 4 and frame_record.is_contiguous() and frame_record.numel() >= n_frames
-        assert cand.element_size() == 4 and cand.is_contiguous() and ncand.element_size() == 4 and ncand.is_contiguous() and ncand.numel() >= n_frames
-        assert pairs.element_size() == 4 and pairs.is_contiguous() and pairs.numel() >= n_frames * max_cand * 2
-        assert select.element_size() == 4 and select.is_contiguous() and select.numel() >= n_frames * max_cand
-        assert scores is None or (scores.element_size() == 4 and scores.dtype.is_floating_point and scores.is_contiguous() and scores.numel() >= n_frames * n_kf)
-        assert common is None or (common.element_size() == 4 and common.is_contiguous() and common.numel() >= n_frames * n_kf)
-        check(self._lib.ivf_tracker_reloc_candidates(self._h, vocabulary._h, kf_bow_word.data_ptr(), kf_bow_value.data_ptr(), kf_bow_n.data_ptr(),
-                                                     None if kf_live is None else kf_live.data_ptr(), kf_neigh.data_ptr(),
-                                                     None if kf_reloc_score is None else kf_reloc_score.data_ptr(), kf_record.data_ptr(), n_kf,
-                                                     bow_word.data_ptr(), bow_value.data_ptr(), bow_n.data_ptr(), frame_record.data_ptr(), n_frames,
-                                                     max_cand, cand.data_ptr(), ncand.data_ptr(), pairs.data_ptr(), select.data_ptr(),
-                                                     None if scores is None else scores.data_ptr(),
-                                                     None if common is None else common.data_ptr(), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        n_kf, n_frames = _tensor("kf_bow_n", kf_bow_n).numel(), _tensor("bow_n", bow_n).numel()
+        max_cand = int(_tensor("cand", cand, 2, "[n_frames, max_candidates]").shape[1])
+        _require(cand.shape[0] == n_frames and max_cand >= 1, "cand is [n_frames, max_candidates]", cand)
+        check(self._lib.ivf_tracker_reloc_candidates(
+            self._h, vocabulary._h, p("kf_bow_word", kf_bow_word, I32, n_kf * nf), p("kf_bow_value", kf_bow_value, F64, n_kf * nf),
+            p("kf_bow_n", kf_bow_n, I32, n_kf), p("kf_live", kf_live, U8, n_kf, optional=True),
+            p("kf_neigh", kf_neigh, I32, n_kf * KF_NEIGH, exact=True, what=KF_NEIGH_IS),
+            p("kf_reloc_score", kf_reloc_score, F32, n_kf, optional=True), p("kf_record", kf_record, I32, n_kf), n_kf,
+            p("bow_word", bow_word, I32, n_frames * nf), p("bow_value", bow_value, F64, n_frames * nf), p("bow_n", bow_n, I32, n_frames),
+            p("frame_record", frame_record, I32, n_frames), n_frames, max_cand, p("cand", cand, I32, n_frames * max_cand, exact=True),
+            p("ncand", ncand, I32, n_frames), p("pairs", pairs, I32, n_frames * max_cand * 2), p("select", select, I32, n_frames * max_cand),
+            p("scores", scores, F32, n_frames * n_kf, optional=True), p("common", common, I32, n_frames * n_kf, optional=True), stream_ptr))
 
     def search_reloc(self, records, pairs, kf_points, assign, nmatches, th=10.0, orb_dist=100, select=None, poses=None, found=None,
                      check_orientation=True, point_quality=None, key_quality=None, stream_ptr=None):
@@ -215,24 +241,15 @@ class BatchTracker:
         keypoint holds or -1, entries >= 0 on entry are occupied and kept; nmatches: torch.int32 [n_pairs] (nadditional);
         point_quality (by keyframe keypoint) / key_quality (by frame keypoint): torch.float32 [n_pairs, nfeatures] in/out or None.
         Asynchronous on the given stream."""
-        n_rec = records.numel() // self.record_bytes
-        n_pairs = pairs.shape[0]
-        assert pairs.dtype.is_floating_point is False and pairs.element_size() == 4 and pairs.is_contiguous()
-        assert assign.element_size() == 4 and assign.is_contiguous() and assign.numel() >= n_pairs * self.nfeatures and nmatches.numel() >= n_pairs
-        assert select is None or (select.element_size() == 4 and select.is_contiguous() and select.numel() >= n_pairs)
-        assert poses is None or (poses.is_contiguous() and poses.element_size() == 4 and poses.numel() == n_pairs * 12), "poses are per pair: [n_pairs, 12]"
-        assert kf_points.is_contiguous() and kf_points.numel() * kf_points.element_size() >= n_rec * self.nfeatures * 80
-        assert found is None or (found.element_size() == 1 and found.is_contiguous() and found.numel() >= n_pairs * self.nfeatures)
-        for q in (point_quality, key_quality):
-            assert q is None or (q.is_contiguous() and q.element_size() == 4 and q.numel() >= n_pairs * self.nfeatures)
-        check(self._lib.ivf_tracker_search_reloc(self._h, records.data_ptr(), self.record_bytes, n_rec, pairs.data_ptr(), n_pairs,
-                                                 None if select is None else select.data_ptr(),
-                                                 None if poses is None else poses.data_ptr(), kf_points.data_ptr(),
-                                                 None if found is None else found.data_ptr(), float(th), int(orb_dist),
-                                                 int(bool(check_orientation)),
-                                                 None if point_quality is None else point_quality.data_ptr(),
-                                                 None if key_quality is None else key_quality.data_ptr(),
-                                                 assign.data_ptr(), nmatches.data_ptr(), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        (records_p, n_rec), (pairs_p, n_pairs) = self._records(records), self._pairs(pairs)
+        check(self._lib.ivf_tracker_search_reloc(
+            self._h, records_p, self.record_bytes, n_rec, pairs_p, n_pairs, p("select", select, I32, n_pairs, optional=True),
+            p("poses", poses, F32, n_pairs * 12, exact=True, optional=True, what="poses are per pair: [n_pairs, 12]"),
+            p("kf_points", kf_points, BYTES, n_rec * nf * LOCAL_POINT_BYTES), p("found", found, U8, n_pairs * nf, optional=True),
+            float(th), int(orb_dist), int(bool(check_orientation)), p("point_quality", point_quality, F32, n_pairs * nf, optional=True),
+            p("key_quality", key_quality, F32, n_pairs * nf, optional=True), p("assign", assign, I32, n_pairs * nf),
+            p("nmatches", nmatches, I32, n_pairs), stream_ptr))
 
     def filter_assign(self, assign, mask=None, keep_when_set=True, found=None, stream_ptr=None):
         """The set bookkeeping of Tracking::Relocalization around search_reloc(), in place: assign[f, i] = -1 where (mask[f, i] != 0) !=
@@ -240,12 +257,11 @@ class BatchTracker:
         assign[f], 0 elsewhere (found: torch.uint8 [n_frames, nfeatures] or None).  mask = solve_pnp()'s inlier, keep_when_set = True and
         found = sFound: Tracking.cc:2351-2361; mask = optimize_pose()'s outlier, keep_when_set = False: :2368-2370, :2398-2400.
         assign: torch.int32 [n_frames, nfeatures].  Asynchronous on the given stream."""
-        n_frames = assign.numel() // self.nfeatures
-        assert assign.element_size() == 4 and assign.is_contiguous() and assign.numel() == n_frames * self.nfeatures
-        for m in (mask, found):
-            assert m is None or (m.element_size() == 1 and m.is_contiguous() and m.numel() >= n_frames * self.nfeatures)
-        check(self._lib.ivf_tracker_filter_assign(self._h, assign.data_ptr(), n_frames, None if mask is None else mask.data_ptr(),
-                                                  int(bool(keep_when_set)), None if found is None else found.data_ptr(), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        n_frames = _tensor("assign", assign).numel() // nf
+        check(self._lib.ivf_tracker_filter_assign(
+            self._h, p("assign", assign, I32, n_frames * nf, exact=True, what="assign is [n_frames, nfeatures]"), n_frames,
+            p("mask", mask, U8, n_frames * nf, optional=True), int(bool(keep_when_set)), p("found", found, U8, n_frames * nf, optional=True), stream_ptr))
 
     def optimize_pose(self, records, frames, xw, has_point, poses, outlier, ninliers, quality=None, n_rounds=4, chi2=None, stream_ptr=None):
         """Optimizer::PoseOptimization (ORB/src/Optimizer.cc:251-503) for n_frames frames in one kernel launch.  frames: torch.int32
@@ -254,19 +270,13 @@ class BatchTracker:
         score, which scales the edge's Huber width; poses: torch.float32 [n_frames, 12] in/out (mTcw -> the optimised pose);
         outlier: torch.uint8 [n_frames, nfeatures] (mvbOutlier); ninliers: torch.int32 [n_frames]; chi2: torch.float32
         [n_frames, nfeatures] or None (mvChi2 of the last round).  Asynchronous on the given stream."""
-        n_rec = records.numel() // self.record_bytes
-        n_frames = frames.numel()
-        nf = self.nfeatures
-        assert frames.element_size() == 4 and frames.is_contiguous() and poses.is_contiguous() and poses.element_size() == 4 and poses.numel() == n_frames * 12
-        assert xw.is_contiguous() and xw.element_size() == 4 and xw.numel() >= n_frames * nf * 3
-        assert has_point.element_size() == 1 and has_point.numel() >= n_frames * nf and outlier.element_size() == 1 and outlier.numel() >= n_frames * nf
-        assert ninliers.element_size() == 4 and ninliers.numel() >= n_frames
-        for q in (quality, chi2):
-            assert q is None or (q.is_contiguous() and q.element_size() == 4 and q.numel() >= n_frames * nf)
-        check(self._lib.ivf_tracker_optimize_pose(self._h, records.data_ptr(), self.record_bytes, n_rec, frames.data_ptr(), n_frames,
-                                                  xw.data_ptr(), has_point.data_ptr(), None if quality is None else quality.data_ptr(),
-                                                  int(n_rounds), poses.data_ptr(), outlier.data_ptr(), ninliers.data_ptr(),
-                                                  None if chi2 is None else chi2.data_ptr(), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        (records_p, n_rec), n_frames = self._records(records), _tensor("frames", frames).numel()
+        check(self._lib.ivf_tracker_optimize_pose(
+            self._h, records_p, self.record_bytes, n_rec, p("frames", frames, I32, n_frames), n_frames, p("xw", xw, F32, n_frames * nf * 3),
+            p("has_point", has_point, U8, n_frames * nf), p("quality", quality, F32, n_frames * nf, optional=True), int(n_rounds),
+            p("poses", poses, F32, n_frames * 12, exact=True, what="poses are per frame: [n_frames, 12]"), p("outlier", outlier, U8, n_frames * nf),
+            p("ninliers", ninliers, I32, n_frames), p("chi2", chi2, F32, n_frames * nf, optional=True), stream_ptr))
 
     def update_local_map(self, map_view, frame_points, local_kf, n_local_kf, ref_kf, points, point_ids, point_offsets, n_local_points,
                          occupied, stream_ptr=None):
@@ -278,23 +288,19 @@ class BatchTracker:
         max_points_per_frame] (max_points_per_frame = point_ids.shape[1]), point_ids: torch.int32 [n_frames, max_points_per_frame],
         point_offsets: torch.int32 [n_frames + 1] and occupied: torch.uint8 [n_frames, nfeatures], what search_local() takes;
         n_local_points: torch.int32 [n_frames], the true count.  Asynchronous on the given stream, no host read."""
-        nf = self.nfeatures
-        assert isinstance(map_view, MapView), "map_view is an iv_slam_amd.track.MapView"
-        assert frame_points.dim() == 2 and frame_points.shape[1] == nf, "frame_points is [n_frames, nfeatures]"
-        n_frames = int(frame_points.shape[0])
-        assert local_kf.dim() == 2 and local_kf.shape[0] == n_frames and local_kf.shape[1] >= 1, "local_kf is [n_frames, max_local_keyframes]"
-        assert point_ids.dim() == 2 and point_ids.shape[0] == n_frames and point_ids.shape[1] >= 1, "point_ids is [n_frames, max_points_per_frame]"
-        max_lk, max_pts = int(local_kf.shape[1]), int(point_ids.shape[1])
-        for x in (frame_points, local_kf, n_local_kf, ref_kf, point_ids, point_offsets, n_local_points):
-            assert x.element_size() == 4 and x.is_contiguous() and not x.dtype.is_floating_point
-        assert n_local_kf.numel() >= n_frames and ref_kf.numel() >= n_frames and n_local_points.numel() >= n_frames
-        assert point_offsets.numel() >= n_frames + 1
-        assert points.is_contiguous() and points.numel() * points.element_size() >= n_frames * max_pts * 80
-        assert occupied.element_size() == 1 and occupied.is_contiguous() and occupied.numel() >= n_frames * nf
-        check(self._lib.ivf_tracker_update_local_map(self._h, C.byref(map_view.c), frame_points.data_ptr(), n_frames, max_lk, max_pts,
-                                                     local_kf.data_ptr(), n_local_kf.data_ptr(), ref_kf.data_ptr(), points.data_ptr(),
-                                                     point_ids.data_ptr(), point_offsets.data_ptr(), n_local_points.data_ptr(),
-                                                     occupied.data_ptr(), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        n_frames = int(_tensor("frame_points", frame_points, 2, "[n_frames, nfeatures]").shape[0])
+        max_lk = int(_tensor("local_kf", local_kf, 2, "[n_frames, max_local_keyframes]").shape[1])
+        max_pts = int(_tensor("point_ids", point_ids, 2, "[n_frames, max_points_per_frame]").shape[1])
+        _require(frame_points.shape[1] == nf, "frame_points is [n_frames, nfeatures]", frame_points)
+        _require(local_kf.shape[0] == n_frames and max_lk >= 1, "local_kf is [n_frames, max_local_keyframes]", local_kf)
+        _require(point_ids.shape[0] == n_frames and max_pts >= 1, "point_ids is [n_frames, max_points_per_frame]", point_ids)
+        check(self._lib.ivf_tracker_update_local_map(
+            self._h, C.byref(self._view(map_view)), p("frame_points", frame_points, I32, n_frames * nf, exact=True), n_frames, max_lk, max_pts,
+            p("local_kf", local_kf, I32, n_frames * max_lk, exact=True), p("n_local_kf", n_local_kf, I32, n_frames), p("ref_kf", ref_kf, I32, n_frames),
+            p("points", points, BYTES, n_frames * max_pts * LOCAL_POINT_BYTES), p("point_ids", point_ids, I32, n_frames * max_pts, exact=True),
+            p("point_offsets", point_offsets, I32, n_frames + 1), p("n_local_points", n_local_points, I32, n_frames),
+            p("occupied", occupied, U8, n_frames * nf), stream_ptr))
 
     def create_map_points(self, vocabulary, records, kf, neigh, poses, has_point, new_point, new_neigh, new_idx2, new_order, new_quality, n_new,
                           levelsup=4, key_quality=None, F12=None, kf_order=None, matches=None, stage=None, stream_ptr=None):
@@ -310,73 +316,55 @@ class BatchTracker:
         new_idx2, new_order: torch.int32 [n_kf, nfeatures]; new_quality: torch.float32 [n_kf, nfeatures]; n_new: torch.int32 [n_kf];
         matches: torch.int32 and stage: torch.uint8 [n_kf, max_neigh, nfeatures] or None.  Slots are independent: each sees has_point
         as on entry.  Asynchronous on the given stream, no host read."""
-        nf = self.nfeatures
-        n_rec = records.numel() // self.record_bytes
-        assert neigh.dim() == 2 and neigh.shape[1] >= 1, "neigh is [n_kf, max_neigh]"
-        n_kf, max_neigh = int(neigh.shape[0]), int(neigh.shape[1])
-        for x in (kf, neigh, new_neigh, new_idx2, new_order, n_new, kf_order, matches):
-            assert x is None or (x.element_size() == 4 and x.is_contiguous() and not x.dtype.is_floating_point)
-        assert kf.numel() == n_kf and n_new.numel() >= n_kf
-        assert poses.is_contiguous() and poses.element_size() == 4 and poses.numel() == n_rec * 12, "poses are per RECORD: [n_records, 12]"
-        assert has_point.element_size() == 1 and has_point.is_contiguous() and has_point.numel() >= n_rec * nf
-        assert key_quality is None or (key_quality.is_contiguous() and key_quality.element_size() == 4 and key_quality.numel() >= n_rec * nf)
-        assert F12 is None or (F12.is_contiguous() and F12.element_size() == 4 and F12.numel() == n_kf * max_neigh * 9), "F12 is [n_kf, max_neigh, 9]"
-        assert kf_order is None or kf_order.numel() == n_rec, "kf_order is [n_records]"
-        assert new_point.is_contiguous() and new_point.numel() * new_point.element_size() >= n_kf * nf * 80
-        for x in (new_neigh, new_idx2, new_order):
-            assert x.numel() >= n_kf * nf
-        assert new_quality.is_contiguous() and new_quality.element_size() == 4 and new_quality.numel() >= n_kf * nf
-        assert matches is None or matches.numel() >= n_kf * max_neigh * nf
-        assert stage is None or (stage.element_size() == 1 and stage.is_contiguous() and stage.numel() >= n_kf * max_neigh * nf)
-        opt = lambda x: None if x is None else x.data_ptr()
-        check(self._lib.ivf_tracker_create_map_points(self._h, vocabulary._h, int(levelsup), records.data_ptr(), self.record_bytes, n_rec,
-                                                      kf.data_ptr(), n_kf, neigh.data_ptr(), max_neigh, poses.data_ptr(), has_point.data_ptr(),
-                                                      opt(key_quality), opt(F12), opt(kf_order), new_point.data_ptr(), new_neigh.data_ptr(),
-                                                      new_idx2.data_ptr(), new_order.data_ptr(), new_quality.data_ptr(), n_new.data_ptr(),
-                                                      opt(matches), opt(stage), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        records_p, n_rec = self._records(records)
+        n_kf, max_neigh = map(int, _tensor("neigh", neigh, 2, "[n_kf, max_neigh]").shape)
+        _require(max_neigh >= 1, "neigh is [n_kf, max_neigh]", neigh)
+        check(self._lib.ivf_tracker_create_map_points(
+            self._h, vocabulary._h, int(levelsup), records_p, self.record_bytes, n_rec, p("kf", kf, I32, n_kf, exact=True, what="kf is [n_kf]"), n_kf,
+            p("neigh", neigh, I32, n_kf * max_neigh, exact=True), max_neigh,
+            p("poses", poses, F32, n_rec * 12, exact=True, what="poses are per RECORD: [n_records, 12]"), p("has_point", has_point, U8, n_rec * nf),
+            p("key_quality", key_quality, F32, n_rec * nf, optional=True),
+            p("F12", F12, F32, n_kf * max_neigh * 9, exact=True, optional=True, what="F12 is [n_kf, max_neigh, 9]"),
+            p("kf_order", kf_order, I32, n_rec, exact=True, optional=True, what="kf_order is [n_records]"),
+            p("new_point", new_point, BYTES, n_kf * nf * LOCAL_POINT_BYTES), p("new_neigh", new_neigh, I32, n_kf * nf),
+            p("new_idx2", new_idx2, I32, n_kf * nf), p("new_order", new_order, I32, n_kf * nf), p("new_quality", new_quality, F32, n_kf * nf),
+            p("n_new", n_new, I32, n_kf), p("matches", matches, I32, n_kf * max_neigh * nf, optional=True),
+            p("stage", stage, U8, n_kf * max_neigh * nf, optional=True), stream_ptr))
 
     def merge_local(self, point_ids, point_offsets, assign, frame_points, stream_ptr=None):
         """ORBmatcher.cc:124 after search_local(): frame_points[f, i] = point_ids[point_offsets[f] + assign[f, i]] where assign >= 0.
         point_ids / point_offsets as update_local_map() wrote them; frame_points: torch.int32 [n_frames, nfeatures] in/out.  Asynchronous."""
-        n_frames = frame_points.numel() // self.nfeatures
-        assert frame_points.element_size() == 4 and frame_points.is_contiguous() and frame_points.numel() == n_frames * self.nfeatures
-        assert point_offsets.element_size() == 4 and point_offsets.is_contiguous() and point_offsets.numel() >= n_frames + 1
-        assert point_ids.element_size() == 4 and point_ids.is_contiguous()
-        assert assign.element_size() == 4 and assign.is_contiguous() and assign.numel() >= n_frames * self.nfeatures
-        check(self._lib.ivf_tracker_merge_local(self._h, point_ids.data_ptr(), point_offsets.data_ptr(), assign.data_ptr(), n_frames,
-                                                frame_points.data_ptr(), stream_ptr))
+        p, nf = partial(_ptr, self.device), self.nfeatures
+        n_frames = _tensor("frame_points", frame_points).numel() // nf
+        # point_ids is update_local_map()'s [n_frames, max_points_per_frame >= 1], the width not told here: one entry per frame at least
+        check(self._lib.ivf_tracker_merge_local(
+            self._h, p("point_ids", point_ids, I32, n_frames), p("point_offsets", point_offsets, I32, n_frames + 1), p("assign", assign, I32, n_frames * nf), n_frames,
+            p("frame_points", frame_points, I32, n_frames * nf, exact=True, what="frame_points is [n_frames, nfeatures]"), stream_ptr))
 
     def points_from_map(self, map_view, frame_points, xw, has_point, quality=None, point_quality=None, stream_ptr=None):
         """optimize_pose()'s input over ALL the points a frame holds: xw[f, i] = GetWorldPos() of map point frame_points[f, i],
         has_point = 1 where there is one; quality: torch.float32 [n_frames, nfeatures] or None, the held point's entry of point_quality
         (torch.float32 [n_points], None = 1).  Asynchronous."""
-        nf = self.nfeatures
-        assert isinstance(map_view, MapView), "map_view is an iv_slam_amd.track.MapView"
-        n_frames = frame_points.numel() // nf
-        assert frame_points.element_size() == 4 and frame_points.is_contiguous() and frame_points.numel() == n_frames * nf
-        assert xw.element_size() == 4 and xw.is_contiguous() and xw.numel() >= n_frames * nf * 3
-        assert has_point.element_size() == 1 and has_point.numel() >= n_frames * nf
-        assert quality is None or (quality.is_contiguous() and quality.element_size() == 4 and quality.numel() >= n_frames * nf)
-        assert point_quality is None or (point_quality.is_contiguous() and point_quality.element_size() == 4 and point_quality.numel() >= map_view.c.n_points)
-        check(self._lib.ivf_tracker_points_from_map(self._h, map_view.c.points, map_view.c.n_points,
-                                                    None if point_quality is None else point_quality.data_ptr(), frame_points.data_ptr(),
-                                                    n_frames, xw.data_ptr(), has_point.data_ptr(),
-                                                    None if quality is None else quality.data_ptr(), stream_ptr))
+        p, nf, view = partial(_ptr, self.device), self.nfeatures, self._view(map_view)
+        n_frames = _tensor("frame_points", frame_points).numel() // nf
+        check(self._lib.ivf_tracker_points_from_map(
+            self._h, view.points, view.n_points, p("point_quality", point_quality, F32, view.n_points, optional=True),
+            p("frame_points", frame_points, I32, n_frames * nf, exact=True, what="frame_points is [n_frames, nfeatures]"), n_frames,
+            p("xw", xw, F32, n_frames * nf * 3), p("has_point", has_point, U8, n_frames * nf),
+            p("quality", quality, F32, n_frames * nf, optional=True), stream_ptr))
 
     def close_local_map(self, map_view, outlier, frame_points, ninliers, only_tracking=False, stereo=True, stream_ptr=None):
         """The statistics loop of TrackLocalMap (ORB/src/Tracking.cc:1648-1677): ninliers[f] = held points optimize_pose() did not flag
         (with only_tracking False only those with Observations() > 0); with stereo an outlier's entry of frame_points becomes -1.
         outlier: torch.uint8 [n_frames, nfeatures]; frame_points: torch.int32 [n_frames, nfeatures] in/out; ninliers: torch.int32
         [n_frames].  The 30 / 50 decision is the caller's.  Asynchronous."""
-        nf = self.nfeatures
-        assert isinstance(map_view, MapView), "map_view is an iv_slam_amd.track.MapView"
-        n_frames = frame_points.numel() // nf
-        assert frame_points.element_size() == 4 and frame_points.is_contiguous() and frame_points.numel() == n_frames * nf
-        assert outlier.element_size() == 1 and outlier.is_contiguous() and outlier.numel() >= n_frames * nf
-        assert ninliers.element_size() == 4 and ninliers.is_contiguous() and ninliers.numel() >= n_frames
-        check(self._lib.ivf_tracker_close_local_map(self._h, map_view.c.points, map_view.c.n_points, outlier.data_ptr(), n_frames,
-                                                    int(bool(only_tracking)), int(bool(stereo)), frame_points.data_ptr(), ninliers.data_ptr(),
-                                                    stream_ptr))
+        p, nf, view = partial(_ptr, self.device), self.nfeatures, self._view(map_view)
+        n_frames = _tensor("frame_points", frame_points).numel() // nf
+        check(self._lib.ivf_tracker_close_local_map(
+            self._h, view.points, view.n_points, p("outlier", outlier, U8, n_frames * nf), n_frames, int(bool(only_tracking)), int(bool(stereo)),
+            p("frame_points", frame_points, I32, n_frames * nf, exact=True, what="frame_points is [n_frames, nfeatures]"),
+            p("ninliers", ninliers, I32, n_frames), stream_ptr))
 
     def solve_pnp(self, records, frames, xw, has_point, draws, poses, inlier, ninliers, max_iterations=300, probability=0.99, min_inliers=10,
                   epsilon=0.5, th2=5.991, iterations=None, hyp_poses=None, hyp_ninliers=None, stream_ptr=None):
@@ -389,24 +377,16 @@ class BatchTracker:
         ninliers: torch.int32 [n_frames] (0: no pose, -1: bad record index); iterations: torch.int32 [n_frames] or None (mnIterations);
         hyp_poses: torch.float32 [n_frames, max_iterations, 12] and hyp_ninliers: torch.int32 [n_frames, max_iterations] or None: every
         hypothesis.  has_point & inlier is the has_point of the optimize_pose() that follows.  Asynchronous on the given stream."""
-        n_rec = records.numel() // self.record_bytes
-        n_frames = frames.numel()
-        nf = self.nfeatures
-        mi = int(max_iterations)
-        assert frames.element_size() == 4 and frames.is_contiguous() and poses.is_contiguous() and poses.element_size() == 4 and poses.numel() == n_frames * 12
-        assert xw.is_contiguous() and xw.element_size() == 4 and xw.numel() >= n_frames * nf * 3
-        assert has_point.element_size() == 1 and has_point.numel() >= n_frames * nf and inlier.element_size() == 1 and inlier.numel() >= n_frames * nf
-        assert draws.is_contiguous() and draws.element_size() == 4 and draws.numel() >= n_frames * mi * 4, "draws are [n_frames, max_iterations, 4]"
-        assert ninliers.element_size() == 4 and ninliers.numel() >= n_frames
-        assert iterations is None or (iterations.element_size() == 4 and iterations.numel() >= n_frames)
-        assert hyp_poses is None or (hyp_poses.is_contiguous() and hyp_poses.element_size() == 4 and hyp_poses.numel() >= n_frames * mi * 12)
-        assert hyp_ninliers is None or (hyp_ninliers.is_contiguous() and hyp_ninliers.element_size() == 4 and hyp_ninliers.numel() >= n_frames * mi)
-        check(self._lib.ivf_tracker_solve_pnp(self._h, records.data_ptr(), self.record_bytes, n_rec, frames.data_ptr(), n_frames,
-                                              xw.data_ptr(), has_point.data_ptr(), draws.data_ptr(), mi, float(probability), int(min_inliers),
-                                              float(epsilon), float(th2), poses.data_ptr(), inlier.data_ptr(), ninliers.data_ptr(),
-                                              None if iterations is None else iterations.data_ptr(),
-                                              None if hyp_poses is None else hyp_poses.data_ptr(),
-                                              None if hyp_ninliers is None else hyp_ninliers.data_ptr(), stream_ptr))
+        p, nf, mi = partial(_ptr, self.device), self.nfeatures, int(max_iterations)
+        (records_p, n_rec), n_frames = self._records(records), _tensor("frames", frames).numel()
+        check(self._lib.ivf_tracker_solve_pnp(
+            self._h, records_p, self.record_bytes, n_rec, p("frames", frames, I32, n_frames), n_frames, p("xw", xw, F32, n_frames * nf * 3),
+            p("has_point", has_point, U8, n_frames * nf), p("draws", draws, ANY4, n_frames * mi * 4, what="draws are [n_frames, max_iterations, 4]"),
+            mi, float(probability), int(min_inliers), float(epsilon), float(th2),
+            p("poses", poses, F32, n_frames * 12, exact=True, what="poses are per frame: [n_frames, 12]"), p("inlier", inlier, U8, n_frames * nf),
+            p("ninliers", ninliers, I32, n_frames), p("iterations", iterations, I32, n_frames, optional=True),
+            p("hyp_poses", hyp_poses, F32, n_frames * mi * 12, optional=True), p("hyp_ninliers", hyp_ninliers, I32, n_frames * mi, optional=True),
+            stream_ptr))
 
     def solve_sim3(self, records, pairs, poses, kf_xw, point_flags, match12, draws, sim3, inlier, ninliers, max_iterations=300, probability=0.99,
                    min_inliers=20, fix_scale=True, select=None, state=None, iterations=None, hyp_sim3=None, hyp_ninliers=None, stream_ptr=None):
@@ -425,29 +405,20 @@ class BatchTracker:
         (mnIterations on return); hyp_sim3: torch.float32 [n_pairs, max_iterations, 16] and hyp_ninliers: torch.int32
         [n_pairs, max_iterations] or None: every hypothesis from the state's iteration to mRansacMaxIts.  (s12 R12, t12) is what ivf_search_by_sim3 takes next.
         Asynchronous on the given stream."""
-        n_rec = records.numel() // self.record_bytes
-        n_pairs = pairs.shape[0]
-        nf = self.nfeatures
-        mi = int(max_iterations)
-        for x in (pairs, match12, ninliers, select, state, iterations, hyp_ninliers):
-            assert x is None or (x.element_size() == 4 and x.is_contiguous() and not x.dtype.is_floating_point)
-        assert poses.is_contiguous() and poses.element_size() == 4 and poses.numel() == n_rec * 12, "poses are per RECORD: [n_records, 12]"
-        assert kf_xw.is_contiguous() and kf_xw.element_size() == 4 and kf_xw.numel() == n_rec * nf * 3, "kf_xw is [n_records, nfeatures, 3]"
-        assert point_flags.element_size() == 1 and point_flags.is_contiguous() and point_flags.numel() >= n_rec * nf
-        assert match12.numel() >= n_pairs * nf and ninliers.numel() >= n_pairs
-        assert draws.is_contiguous() and draws.element_size() == 4 and draws.numel() >= n_pairs * mi * 3, "draws are [n_pairs, max_iterations, 3]"
-        assert sim3.is_contiguous() and sim3.element_size() == 4 and sim3.numel() == n_pairs * 16, "sim3 is [n_pairs, 16]"
-        assert inlier.element_size() == 1 and inlier.is_contiguous() and inlier.numel() >= n_pairs * nf
-        assert select is None or select.numel() >= n_pairs
-        assert state is None or state.numel() == n_pairs * 2, "state is [n_pairs, 2]"
-        assert iterations is None or iterations.numel() >= n_pairs
-        assert hyp_sim3 is None or (hyp_sim3.is_contiguous() and hyp_sim3.element_size() == 4 and hyp_sim3.numel() >= n_pairs * mi * 16)
-        assert hyp_ninliers is None or hyp_ninliers.numel() >= n_pairs * mi
-        opt = lambda x: None if x is None else x.data_ptr()
-        check(self._lib.ivf_tracker_solve_sim3(self._h, records.data_ptr(), self.record_bytes, n_rec, pairs.data_ptr(), n_pairs, opt(select),
-                                               poses.data_ptr(), kf_xw.data_ptr(), point_flags.data_ptr(), match12.data_ptr(), draws.data_ptr(), mi,
-                                               float(probability), int(min_inliers), int(bool(fix_scale)), opt(state), sim3.data_ptr(),
-                                               inlier.data_ptr(), ninliers.data_ptr(), opt(iterations), opt(hyp_sim3), opt(hyp_ninliers), stream_ptr))
+        p, nf, mi = partial(_ptr, self.device), self.nfeatures, int(max_iterations)
+        (records_p, n_rec), (pairs_p, n_pairs) = self._records(records), self._pairs(pairs)
+        check(self._lib.ivf_tracker_solve_sim3(
+            self._h, records_p, self.record_bytes, n_rec, pairs_p, n_pairs, p("select", select, I32, n_pairs, optional=True),
+            p("poses", poses, F32, n_rec * 12, exact=True, what="poses are per RECORD: [n_records, 12]"),
+            p("kf_xw", kf_xw, F32, n_rec * nf * 3, exact=True, what="kf_xw is [n_records, nfeatures, 3]"),
+            p("point_flags", point_flags, U8, n_rec * nf), p("match12", match12, I32, n_pairs * nf),
+            p("draws", draws, ANY4, n_pairs * mi * 3, what="draws are [n_pairs, max_iterations, 3]"),
+            mi, float(probability), int(min_inliers), int(bool(fix_scale)),
+            p("state", state, I32, n_pairs * 2, exact=True, optional=True, what="state is [n_pairs, 2]"),
+            p("sim3", sim3, F32, n_pairs * 16, exact=True, what="sim3 is [n_pairs, 16]"), p("inlier", inlier, U8, n_pairs * nf),
+            p("ninliers", ninliers, I32, n_pairs), p("iterations", iterations, I32, n_pairs, optional=True),
+            p("hyp_sim3", hyp_sim3, F32, n_pairs * mi * 16, optional=True), p("hyp_ninliers", hyp_ninliers, I32, n_pairs * mi, optional=True),
+            stream_ptr))
 
 
 def local_map_lds_keyframes():
@@ -467,22 +438,25 @@ class MapView:
 
     def __init__(self, points, obs_offsets, obs_kf, kf_point_offsets, kf_points, kf_neigh, kf_child_offsets, kf_children, kf_parent,
                  kf_live=None, kf_order=None):
-        n_points, n_kf = obs_offsets.numel() - 1, kf_parent.numel()
-        for x in (obs_offsets, obs_kf, kf_point_offsets, kf_points, kf_neigh, kf_child_offsets, kf_children, kf_parent, kf_order):
-            assert x is None or (x.element_size() == 4 and x.is_contiguous() and not x.dtype.is_floating_point), "index tables are contiguous int32"
-        assert n_points >= 0 and points.is_contiguous() and points.numel() * points.element_size() == n_points * 80, "points / obs_offsets disagree"
-        assert kf_point_offsets.numel() == n_kf + 1 and kf_child_offsets.numel() == n_kf + 1, "offset tables are [n_keyframes + 1]"
-        assert kf_neigh.numel() == n_kf * 10, "kf_neigh is [n_keyframes, 10]"
-        assert kf_live is None or (kf_live.element_size() == 1 and kf_live.is_contiguous() and kf_live.numel() == n_kf)
-        assert kf_order is None or kf_order.numel() == n_kf, "kf_order is [n_keyframes]"
+        n_points, n_kf = _tensor("obs_offsets", obs_offsets).numel() - 1, _tensor("kf_parent", kf_parent).numel()
+        n_obs, n_kf_points, n_children = _tensor("obs_kf", obs_kf).numel(), _tensor("kf_points", kf_points).numel(), _tensor("kf_children", kf_children).numel()
+        _require(n_points >= 0, "obs_offsets is [n_points + 1]", obs_offsets)
+        self.device = _tensor("points", points).device                       # every table lives where the points do
+
+        def p(name, x, kind, count, **kw):                                   # an empty table reaches the library as NULL
+            ptr = _ptr(self.device, name, x, kind, count, exact=True, **kw)
+            return ptr if count else None
+        self.c = _lib.MapViewC(
+            points=p("points", points, BYTES, n_points * LOCAL_POINT_BYTES, what="points / obs_offsets disagree"),
+            obs_offsets=p("obs_offsets", obs_offsets, I32, n_points + 1), obs_kf=p("obs_kf", obs_kf, I32, n_obs),
+            kf_point_offsets=p("kf_point_offsets", kf_point_offsets, I32, n_kf + 1, what="offset tables are [n_keyframes + 1]"),
+            kf_points=p("kf_points", kf_points, I32, n_kf_points),
+            kf_live=p("kf_live", kf_live, U8, n_kf, optional=True), kf_neigh=p("kf_neigh", kf_neigh, I32, n_kf * KF_NEIGH, what=KF_NEIGH_IS),
+            kf_child_offsets=p("kf_child_offsets", kf_child_offsets, I32, n_kf + 1, what="offset tables are [n_keyframes + 1]"),
+            kf_children=p("kf_children", kf_children, I32, n_children), kf_parent=p("kf_parent", kf_parent, I32, n_kf),
+            kf_order=p("kf_order", kf_order, I32, n_kf, optional=True, what="kf_order is [n_keyframes]"),
+            n_points=n_points, n_keyframes=n_kf, n_obs=n_obs, n_kf_points=n_kf_points, n_children=n_children)
         self._keep = (points, obs_offsets, obs_kf, kf_point_offsets, kf_points, kf_neigh, kf_child_offsets, kf_children, kf_parent, kf_live, kf_order)
-        c = _lib.MapViewC()
-        for name, x in zip(("points", "obs_offsets", "obs_kf", "kf_point_offsets", "kf_points", "kf_neigh", "kf_child_offsets", "kf_children",
-                            "kf_parent", "kf_live", "kf_order"), self._keep):
-            setattr(c, name, None if x is None or x.numel() == 0 else x.data_ptr())
-        c.n_points, c.n_keyframes = n_points, n_kf
-        c.n_obs, c.n_kf_points, c.n_children = obs_kf.numel(), kf_points.numel(), kf_children.numel()
-        self.c = c
         self.n_points, self.n_keyframes = n_points, n_kf
 
 

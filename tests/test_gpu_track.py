@@ -500,6 +500,25 @@ def test_tracker_argument_checks(iv):
     assert (nm.cpu().numpy()[:2] == 0).all() and (out.cpu().numpy()[:2] == -1).all()
 
 
+def test_a_wrong_tensor_is_refused_before_any_launch(iv):
+    """a host address, a tensor of another kind or a strided view never reaches the library; the handle is as good as before afterwards"""
+    import torch
+    nf, dev = 64, torch.device("cuda:0")
+    tr = iv.BatchTracker(nf, scale_table(), 700.0, 700.0, 600.0, 180.0, 386.0, (0.0, 0.0, 1242.0, 375.0), max_pairs=1)
+    assert tr.device == dev and tr.device_id == 0
+    blk = torch.zeros(2 * tr.record_bytes, dtype=torch.uint8, device=dev)
+    pairs = torch.tensor([[0, 1]], dtype=torch.int32, device=dev)
+    out = torch.full((1, nf), -7, dtype=torch.int32, device=dev); nm = torch.full((1,), -7, dtype=torch.int32, device=dev)
+    launches = iv.load().ivf_debug_launch_count()
+    for bad in (dict(pairs=pairs.cpu()), dict(assign=out.float()), dict(records=torch.zeros(4 * tr.record_bytes, dtype=torch.uint8, device=dev)[::2])):
+        with pytest.raises(AssertionError, match=next(iter(bad))):
+            tr.run(**dict(dict(records=blk, pairs=pairs, assign=out, nmatches=nm), **bad))
+    assert iv.load().ivf_debug_launch_count() == launches, "nothing was launched"
+    tr.run(blk, pairs, out, nm)                                             # empty records: no matches
+    torch.cuda.synchronize()
+    assert iv.load().ivf_debug_launch_count() > launches and nm.item() == 0 and (out.cpu().numpy() == -1).all()
+
+
 def test_one_handle_on_several_streams_serialises_its_runs(iv):
     """the handle's scratch belongs to one run at a time: runs enqueued back to back on DIFFERENT streams (what a pipelined
     caller does) must not overlap in it -- same results as one run at a time."""
