@@ -712,7 +712,7 @@ int  ivf_tracker_solve_pnp(ivf_tracker* t, const uint8_t* d_records, size_t reco
  * ivf_tracker_search_by_bow; d_poses [n_records][12] = Tcw of every record (row-major 3x4) as ivf_tracker_create_map_points takes it;
  * d_kf_xw [n_records][nfeatures][3] = GetWorldPos() as ivf_tracker_points_from_keyframe takes it; d_point_flags
  * [n_records][nfeatures], bit 0 = the keypoint holds a live map point; d_match12 [n_pairs][nfeatures] = vpMatched12 as indices: the
- * KF2 keypoint whose point KF1 keypoint i1 is matched to, or -1 (what ivf_search_by_bow_keyframes returns).
+ * KF2 keypoint whose point KF1 keypoint i1 is matched to, or -1 (the array ivf_tracker_search_by_bow_keyframes writes).
  * The constructor (Sim3Solver.cc:40-115): for i1 ascending below KF1's count a correspondence is collected when d_match12[p][i1] = i2
  * >= 0, i2 is below KF2's count and both keypoints hold a live point (:67-76); GetIndexInKeyFrame (:78-82) is taken to be i1 / i2, the
  * keypoint that holds the point.  mvX3Dc = Rcw * Xw + tcw per side (:97-101); mvnMaxError = 9.210 * mvLevelSigma2[octave] computed in
@@ -749,6 +749,57 @@ int  ivf_tracker_solve_sim3(ivf_tracker* t, const uint8_t* d_records, size_t rec
                             const int32_t* d_match12, const uint32_t* d_draws, int max_iterations, double probability, int min_inliers,
                             int fix_scale, int32_t* d_state, float* d_sim3, uint8_t* d_inlier, int32_t* d_ninliers, int32_t* d_iterations,
                             float* d_hyp_sim3, int32_t* d_hyp_ninliers, void* hip_stream);
+/* The two searches around that solver in LoopClosing::ComputeSim3 (ORB/src/LoopClosing.cc:236-405), on the device: with them the chain
+ * runs from a candidate pair of gather records to the full correspondence set of OptimizeSim3 without the host reading anything.  Both
+ * take pair p = (KF1 = d_pairs[p][0], KF2 = d_pairs[p][1]) and d_select as ivf_tracker_search_by_bow does, except that a pair left out
+ * is left alone: d_select 0 gives -2 in the count output, a record index outside [0, n_records) gives -1, and nothing else of such a pair
+ * is written.  Asynchronous on hip_stream, one call of the handle at a time, no host synchronisation -- except in the first
+ * ivf_tracker_search_by_sim3 of a handle, which enlarges the grid scratch and waits on the host for the handle's previous call first; every loop is bounded by nfeatures,
+ * by the grid or by the node count, so a NaN pose or a NaN similarity cannot hang a launch; two runs are bit-identical.
+ *
+ * ivf_tracker_search_by_bow_keyframes: ORBmatcher(nn_ratio, check_orientation).SearchByBoW(pKF1, pKF2, vpMatches12)
+ * (ORB/src/ORBmatcher.cc:528-661; LoopClosing.cc:270 calls it with 0.75, true).  The feature vectors of both records are computed in
+ * the call as ivf_tracker_search_by_bow computes them (same descent, same sort, same scratch), and the search is that call's kernel body
+ * with the differences of this overload: a KF2 candidate must itself hold a live point (:580-586); the occupancy is vbMatched2, by KF2
+ * keypoint; the acceptance is bestDist1 < TH_LOW, strictly (:604); the histogram takes angle1 - angle2 (:613); a match the rotation
+ * filter removes is cleared in vpMatches12 only (:654).  d_point_flags [n_records][nfeatures] (nullable), bit 0 = the keypoint holds a
+ * live map point, read for both sides; NULL: every keypoint with a stereo depth holds one, on both sides.
+ * d_match12 [n_pairs][nfeatures], by KF1 keypoint: the KF2 keypoint whose point it is matched to, or -1 -- the array
+ * ivf_tracker_solve_sim3 reads; d_nmatches [n_pairs] = the return value.  Results equal ivf_bow_transform + ivf_bow_vectors +
+ * ivf_search_by_bow_keyframes on the same data, bit for bit.  IVF_E_INVALID as ivf_tracker_search_by_bow. */
+int  ivf_tracker_search_by_bow_keyframes(ivf_tracker* t, const ivf_vocabulary* voc, int levelsup,
+                                         const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_pairs, int n_pairs,
+                                         const int32_t* d_select, const uint8_t* d_point_flags, float nn_ratio, int check_orientation,
+                                         int32_t* d_match12, int32_t* d_nmatches, void* hip_stream);
+/* ivf_tracker_search_by_sim3: ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (ORB/src/ORBmatcher.cc:1145-1369)
+ * INCLUDING both projection loops, behind the inlier filter of LoopClosing.cc:318-323.  d_select: the caller derives it on the device
+ * from ivf_tracker_solve_sim3's d_ninliers > 0 (d_sim3 is unwritten for a failed pair).  d_poses [n_records][12] as
+ * ivf_tracker_solve_sim3 takes it; d_kf_points [n_records][nfeatures] (16-byte aligned) as ivf_tracker_search_reloc takes it: pos,
+ * min_distance, max_distance and desc are read, flags bit 0 = no point / isBad(); d_sim3 [n_pairs][16] as ivf_tracker_solve_sim3 writes
+ * it; d_match12 [n_pairs][nfeatures]; d_inlier [n_pairs][nfeatures] (nullable; NULL: every match is kept); th: the reference passes 7.5.
+ * Per pair: vpMatches12[i1] = d_match12[p][i1] where d_inlier is set, else none; vbAlreadyMatched1 / 2 (:1175-1185) with
+ * GetIndexInKeyFrame taken to be the keypoint index itself (as ivf_tracker_solve_sim3 does), an index outside KF2's count marks nothing
+ * there.  Direction 1 -> 2 (:1191-1268), for every KF1 keypoint in this order: skipped without a point, with a bad one or an already
+ * matched one; p3Dc1 = R1w * xw + t1w, p3Dc2 = sR21 * p3Dc1 + t21; skipped on z < 0.0 (a zero depth goes on: its infinite or NaN
+ * projection fails the next test); invz = 1.0 / z in double, narrowed once; u = fx * (x * invz) + cx, v likewise, with the HANDLE's
+ * intrinsics in both directions (the reference uses KF1's for both); KeyFrame::IsInImage (KeyFrame.cc:647-650): >= min and < max,
+ * strictly; dist3D = cv::norm(p3Dc2), the camera-frame norm, inside [0.8f * min_distance, 1.2f * max_distance]; MapPoint::PredictScale;
+ * radius = th * scale[level]; the window of KeyFrame::GetFeaturesInArea (KeyFrame.cc:606-645) on octaves [level - 1, level]; the FIRST
+ * minimum of the descriptor distance, with no occupancy test, accepted at <= TH_HIGH (100).  Direction 2 -> 1 (:1271-1348) is the mirror
+ * image with sR12, t12 and vbAlreadyMatched2.  Then the agreement check (:1350-1366).
+ * Arithmetic: matrix * vector products accumulate in double and narrow once, R * x + t in one accumulation;
+ * sR12[k] = (float)((double)s12 * R12[k]); sR21[k] = (float)((1.0 / (double)s12) * R12^T[k]); t21 = -(sR21 * t12); the norm accumulates in
+ * double, then sqrt, then narrows; nothing is fused.  OpenCV's own rounding of scalar * Mat is not pinned by the reference.
+ * Outputs: d_matches [n_pairs][nfeatures] = vpMatches12 on return as KF2 keypoint indices by KF1 keypoint: the filtered input entries
+ * plus the agreed new ones, -1 elsewhere and past KF1's count; it may not alias d_match12.  d_nfound [n_pairs] = the return value.
+ * d_match1 / d_match2 [n_pairs][nfeatures] (nullable) = vnMatch1 / vnMatch2.  IVF_E_INVALID: a null required pointer, th <= 0, d_matches
+ * == d_match12, n_pairs > max_pairs.  Uses the handle's grid scratch with two grids per pair (grown at the first call: the new buffers
+ * are allocated before the old ones are freed, so a failure, IVF_E_NO_DEVICE, leaves the handle usable) and a query scratch of its own of
+ * 2 * nfeatures queries per pair, allocated at the first call. */
+int  ivf_tracker_search_by_sim3(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_pairs, int n_pairs,
+                                const int32_t* d_select, const float* d_poses, const ivf_local_point* d_kf_points, const float* d_sim3,
+                                const int32_t* d_match12, const uint8_t* d_inlier, float th, int32_t* d_matches, int32_t* d_nfound,
+                                int32_t* d_match1, int32_t* d_match2, void* hip_stream);
 /* The first two lines of Tracking::Relocalization (ORB/src/Tracking.cc:2274-2285), on the device: with them the chain runs from a lost
  * frame's gather record to its restart pose without the host reading anything.
  *

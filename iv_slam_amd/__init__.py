@@ -10,4 +10,5 @@ from .frontend import StereoFrontend  # noqa: F401
 from .fcn import IntrospectionFCN  # noqa: F401
 from .rectify import initUndistortRectifyMap, Remap, Resize, resize_linear  # noqa: F401
 from .track import BatchTracker  # noqa: F401
+from .loop import LoopSearch  # noqa: F401
 from .camera import Camera  # noqa: F401

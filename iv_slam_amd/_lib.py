@@ -178,6 +178,8 @@ _SIGS = {
                                         vp, vp, vp, vp, vp, vp, vp]),
     "ivf_tracker_solve_sim3": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_int,
                                          vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ivf_tracker_search_by_bow_keyframes": (C.c_int, [vp, vp, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, C.c_float, C.c_int, vp, vp, vp]),
+    "ivf_tracker_search_by_sim3": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
     "ivf_tracker_bow_vectors": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
     "ivf_tracker_reloc_candidates": (C.c_int, [vp, vp] + [vp] * 7 + [C.c_int] + [vp] * 4 + [C.c_int, C.c_int] + [vp] * 6 + [vp]),
     "ivf_tracker_update_local_map": (C.c_int, [vp, C.POINTER(MapViewC), vp, C.c_int, C.c_int, C.c_int] + [vp] * 8 + [vp]),

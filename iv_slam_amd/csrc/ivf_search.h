@@ -1,6 +1,7 @@
 // ivf_search.h -- the device text the projection searches of the batched tracker share: ivf_track.hip (TrackWithMotionModel),
-// ivf_track_local.hip (SearchLocalPoints) and ivf_track_reloc.hip (Relocalization); ivf_track_bow.hip takes the liveness test.  Every
-// search is prepare -> window -> greedy walk; what makes them differ -- what a dead pair writes, the depth and viewing-angle tests, the
+// ivf_track_local.hip (SearchLocalPoints) and ivf_track_reloc.hip (Relocalization); ivf_track_bow.hip takes the liveness test,
+// ivf_track_sim3.hip (SearchBySim3, which is not greedy) the liveness test, the range-and-level gate and the first minimum of a window.  Every
+// other search is prepare -> window -> greedy walk; what makes them differ -- what a dead pair writes, the depth and viewing-angle tests, the
 // radius, the level range, best / second best, the admission against the live state -- stays with each kernel.
 #pragma once
 #include "ivf_tracker.h"
@@ -35,16 +36,22 @@ DEVINL bool ur_admits(float u2, float qur, float r) { return !(u2 > 0 && fabsf(q
 
 // ---- the gates of a projected map point (Frame::isInFrustum, Frame.cc:579-590; ORBmatcher.cc:1556-1572)
 DEVINL bool in_image(const TrackParams& P, float u, float v) { return !(u < P.minX || u > P.maxX) && !(v < P.minY || v > P.maxY); }
-// dist = cv::norm(P - Ow); false: outside [0.8 min_distance, 1.2 max_distance] (MapPoint.cc:378-388); else lv = MapPoint::PredictScale
+// false: dist outside [0.8 min_distance, 1.2 max_distance] (MapPoint.cc:378-388); else lv = MapPoint::PredictScale.  The one statement of
+// the range and the level, whatever distance a search measures: |P - Ow| below, the camera-frame norm in SearchBySim3 (ivf_track_sim3.hip)
+DEVINL bool range_level(const TrackParams& P, const ivf_local_point& mp, float dist, int& lv)
+{
+    const float minD = 0.8f * mp.min_distance, maxD = 1.2f * mp.max_distance;
+    if (dist < minD || dist > maxD) return false;
+    lv = predict_scale(P, mp.max_distance, dist);
+    return true;
+}
+// dist = cv::norm(P - Ow), then range_level
 DEVINL bool point_range_level(const TrackParams& P, const ivf_local_point& mp, const float* Ow, float& dist, int& lv)
 {
     const float PO[3] = {mp.pos[0] - Ow[0], mp.pos[1] - Ow[1], mp.pos[2] - Ow[2]};
     const double n2 = (double)PO[0] * (double)PO[0] + (double)PO[1] * (double)PO[1] + (double)PO[2] * (double)PO[2];
     dist = (float)sqrt(n2);
-    const float minD = 0.8f * mp.min_distance, maxD = 1.2f * mp.max_distance;
-    if (dist < minD || dist > maxD) return false;
-    lv = predict_scale(P, mp.max_distance, dist);
-    return true;
+    return range_level(P, mp, dist, lv);
 }
 
 // ---- the FIRST minimum of up to 64 candidates in list order, one per lane (live: the lane holds one; admits(idx): the search's own

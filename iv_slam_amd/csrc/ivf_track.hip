@@ -429,6 +429,23 @@ int tracker_grow_queries(ivf_tracker* t, int cap)
     t->queryCap = cap;
     return IVF_OK;
 }
+int tracker_grow_grids(ivf_tracker* t, int per_pair)
+{
+    if (per_pair <= t->gridCap) return IVF_OK;
+    // the larger buffers first: a failure leaves the handle with the grids it had, which run / search_local / search_reloc use unguarded
+    int* start = nullptr; unsigned short* idx = nullptr;
+    const size_t n = (size_t)t->cfg.max_pairs * (size_t)per_pair;
+    if (!t->alloc_all(start, n * (kGC * kGR + 1) * sizeof(int), idx, n * (size_t)t->cfg.nfeatures * sizeof(unsigned short)))
+        return fail(IVF_E_NO_DEVICE, "device allocation failed for %d pairs x %d grids", t->cfg.max_pairs, per_pair);
+    // the previous call (if any) must be done with the old buffers before they are freed; on a failure here the new ones are given back
+    if (t->ran && hipEventSynchronize(t->evDone) != hipSuccess) {
+        t->release(start); t->release(idx);
+        return fail(IVF_E_NO_DEVICE, "waiting for the previous call failed");
+    }
+    t->release(t->dStart); t->release(t->dIdx);
+    t->dStart = start; t->dIdx = idx; t->gridCap = per_pair;
+    return IVF_OK;
+}
 }  // namespace ivf
 
 extern "C" {
@@ -477,8 +494,7 @@ int ivf_tracker_create(const ivf_track_config* cfg, ivf_tracker** out)
     P.logScale = cfg->nlevels > 1 ? logf(cfg->scale_factors[1]) : 1.0f;             // mfLogScaleFactor = log(mfScaleFactor) (Frame.cc:106): logf
     const size_t np = (size_t)cfg->max_pairs, nf = (size_t)cfg->nfeatures;
     t->ldsBytes = nf * 20;
-    const bool ok = t->alloc(t->dStart, np * (kGC * kGR + 1) * sizeof(int)) && t->alloc(t->dIdx, np * nf * sizeof(unsigned short)) &&
-                    t->alloc(t->dRetry, np * sizeof(int)) &&
+    const bool ok = tracker_grow_grids(t, 1) == IVF_OK && t->alloc(t->dRetry, np * sizeof(int)) &&
                     t->alloc(t->bow.nodeKey, 2 * np * nf * sizeof(int)) && t->alloc(t->bow.fvNode, 2 * np * nf * sizeof(int)) &&
                     t->alloc(t->bow.fvStart, 2 * np * (nf + 1) * sizeof(int)) && t->alloc(t->bow.fvIdx, 2 * np * nf * sizeof(int)) &&
                     t->alloc(t->bow.fvN, 2 * np * sizeof(int)) && tracker_grow_queries(t, cfg->nfeatures) == IVF_OK;

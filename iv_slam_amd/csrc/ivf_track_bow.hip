@@ -5,6 +5,8 @@
 //     (FeatureVector.cpp:31-45); mBowVec is not computed;
 //   * ORBmatcher(nn_ratio, check_orientation).SearchByBoW(mpReferenceKF, mCurrentFrame, vpMapPointMatches) (ORB/src/ORBmatcher.cc:165-294);
 //   * ORBmatcher::UpdateQualityScores(mCurrentFrame) (Tracking.cc:1174-1176, ORBmatcher.cc:1108-1121) when the quality arrays are given.
+// and, on the same kernel body, loop closing's ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (ORB/src/ORBmatcher.cc:528-661, called at
+// LoopClosing.cc:270) for (current keyframe, candidate) pairs: ivf_tracker_search_by_bow_keyframes, whose d_match12 ivf_tracker_solve_sim3 reads.
 // Nothing crosses PCIe and nothing is replayed on the host.  The search parallelises exactly: a FeatureVector holds every feature in
 // exactly one node, and the loop's only serial dependence -- `if(vpMapPointMatches[realIdxF]) continue;` (:215) -- links keyframe
 // features of the SAME node only.  Nodes are independent (whichever wave takes whichever node, in whatever order, the result is the
@@ -18,6 +20,8 @@
 //   k_bow_search   one workgroup per pair: node merge (sorted_find of every keyframe node in the frame's list: only equal ids match,
 //                  the lower_bound walk of :186-270), the common nodes handed to the four waves one at a time, the greedy walk,
 //                  the rotation filter (rot_bin / rot_three_maxima, ivf_device.h), the quality epilogue (ivf_tracker.h)
+//                  k_bow_search_keyframes is the same body (bow_search_body) with the differences of the (KF, KF) overload: vbMatched2 links
+//                  KF2 features of one node only, so the argument above carries over unchanged
 // Which pairs take part (pair_live) is ivf_search.h's, the one test of it for every search of the handle.
 #include "ivf_search.h"
 
@@ -61,10 +65,15 @@ __global__ __launch_bounds__(256) void k_bow_featvec(BowParams P, const uint8_t*
     featvec_of_slot(B, s, P.nf, rec_count(rec, P.nf), s_key, part, tid);
 }
 
-__global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
-                                                   const int* __restrict__ select, const uint8_t* __restrict__ pointFlags, TrackerBowScratch B,
-                                                   float* __restrict__ pointQuality, float* __restrict__ keyQuality,
-                                                   int* __restrict__ assignOut, int* __restrict__ nmatchesOut)
+// The one body of both SearchByBoW overloads.  KF2KF = false: SearchByBoW(KeyFrame*, Frame&) (:165-294), side 2 is the current frame, the
+// result is indexed by ITS keypoint.  KF2KF = true: SearchByBoW(KeyFrame*, KeyFrame*) (:528-661): a KF2 candidate must itself hold a live
+// point (:580-586), the occupancy is vbMatched2 (by KF2 keypoint, the same s_assign), the acceptance is bestDist1 < TH_LOW strictly (:604),
+// the result is vpMatches12, indexed by KF1 keypoint, a dead pair writes nothing but its count, and there is no quality epilogue.
+template <bool KF2KF>
+DEVINL void bow_search_body(const BowParams& P, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
+                            const int* __restrict__ select, const uint8_t* __restrict__ pointFlags, const TrackerBowScratch& B,
+                            float* __restrict__ pointQuality, float* __restrict__ keyQuality,
+                            int* __restrict__ assignOut, int* __restrict__ nmatchesOut)
 {
     extern __shared__ int s_mem[];
     int* s_assign = s_mem;                                    // [nf] vpMapPointMatches as keyframe keypoint | bin << 16, or -1
@@ -75,7 +84,7 @@ __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* 
     int* out = assignOut + (size_t)p * P.nf;
     const int2 pr = pairs[p];
     if (!pair_live(P.nRecords, pr, select, p)) {
-        for (int i = tid; i < P.nf; i += 256) out[i] = -1;
+        if (!KF2KF) for (int i = tid; i < P.nf; i += 256) out[i] = -1;
         if (tid == 0) nmatchesOut[p] = (select && select[p] == 0) ? -2 : -1;
         return;
     }
@@ -104,6 +113,9 @@ __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* 
     const uint8_t* dF = rec_desc(recF, P.nf);
     const float* zK = rec_depth(recK, P.nf);
     const uint8_t* fl = pointFlags ? pointFlags + (size_t)pr.x * P.nf : nullptr;
+    const float* zF = rec_depth(recF, P.nf);                  // KF2KF: the candidate's own point, by the rule of side 1
+    const uint8_t* fl2 = pointFlags ? pointFlags + (size_t)pr.y * P.nf : nullptr;
+    auto holds2 = [&](int iF) { return fl2 ? (fl2[iF] & 1) != 0 : zF[iF] > 0; };
     int nmWave = 0;
     for (;;) {
         int c = 0;
@@ -118,6 +130,8 @@ __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* 
         const uint4* pf0 = (const uint4*)(dF + (size_t)iF0 * 32);
         const uint4 fa0 = pf0[0], fb0 = pf0[1];
         const float ang0 = kF[iF0].angle;
+        bool pt0 = true;
+        if (KF2KF) pt0 = holds2(iF0);
         for (int k0 = ks; k0 < ke; k0 += 64) {
             // 64 keyframe features at once: index, map point, descriptor and angle of feature k0 + lane, broadcast from its lane in turn
             const int i1L = idxK[min(k0 + lane, ke - 1)];
@@ -135,13 +149,14 @@ __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* 
                 // per lane over its strides: the smallest (distance, list position) and the smallest distance among its others
                 unsigned bestKey = 0xffffffffu; int second = 256, bestI = 0; float bestAng = 0.0f;
                 for (int q = 0; q < nFn; q += 64) {
-                    int iF = iF0; uint4 fa = fa0, fb = fb0; float ang = ang0;
+                    int iF = iF0; uint4 fa = fa0, fb = fb0; float ang = ang0; bool pt = pt0;
                     if (q) {
                         iF = idxF[fs + min(q + lane, nFn - 1)];
                         const uint4* pf = (const uint4*)(dF + (size_t)iF * 32);
                         fa = pf[0]; fb = pf[1]; ang = kF[iF].angle;
+                        if (KF2KF) pt = holds2(iF);
                     }
-                    const bool free_ = q + lane < nFn && s_assign[iF] < 0;                         // :215
+                    const bool free_ = q + lane < nFn && s_assign[iF] < 0 && pt;                   // :215; :580-586
                     const unsigned d = (unsigned)hamming256(qa, qb, fa, fb);
                     const unsigned key = free_ ? (d << 12) | (unsigned)(q + lane) : 0xffffffffu;
                     if (key < bestKey) { second = min(second, (int)min(bestKey >> 12, 256u)); bestKey = key; bestI = iF; bestAng = ang; }
@@ -153,7 +168,7 @@ __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* 
                 const int who = __ffsll((long long)__ballot(bestKey == best)) - 1;
                 const int bestDist1 = (int)(best >> 12);
                 const int bestDist2 = (int)wave_min_u32(lane == who ? (unsigned)second : min(bestKey >> 12, 256u));
-                if (bestDist1 <= 50 && (float)bestDist1 < P.nnRatio * (float)bestDist2) {           // TH_LOW, mfNNratio (:234-236)
+                if ((KF2KF ? bestDist1 < 50 : bestDist1 <= 50) && (float)bestDist1 < P.nnRatio * (float)bestDist2) {   // TH_LOW, mfNNratio (:234-236; :604-606)
                     const int bestIdxF = __builtin_amdgcn_readlane(bestI, who);
                     int bin = 0;
                     if (P.checkOri) bin = rot_bin(angK - readlane_f32(bestAng, who));
@@ -179,20 +194,47 @@ __global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* 
         if (removed) atomicSub(&s_nm, removed);
         __syncthreads();
     }
+    if (KF2KF) {
+        // vpMatches12 by KF1 keypoint: a KF1 feature is walked once, so it names at most one KF2 keypoint; the node list is done with
+        int* s_m12 = s_common;
+        for (int i = tid; i < P.nf; i += 256) s_m12[i] = -1;
+        __syncthreads();
+        for (int i = tid; i < nF; i += 256) { const int a = s_assign[i]; if (a >= 0) s_m12[a & 0xffff] = i; }
+        __syncthreads();
+        for (int i = tid; i < P.nf; i += 256) out[i] = s_m12[i];
+        if (tid == 0) nmatchesOut[p] = s_nm;
+        return;
+    }
     for (int i = tid; i < P.nf; i += 256) { const int a = i < nF ? s_assign[i] : -1; out[i] = a < 0 ? -1 : (a & 0xffff); }
     // UpdateQualityScores(mCurrentFrame) (Tracking.cc:1174-1176)
     if (pointQuality && keyQuality) update_quality_scores(s_assign, nF, 0xffff, tid, 256, pointQuality + (size_t)p * P.nf, keyQuality + (size_t)p * P.nf);
     if (tid == 0) nmatchesOut[p] = s_nm;
 }
 
+__global__ __launch_bounds__(256) void k_bow_search(BowParams P, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
+                                                   const int* __restrict__ select, const uint8_t* __restrict__ pointFlags, TrackerBowScratch B,
+                                                   float* __restrict__ pointQuality, float* __restrict__ keyQuality,
+                                                   int* __restrict__ assignOut, int* __restrict__ nmatchesOut)
+{
+    bow_search_body<false>(P, records, pairs, select, pointFlags, B, pointQuality, keyQuality, assignOut, nmatchesOut);
+}
+
+__global__ __launch_bounds__(256) void k_bow_search_keyframes(BowParams P, const uint8_t* __restrict__ records, const int2* __restrict__ pairs,
+                                                             const int* __restrict__ select, const uint8_t* __restrict__ pointFlags,
+                                                             TrackerBowScratch B, int* __restrict__ match12, int* __restrict__ nmatchesOut)
+{
+    bow_search_body<true>(P, records, pairs, select, pointFlags, B, nullptr, nullptr, match12, nmatchesOut);
+}
+
 }  // namespace
 
 extern "C" {
 
-int ivf_tracker_search_by_bow(ivf_tracker* t, const ivf_vocabulary* voc, int levelsup, const uint8_t* d_records, size_t record_bytes, int n_records,
-                              const int32_t* d_pairs, int n_pairs, const int32_t* d_select, const uint8_t* d_point_flags, float nn_ratio,
-                              int check_orientation, float* d_point_quality, float* d_key_quality, int32_t* d_assign, int32_t* d_nmatches,
-                              void* hip_stream)
+// both entry points: the checks, the feature vectors of both records of every pair, the search of one of the two overloads
+static int search_by_bow(bool kf2kf, ivf_tracker* t, const ivf_vocabulary* voc, int levelsup, const uint8_t* d_records, size_t record_bytes, int n_records,
+                         const int32_t* d_pairs, int n_pairs, const int32_t* d_select, const uint8_t* d_point_flags, float nn_ratio,
+                         int check_orientation, float* d_point_quality, float* d_key_quality, int32_t* d_assign, int32_t* d_nmatches,
+                         void* hip_stream)
 {
     if (!t || !voc || !d_records || !d_pairs || !d_assign || !d_nmatches) return fail(IVF_E_INVALID, "null argument");
     if (((size_t)d_records & 15) != 0) return fail(IVF_E_INVALID, "the record block must be 16-byte aligned");
@@ -214,9 +256,30 @@ int ivf_tracker_search_by_bow(ivf_tracker* t, const ivf_vocabulary* voc, int lev
     key_sort_pad(nf, &keyBytes);
     hipLaunchKernelGGL(k_bow_nodes, dim3((nf + 15) / 16, 2 * n_pairs), dim3(256), 0, st, P, V, d_records, pairs, d_select, B.nodeKey);
     hipLaunchKernelGGL(k_bow_featvec, dim3(2 * n_pairs), dim3(256), keyBytes, st, P, d_records, pairs, d_select, B);
-    hipLaunchKernelGGL(k_bow_search, dim3(n_pairs), dim3(256), (size_t)nf * 2 * sizeof(int), st, P, d_records, pairs, d_select, d_point_flags, B,
-                       d_point_quality, d_key_quality, d_assign, d_nmatches);
+    if (kf2kf)
+        hipLaunchKernelGGL(k_bow_search_keyframes, dim3(n_pairs), dim3(256), (size_t)nf * 2 * sizeof(int), st, P, d_records, pairs, d_select,
+                           d_point_flags, B, d_assign, d_nmatches);
+    else
+        hipLaunchKernelGGL(k_bow_search, dim3(n_pairs), dim3(256), (size_t)nf * 2 * sizeof(int), st, P, d_records, pairs, d_select, d_point_flags, B,
+                           d_point_quality, d_key_quality, d_assign, d_nmatches);
     return tracker_end(t, st);
+}
+
+int ivf_tracker_search_by_bow(ivf_tracker* t, const ivf_vocabulary* voc, int levelsup, const uint8_t* d_records, size_t record_bytes, int n_records,
+                              const int32_t* d_pairs, int n_pairs, const int32_t* d_select, const uint8_t* d_point_flags, float nn_ratio,
+                              int check_orientation, float* d_point_quality, float* d_key_quality, int32_t* d_assign, int32_t* d_nmatches,
+                              void* hip_stream)
+{
+    return search_by_bow(false, t, voc, levelsup, d_records, record_bytes, n_records, d_pairs, n_pairs, d_select, d_point_flags, nn_ratio,
+                         check_orientation, d_point_quality, d_key_quality, d_assign, d_nmatches, hip_stream);
+}
+
+int ivf_tracker_search_by_bow_keyframes(ivf_tracker* t, const ivf_vocabulary* voc, int levelsup, const uint8_t* d_records, size_t record_bytes,
+                                        int n_records, const int32_t* d_pairs, int n_pairs, const int32_t* d_select, const uint8_t* d_point_flags,
+                                        float nn_ratio, int check_orientation, int32_t* d_match12, int32_t* d_nmatches, void* hip_stream)
+{
+    return search_by_bow(true, t, voc, levelsup, d_records, record_bytes, n_records, d_pairs, n_pairs, d_select, d_point_flags, nn_ratio,
+                         check_orientation, nullptr, nullptr, d_match12, d_nmatches, hip_stream);
 }
 
 }  // extern "C"

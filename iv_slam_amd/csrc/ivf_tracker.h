@@ -1,6 +1,7 @@
-// ivf_tracker.h -- the batched tracker handle and what its eleven translation units share (not part of the public C-ABI):
+// ivf_tracker.h -- the batched tracker handle and what its twelve translation units share (not part of the public C-ABI):
 // ivf_track.hip (the handle's life cycle and the TrackWithMotionModel search), ivf_track_local.hip (SearchLocalPoints),
-// ivf_track_bow.hip (TrackReferenceKeyFrame), ivf_track_reloc.hip (Relocalization's SearchByProjection and the set bookkeeping around
+// ivf_track_bow.hip (TrackReferenceKeyFrame and loop closing's SearchByBoW(KF, KF)), ivf_track_sim3.hip (loop closing's SearchBySim3),
+// ivf_track_reloc.hip (Relocalization's SearchByProjection and the set bookkeeping around
 // it), ivf_track_db.hip (Relocalization's first two lines: mBowVec and KeyFrameDatabase::DetectRelocalizationCandidates),
 // ivf_track_map.hip (UpdateLocalMap: the local keyframes and points of a frame from a device-resident map),
 // ivf_track_points.hip (the points a search hands to a solver and the tail of TrackLocalMap), ivf_track_create.hip
@@ -102,6 +103,10 @@ __device__ __forceinline__ int predict_scale(const TrackParams& P, float maxDist
 // per-query record written by k_track_prepare / k_local_prepare / k_reloc_prepare: projection (u, v), ur = u - bf * invzc, and the packed
 // {octave, minLevel + 1, maxLevel + 1, flags: bit 0 valid, bit 1 blocks}
 struct __attribute__((aligned(16))) Query { float u, v, ur; unsigned bits; };
+// The handle's scratch of ivf_tracker_search_by_sim3 (ivf_track_sim3.hip), allocated at its first call for max_pairs pairs, two slots
+// (direction 1 -> 2, 2 -> 1) per pair: the queries and radii [2 * max_pairs][nfeatures] and vnMatch1 / vnMatch2.  Its own, not the
+// candidate scratch of the projection searches: that one carries kListCap list entries per query, which this search never writes.
+struct Sim3SearchScratch { Query* q; float* rad; int* vn; };
 __device__ __forceinline__ unsigned pack_bits(int oct, int lo, int hi, int valid, int blocks)
 { return (unsigned)oct | ((unsigned)(lo + 1) << 8) | ((unsigned)(hi + 1) << 16) | ((unsigned)valid << 24) | ((unsigned)blocks << 25); }
 
@@ -152,8 +157,13 @@ __device__ __forceinline__ void update_quality_scores(const int* assign, int n, 
 struct ivf_tracker {
     ivf_track_config cfg;
     ivf::TrackParams P;                   // nRecords is the one per-call field: every entry point sets it in its own copy
+    // the device grids (ivf_grid.h), [max_pairs * gridCap] of them: gridCap is 1 (one grid per pair: the record every projection search
+    // looks into) until ivf_tracker_search_by_sim3, which searches both records of a pair, grows it to 2 (tracker_grow_grids: the new
+    // buffers are allocated before the old ones are freed, so a failed growth leaves the handle as it was; that first call waits on the
+    // host for the handle's previous call)
     int *dStart = nullptr, *dRetry = nullptr;
     unsigned short* dIdx = nullptr;
+    int gridCap = 0;
     // the candidate scratch of the three projection searches, [max_pairs][queryCap] queries, radii (search_local, search_reloc),
     // counts, lists: queryCap starts at nfeatures (run and search_reloc index it with that stride) and grows on demand
     // (tracker_grow_queries) to search_local's max_points_per_frame, its stride
@@ -161,6 +171,7 @@ struct ivf_tracker {
     ivf::TrackerBowScratch bow{nullptr, nullptr, nullptr, nullptr, nullptr};   // ivf_tracker_search_by_bow: [2 * max_pairs] slots
     ivf::PnpScratch pnp{nullptr, nullptr, nullptr, nullptr};
     ivf::Sim3Scratch sim3{nullptr, nullptr, nullptr, nullptr, nullptr};
+    ivf::Sim3SearchScratch sim3s{nullptr, nullptr, nullptr};
     ivf::DbScratch db{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
     ivf::MapScratch map{nullptr, nullptr, 0, 0};
     size_t ldsBytes = 0;
@@ -198,7 +209,8 @@ namespace ivf {
 // search_args_ok: what the three projection searches check alike -- the pointers (points: the array of search_local / search_reloc),
 // the 16-byte alignment of what the kernels read as uint4 and, in a call of n_items != 0, that the quality arrays come together;
 // ransac_args_ok: what ivf_pnp.hip and ivf_sim3.hip check alike -- the record block's alignment, max_iterations, probability, min_inliers;
-// tracker_grow_queries: the candidate scratch (dQ, dLRad, dCount, dLists) for at least `cap` queries per frame / pair
+// tracker_grow_queries: the candidate scratch (dQ, dLRad, dCount, dLists) for at least `cap` queries per frame / pair;
+// tracker_grow_grids: the grid scratch (dStart, dIdx) for at least `per_pair` grids per pair
 int tracker_begin(ivf_tracker* t, bool reads_records, size_t record_bytes, int n_records, int n_items, hipStream_t st);
 int tracker_begin_with_vocabulary(ivf_tracker* t, const ivf_vocabulary* voc, VocabularyView* V, bool reads_records, size_t record_bytes, int n_records,
                                   int n_items, hipStream_t st);
@@ -207,4 +219,5 @@ int search_args_ok(const ivf_tracker* t, const void* records, const void* items,
                    const void* nmatches, int n_items, const float* point_quality, const float* key_quality);
 int ransac_args_ok(const void* records, int max_iterations, double probability, int min_inliers);
 int tracker_grow_queries(ivf_tracker* t, int cap);
+int tracker_grow_grids(ivf_tracker* t, int per_pair);
 }  // namespace ivf

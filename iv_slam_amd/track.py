@@ -403,7 +403,8 @@ class BatchTracker:
         (9), t12 (3), s12, 3 zeros, written only on success; inlier: torch.uint8 [n_pairs, nfeatures] by i1 (vbInliers); ninliers:
         torch.int32 [n_pairs] (0: no transform, -1: bad record index, -2: not selected); iterations: torch.int32 [n_pairs] or None
         (mnIterations on return); hyp_sim3: torch.float32 [n_pairs, max_iterations, 16] and hyp_ninliers: torch.int32
-        [n_pairs, max_iterations] or None: every hypothesis from the state's iteration to mRansacMaxIts.  (s12 R12, t12) is what ivf_search_by_sim3 takes next.
+        [n_pairs, max_iterations] or None: every hypothesis from the state's iteration to mRansacMaxIts.  match12 is what LoopSearch.search_by_bow_keyframes
+        writes; sim3, inlier and (ninliers > 0) are what LoopSearch.search_by_sim3 takes next (iv_slam_amd/loop.py).
         Asynchronous on the given stream."""
         p, nf, mi = partial(_ptr, self.device), self.nfeatures, int(max_iterations)
         (records_p, n_rec), (pairs_p, n_pairs) = self._records(records), self._pairs(pairs)
