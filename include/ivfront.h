@@ -413,7 +413,8 @@ typedef struct ivf_local_point {
  * through the same update when they got it, and a second pass over them changes nothing (min(q_mp, q_kp) == q_kp by then).
  * Outputs: d_assign [n_frames][nfeatures] = index (within the frame's point range) of the map point each keypoint received in
  * THIS call or -1; d_nmatches [n_frames] = the return value (assignments made, replaced ones included).  n_frames <= max_pairs.
- * Asynchronous on hip_stream; shares the handle's scratch (and its one-call-at-a-time rule) with ivf_tracker_run. */
+ * Asynchronous on hip_stream; shares the handle's scratch (and its one-call-at-a-time rule) with ivf_tracker_run.  A max_points_per_frame
+ * beyond nfeatures enlarges that scratch; when the device refuses (IVF_E_NO_DEVICE) the handle stays usable with the scratch it had. */
 int  ivf_tracker_search_local(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_frames,
                               int n_frames, const float* d_poses, const ivf_local_point* d_points, const int32_t* d_point_offsets,
                               int max_points_per_frame, const uint8_t* d_occupied, float th, float nn_ratio, float cos_limit,
@@ -852,7 +853,8 @@ int  ivf_tracker_bow_vectors(ivf_tracker* t, const ivf_vocabulary* voc, const ui
  * 10; garbage input (unsorted words, a count above nfeatures, a neighbour outside the database) may give a meaningless answer but no
  * read outside the arrays.  Two runs are bit-identical.  Asynchronous on hip_stream, no host synchronisation; the scratch
  * (40 bytes per frame and keyframe) sits on the handle, grows on demand (the one place where the call waits, for the handle's previous
- * call, before it frees the smaller buffers) and obeys the one-call-at-a-time rule. */
+ * call, before it frees the smaller buffers; a refused growth, IVF_E_NO_DEVICE, leaves the handle usable with the scratch it had) and
+ * obeys the one-call-at-a-time rule. */
 int  ivf_tracker_reloc_candidates(ivf_tracker* t, const ivf_vocabulary* voc, const int32_t* d_kf_bow_word, const double* d_kf_bow_value,
                                   const int32_t* d_kf_bow_n, const uint8_t* d_kf_live, const int32_t* d_kf_neigh,
                                   const float* d_kf_reloc_score, const int32_t* d_kf_record, int n_keyframes, const int32_t* d_bow_word,

@@ -620,8 +620,8 @@ int ivf_tracker_solve_pnp(ivf_tracker* t, const uint8_t* d_records, size_t recor
     if (rc != IVF_OK) return rc;
     if (!t->pnp.corr) {                                                // first use: the scratch of ONE call, sized by max_pairs
         const size_t np = (size_t)t->cfg.max_pairs, nf = (size_t)t->P.nf;
-        if (!t->alloc_all(t->pnp.corr, np * nf * sizeof(Corr), t->pnp.head, np * sizeof(int4), t->pnp.hypPose,
-                          np * kRansacMaxIterations * 12 * sizeof(double), t->pnp.hypN, np * kRansacMaxIterations * sizeof(int)))
+        if (!t->replace({{t->pnp.corr, np * nf * sizeof(Corr)}, {t->pnp.head, np * sizeof(int4)},
+                         {t->pnp.hypPose, np * kRansacMaxIterations * 12 * sizeof(double)}, {t->pnp.hypN, np * kRansacMaxIterations * sizeof(int)}}))
             return fail(IVF_E_NO_DEVICE, "device allocation failed for the PnP scratch of %d frames x %d features", t->cfg.max_pairs, t->P.nf);
     }
     PnpParams P;

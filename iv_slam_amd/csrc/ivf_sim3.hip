@@ -384,8 +384,8 @@ int ivf_tracker_solve_sim3(ivf_tracker* t, const uint8_t* d_records, size_t reco
     if (rc != IVF_OK) return rc;
     if (!t->sim3.corr) {                                               // first use: the scratch of ONE call, sized by max_pairs
         const size_t np = (size_t)t->cfg.max_pairs, nf = (size_t)t->P.nf;
-        if (!t->alloc_all(t->sim3.corr, np * nf * sizeof(Corr3), t->sim3.idx, np * nf * sizeof(unsigned short), t->sim3.head, np * sizeof(int4),
-                          t->sim3.hyp, np * kRansacMaxIterations * 16 * sizeof(float), t->sim3.hypN, np * kRansacMaxIterations * sizeof(int)))
+        if (!t->replace({{t->sim3.corr, np * nf * sizeof(Corr3)}, {t->sim3.idx, np * nf * sizeof(unsigned short)}, {t->sim3.head, np * sizeof(int4)},
+                         {t->sim3.hyp, np * kRansacMaxIterations * 16 * sizeof(float)}, {t->sim3.hypN, np * kRansacMaxIterations * sizeof(int)}}))
             return fail(IVF_E_NO_DEVICE, "device allocation failed for the Sim3 scratch of %d pairs x %d features", t->cfg.max_pairs, t->P.nf);
     }
     Sim3Params P;

@@ -416,34 +416,19 @@ int ransac_args_ok(const void* records, int max_iterations, double probability, 
 int tracker_grow_queries(ivf_tracker* t, int cap)
 {
     if (cap <= t->queryCap) return IVF_OK;
-    // grow the scratch: the previous call (if any) must be done with the old buffers before they are freed
-    if (t->ran) HIPCHK(hipEventSynchronize(t->evDone));
-    auto drop = [&] { t->release(t->dQ); t->release(t->dLRad); t->release(t->dCount); t->release(t->dLists); t->queryCap = 0; };
-    drop();
     const size_t n = (size_t)t->cfg.max_pairs * (size_t)cap;
-    if (!(t->alloc(t->dQ, n * sizeof(Query)) && t->alloc(t->dLRad, n * sizeof(float)) && t->alloc(t->dCount, n * sizeof(int)) &&
-          t->alloc(t->dLists, n * kListCap * sizeof(unsigned)))) {
-        drop();
+    if (!t->replace({{t->dQ, n * sizeof(Query)}, {t->dLRad, n * sizeof(float)}, {t->dCount, n * sizeof(int)}, {t->dLists, n * kListCap * sizeof(unsigned)}}))
         return fail(IVF_E_NO_DEVICE, "device allocation failed for %d frames x %d queries", t->cfg.max_pairs, cap);
-    }
     t->queryCap = cap;
     return IVF_OK;
 }
 int tracker_grow_grids(ivf_tracker* t, int per_pair)
 {
     if (per_pair <= t->gridCap) return IVF_OK;
-    // the larger buffers first: a failure leaves the handle with the grids it had, which run / search_local / search_reloc use unguarded
-    int* start = nullptr; unsigned short* idx = nullptr;
     const size_t n = (size_t)t->cfg.max_pairs * (size_t)per_pair;
-    if (!t->alloc_all(start, n * (kGC * kGR + 1) * sizeof(int), idx, n * (size_t)t->cfg.nfeatures * sizeof(unsigned short)))
+    if (!t->replace({{t->dStart, n * (kGC * kGR + 1) * sizeof(int)}, {t->dIdx, n * (size_t)t->cfg.nfeatures * sizeof(unsigned short)}}))
         return fail(IVF_E_NO_DEVICE, "device allocation failed for %d pairs x %d grids", t->cfg.max_pairs, per_pair);
-    // the previous call (if any) must be done with the old buffers before they are freed; on a failure here the new ones are given back
-    if (t->ran && hipEventSynchronize(t->evDone) != hipSuccess) {
-        t->release(start); t->release(idx);
-        return fail(IVF_E_NO_DEVICE, "waiting for the previous call failed");
-    }
-    t->release(t->dStart); t->release(t->dIdx);
-    t->dStart = start; t->dIdx = idx; t->gridCap = per_pair;
+    t->gridCap = per_pair;
     return IVF_OK;
 }
 }  // namespace ivf
@@ -459,7 +444,7 @@ void ivf_tracker_destroy(ivf_tracker* t)
 {
     if (!t) return;
     (void)hipSetDevice(t->cfg.device_id);
-    for (void* q : t->owned) (void)hipFree(q);
+    scratch_free_all(ivf_tracker::Device{t}, t->owned);
     if (t->evDone) (void)hipEventDestroy(t->evDone);
     delete t;
 }
@@ -494,11 +479,9 @@ int ivf_tracker_create(const ivf_track_config* cfg, ivf_tracker** out)
     P.logScale = cfg->nlevels > 1 ? logf(cfg->scale_factors[1]) : 1.0f;             // mfLogScaleFactor = log(mfScaleFactor) (Frame.cc:106): logf
     const size_t np = (size_t)cfg->max_pairs, nf = (size_t)cfg->nfeatures;
     t->ldsBytes = nf * 20;
-    const bool ok = tracker_grow_grids(t, 1) == IVF_OK && t->alloc(t->dRetry, np * sizeof(int)) &&
-                    t->alloc(t->bow.nodeKey, 2 * np * nf * sizeof(int)) && t->alloc(t->bow.fvNode, 2 * np * nf * sizeof(int)) &&
-                    t->alloc(t->bow.fvStart, 2 * np * (nf + 1) * sizeof(int)) && t->alloc(t->bow.fvIdx, 2 * np * nf * sizeof(int)) &&
-                    t->alloc(t->bow.fvN, 2 * np * sizeof(int)) && tracker_grow_queries(t, cfg->nfeatures) == IVF_OK;
-    if (!ok) {
+    if (tracker_grow_grids(t, 1) != IVF_OK || tracker_grow_queries(t, cfg->nfeatures) != IVF_OK ||
+        !t->replace({{t->dRetry, np * sizeof(int)}, {t->bow.nodeKey, 2 * np * nf * sizeof(int)}, {t->bow.fvNode, 2 * np * nf * sizeof(int)},
+                     {t->bow.fvStart, 2 * np * (nf + 1) * sizeof(int)}, {t->bow.fvIdx, 2 * np * nf * sizeof(int)}, {t->bow.fvN, 2 * np * sizeof(int)}})) {
         ivf_tracker_destroy(t);
         return fail(IVF_E_NO_DEVICE, "device allocation failed for a tracker of %d pairs x %d features", cfg->max_pairs, cfg->nfeatures);
     }
@@ -526,8 +509,6 @@ int ivf_tracker_run(ivf_tracker* t, const uint8_t* d_records, size_t record_byte
     // previous one queues behind it (use one tracker per stream to let runs overlap)
     const int rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st);
     if (rc != IVF_OK) return rc;
-    const int rg = tracker_grow_queries(t, t->P.nf);                                   // a no-op unless a larger request failed
-    if (rg != IVF_OK) return rg;
     TrackParams P = t->P;
     P.nRecords = n_records;
     const int2* pairs = (const int2*)d_pairs;

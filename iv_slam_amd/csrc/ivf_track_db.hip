@@ -284,29 +284,21 @@ __global__ __launch_bounds__(256) void k_db_select(DbParams P, DbIn I, DbScratch
     if (tid == 0) ncand[f] = C;
 }
 
-// the scratch of ivf_tracker_reloc_candidates for `cells` (frame, keyframe) cells and `frames` frames
-int db_grow(ivf_tracker* t, size_t cells, int frames)
+// the scratch of ivf_tracker_reloc_candidates for n (frame, keyframe) cells and `frames` frames: two sets, each with its cap
+int db_grow(ivf_tracker* t, size_t n, int frames)
 {
     DbScratch& S = t->db;
-    if (cells <= S.cap && frames <= S.frameCap) return IVF_OK;
-    // the previous call (if any) must be done with the old buffers before they are freed
-    if (t->ran) HIPCHK(hipEventSynchronize(t->evDone));
-    const size_t n = cells > S.cap ? (cells > 0 ? cells : 1) : S.cap;
-    const int nFrames = frames > S.frameCap ? frames : S.frameCap;
-    auto drop = [&] {
-        t->release(S.common); t->release(S.minWord); t->release(S.score); t->release(S.acc); t->release(S.best); t->release(S.place);
-        t->release(S.list); t->release(S.listKey); t->release(S.maxCommon);
-        S.cap = 0; S.frameCap = 0;
-    };
-    drop();
-    if (!(t->alloc(S.common, n * sizeof(int)) && t->alloc(S.minWord, n * sizeof(int)) && t->alloc(S.score, n * sizeof(float)) &&
-          t->alloc(S.acc, n * sizeof(float)) && t->alloc(S.best, n * sizeof(int)) && t->alloc(S.place, n * sizeof(unsigned long long)) &&
-          t->alloc(S.list, n * sizeof(int)) && t->alloc(S.listKey, n * sizeof(unsigned long long)) &&
-          t->alloc(S.maxCommon, (size_t)nFrames * sizeof(int)))) {
-        drop();
-        return fail(IVF_E_NO_DEVICE, "device allocation failed for %zu frame x keyframe cells", n);
+    if (n > S.cap) {                                                   // the eight cell arrays
+        if (!t->replace({{S.common, n * sizeof(int)}, {S.minWord, n * sizeof(int)}, {S.score, n * sizeof(float)}, {S.acc, n * sizeof(float)},
+                         {S.best, n * sizeof(int)}, {S.place, n * sizeof(unsigned long long)}, {S.list, n * sizeof(int)},
+                         {S.listKey, n * sizeof(unsigned long long)}}))
+            return fail(IVF_E_NO_DEVICE, "device allocation failed for %zu frame x keyframe cells", n);
+        S.cap = n;
     }
-    S.cap = n; S.frameCap = nFrames;
+    if (frames > S.frameCap) {                                         // maxCommon, per frame
+        if (!t->replace({{S.maxCommon, (size_t)frames * sizeof(int)}})) return fail(IVF_E_NO_DEVICE, "device allocation failed for %zu frame x keyframe cells", n);
+        S.frameCap = frames;
+    }
     return IVF_OK;
 }
 

@@ -254,17 +254,12 @@ int ceil_log2(size_t n) { int l = 0; while (((size_t)1 << l) < n) l++; return l;
 int map_grow(ivf_tracker* t, size_t voteInts, size_t hashWords)
 {
     MapScratch& S = t->map;
-    if (voteInts <= S.voteCap && hashWords <= S.hashCap) return IVF_OK;
-    // the previous call (if any) must be done with the old buffers before they are freed
-    if (t->ran) HIPCHK(hipEventSynchronize(t->evDone));
     if (voteInts > S.voteCap) {
-        t->release(S.vote); S.voteCap = 0;
-        if (!t->alloc(S.vote, voteInts * sizeof(int))) return fail(IVF_E_NO_DEVICE, "device allocation failed for %zu vote cells", voteInts);
+        if (!t->replace({{S.vote, voteInts * sizeof(int)}})) return fail(IVF_E_NO_DEVICE, "device allocation failed for %zu vote cells", voteInts);
         S.voteCap = voteInts;
     }
     if (hashWords > S.hashCap) {
-        t->release(S.hash); S.hashCap = 0;
-        if (!t->alloc(S.hash, hashWords * sizeof(unsigned))) return fail(IVF_E_NO_DEVICE, "device allocation failed for %zu hash words", hashWords);
+        if (!t->replace({{S.hash, hashWords * sizeof(unsigned)}})) return fail(IVF_E_NO_DEVICE, "device allocation failed for %zu hash words", hashWords);
         S.hashCap = hashWords;
     }
     return IVF_OK;

@@ -227,8 +227,6 @@ int ivf_tracker_search_reloc(ivf_tracker* t, const uint8_t* d_records, size_t re
     const int rc = tracker_begin(t, true, record_bytes, n_records, n_pairs, st);
     if (rc != IVF_OK) return rc;
     if (n_pairs == 0) return IVF_OK;
-    const int rg = tracker_grow_queries(t, t->P.nf);
-    if (rg != IVF_OK) return rg;
     TrackParams P = t->P;
     P.nRecords = n_records;
     const int2* pairs = (const int2*)d_pairs;

@@ -203,7 +203,7 @@ int ivf_tracker_search_by_sim3(ivf_tracker* t, const uint8_t* d_records, size_t 
     if (rg != IVF_OK) return rg;
     Sim3SearchScratch& W = t->sim3s;
     const size_t nq = 2 * (size_t)t->cfg.max_pairs * (size_t)t->P.nf;
-    if (!W.q && !t->alloc_all(W.q, nq * sizeof(Query), W.rad, nq * sizeof(float), W.vn, nq * sizeof(int)))
+    if (!W.q && !t->replace({{W.q, nq * sizeof(Query)}, {W.rad, nq * sizeof(float)}, {W.vn, nq * sizeof(int)}}))
         return fail(IVF_E_NO_DEVICE, "device allocation failed for the queries of %d pairs", t->cfg.max_pairs);
     TrackParams P = t->P;
     P.nRecords = n_records;

@@ -10,10 +10,11 @@
 // camera and record constants (TrackParams), and the device pieces searches and solvers both read (the query record, the pose algebra,
 // PredictScale, UpdateQualityScores); what only the projection searches repeat is ivf_search.h's, what only the solvers repeat
 // ivf_solve.h's, what the BoW units (ivf_track_bow.hip, ivf_track_db.hip and the per-call transform) repeat ivf_bow.h's.  Of the two
-// RANSAC solvers: the cap kRansacMaxIterations, the checks ransac_args_ok, the scratch allocation alloc_all; the rest is ivf_solve.h's.
+// RANSAC solvers: the cap kRansacMaxIterations, the checks ransac_args_ok; the rest is ivf_solve.h's.  How the handle's scratch is
+// allocated, grown and kept through a failed growth is stated once, in ivf_scratch.h (host-only): every unit goes through ivf_tracker::replace.
 #pragma once
 #include "ivf_bow.h"
-#include <vector>
+#include "ivf_scratch.h"
 
 namespace ivf {
 
@@ -158,9 +159,7 @@ struct ivf_tracker {
     ivf_track_config cfg;
     ivf::TrackParams P;                   // nRecords is the one per-call field: every entry point sets it in its own copy
     // the device grids (ivf_grid.h), [max_pairs * gridCap] of them: gridCap is 1 (one grid per pair: the record every projection search
-    // looks into) until ivf_tracker_search_by_sim3, which searches both records of a pair, grows it to 2 (tracker_grow_grids: the new
-    // buffers are allocated before the old ones are freed, so a failed growth leaves the handle as it was; that first call waits on the
-    // host for the handle's previous call)
+    // looks into) until ivf_tracker_search_by_sim3, which searches both records of a pair, grows it to 2 (tracker_grow_grids)
     int *dStart = nullptr, *dRetry = nullptr;
     unsigned short* dIdx = nullptr;
     int gridCap = 0;
@@ -177,28 +176,17 @@ struct ivf_tracker {
     size_t ldsBytes = 0;
     hipEvent_t evDone = nullptr;          // end of the previous call: the scratch above belongs to ONE call at a time
     bool ran = false;
-    std::vector<void*> owned;             // every device allocation of the handle (alloc): ivf_tracker_destroy frees these
-
-    // one hipMalloc the handle owns from here on
-    template <class T> bool alloc(T*& p, size_t bytes)
-    {
-        if (hipMalloc(&p, bytes) != hipSuccess) { p = nullptr; return false; }
-        owned.push_back(p);
-        return true;
-    }
-    // gives one of them back early (null: nothing to do)
-    template <class T> void release(T*& p)
-    {
-        for (size_t i = 0; i < owned.size(); i++)
-            if (p && owned[i] == p) { (void)hipFree(p); owned.erase(owned.begin() + i); break; }
-        p = nullptr;
-    }
-    // several buffers at once, as (pointer, bytes) pairs, all null on entry: every one is allocated and owned, or none is and all stay null
-    bool alloc_all() { return true; }
-    template <class T, class... Rest> bool alloc_all(T*& p, size_t bytes, Rest&&... rest)
-    {
-        return (alloc(p, bytes) && alloc_all(rest...)) || (release(p), false);
-    }
+    std::vector<void*> owned;             // the members above that hold a device buffer (ivf_scratch.h): ivf_tracker_destroy frees these
+    // ivf_scratch.h's device: a refused allocation also consumes the runtime's last-error word, so that the failure is reported once, by
+    // the call that caused it, and not again by the next call's tracker_end.  Every scratch set of the handle is allocated and grown
+    // through replace(), as {member, bytes} entries: all of them are replaced, or (false) none
+    struct Device {
+        ivf_tracker* t;
+        void* alloc(size_t bytes) { void* p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : ((void)hipGetLastError(), nullptr); }
+        void free(void* p) { (void)hipFree(p); }
+        bool wait() { return !t->ran || hipEventSynchronize(t->evDone) == hipSuccess; }
+    };
+    bool replace(std::initializer_list<ivf::ScratchSlot> set) { return ivf::scratch_replace(Device{this}, owned, set); }
 };
 
 namespace ivf {

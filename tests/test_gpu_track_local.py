@@ -313,7 +313,7 @@ def test_local_points_random_synthetic(iv, seed):
 
 def test_one_handle_through_every_search_equals_fresh_handles(iv):
     """The handle's owned device buffers: ONE handle (nfeatures 64, max_pairs 2) goes through run, search_local with 8 points per frame,
-    search_local with 40 (its scratch is released and allocated again after use), search_by_bow, optimize_pose and search_local with 8
+    search_local with 40 (its scratch is replaced by a larger one after use), search_by_bow, optimize_pose and search_local with 8
     again (no regrowth).  Every output is byte for byte what a fresh handle returns for that call alone; then the handle is destroyed."""
     import torch
     from iv_slam_amd import dist as ivd
@@ -400,3 +400,119 @@ def test_one_handle_through_every_search_equals_fresh_handles(iv):
     assert got["search_by_bow"][1].tolist() == [S.oracle(O, sc, 1)[1] for sc in scs] and got["search_by_bow"][1].min() > 5
     assert got["optimize_pose"][2].min() >= 3
     assert all(g.tobytes() == e.tobytes() for g, e in zip(got["search_local 8 again"], got["search_local 8"]))
+
+
+class _GrowthScene:
+    """nfeatures 64, max_pairs 2: three related random records, the local maps of frames 1 and 2 (39 and 36 points), every record's own stereo points as the points its keypoints hold (search_reloc, search_by_sim3), identity poses and an identity
+    similarity.  Each call_* takes a handle and returns that call's outputs as numpy arrays."""
+
+    def __init__(self, iv):
+        import torch
+        from iv_slam_amd import dist as ivd
+        from iv_slam_amd._lib import LOCAL_POINT_DTYPE
+        import track_bow_scenes as S
+        from test_gpu_track import _random_records, scale_table
+        self.iv, self.nf, self.dev = iv, 64, torch.device("cuda:0")
+        nf, dev = self.nf, self.dev
+        rng = np.random.default_rng(64)
+        cam = self.cam = dict(nf=nf, scale=scale_table(), fx=S.CAM["fx"], fy=S.CAM["fy"], cx=S.CAM["cx"], cy=S.CAM["cy"], bf=S.CAM["bf"],
+                              b=F(S.CAM["bf"] / S.CAM["fx"]), bounds=S.BOUNDS)
+        self.recs = recs = _random_records(rng, nf, 3, int(S.W), int(S.H), 1.0)
+        I = np.eye(4, dtype=F)
+        self.per_frame = [map_points_from(cam, recs[0], I, rng, jitter=0.0), map_points_from(cam, recs[1], I, rng, jitter=0.0)]
+        self.frames = [1, 2]
+        self.block = torch.from_numpy(ivd.pack_records(recs, nf).reshape(-1)).to(dev)
+        self.pairs = torch.tensor([(0, 1), (1, 2)], dtype=torch.int32, device=dev)
+        pts = np.zeros((3, nf), LOCAL_POINT_DTYPE); pts["flags"] = 1
+        for r, rec in enumerate(recs):
+            kp, z = rec["kps"], rec["depth"]
+            for i in np.nonzero(z > 0)[0]:
+                pos = np.array([(kp["x"][i] - cam["cx"]) * z[i] / cam["fx"], (kp["y"][i] - cam["cy"]) * z[i] / cam["fy"], z[i]], F)
+                dist = F(np.sqrt((pos.astype(np.float64) ** 2).sum()))
+                pts["pos"][r, i] = pos; pts["normal"][r, i] = pos / dist; pts["desc"][r, i] = rec["desc"][i]; pts["flags"][r, i] = 0
+                pts["max_distance"][r, i] = F(dist * cam["scale"][int(kp["octave"][i])])
+                pts["min_distance"][r, i] = F(pts["max_distance"][r, i] / cam["scale"][-1])
+        self.kf_points = torch.from_numpy(pts.view(np.uint8).reshape(-1)).to(dev)
+        self.poses = torch.from_numpy(np.tile(I[:3, :4].reshape(12), (3, 1))).to(dev)
+        sim3 = np.zeros((2, 16), F); sim3[:, [0, 4, 8, 12]] = 1.0
+        self.sim3 = torch.from_numpy(sim3).to(dev)
+
+    def fresh(self):
+        cam = self.cam
+        return self.iv.BatchTracker(self.nf, cam["scale"], float(cam["fx"]), float(cam["fy"]), float(cam["cx"]), float(cam["cy"]), float(cam["bf"]),
+                                    cam["bounds"], max_pairs=2, b=float(cam["b"]))
+
+    def _results(self, *shapes):
+        import torch
+        return [torch.full(s, -7, dtype=torch.int32, device=self.dev) for s in shapes]
+
+    @staticmethod
+    def _out(*tensors):
+        import torch
+        torch.cuda.synchronize()
+        return tuple(t.cpu().numpy() for t in tensors)
+
+    def call_run(self, tr):
+        a, nm = self._results((2, self.nf), (2,))
+        tr.run(self.block, self.pairs, a, nm)
+        return self._out(a, nm)
+
+    def call_local(self, tr, cap=40):
+        return run_local(self.iv, self.cam, self.recs, self.frames, self.per_frame, None, None, 3.0, 0.8, max_points=cap, tracker=tr)
+
+    def call_reloc(self, tr):
+        a, nm = self._results((2, self.nf), (2,))
+        a.fill_(-1)
+        tr.search_reloc(self.block, self.pairs, self.kf_points, a, nm)
+        return self._out(a, nm)
+
+    def call_sim3(self, tr):
+        import torch
+        m, nfound, m1, m2 = self._results((2, self.nf), (2,), (2, self.nf), (2, self.nf))
+        m12 = torch.full((2, self.nf), -1, dtype=torch.int32, device=self.dev)
+        self.iv.LoopSearch(tr).search_by_sim3(self.block, self.pairs, self.poses, self.kf_points, self.sim3, m12, m, nfound, match1=m1, match2=m2)
+        return self._out(m, nfound, m1, m2)
+
+    def same_as_a_fresh_handle(self, name, call, got):
+        alone = call(self.fresh())
+        assert len(got) == len(alone)
+        for g, e in zip(got, alone):
+            assert g.dtype == e.dtype and g.tobytes() == e.tobytes(), name
+
+
+def test_one_handle_grows_grids_and_queries_between_runs_and_equals_fresh_handles(iv):
+    """The growth orders of the handle's scratch no other test walks: ONE handle (nfeatures 64, max_pairs 2) goes through run,
+    search_by_sim3 (one grid per pair becomes two, first use of its own queries), run, search_local with 40 points per frame (inside the
+    nfeatures queries the handle starts with) and with 100 (the candidate scratch grows), search_reloc, search_by_sim3 again (no growth)
+    and run.  Every output is byte for byte what a fresh handle returns for that call alone."""
+    sc = _GrowthScene(iv)
+    tr = sc.fresh()
+    steps = [("run", sc.call_run), ("search_by_sim3", sc.call_sim3), ("run after the grids grew", sc.call_run), ("search_local 40", sc.call_local),
+             ("search_local 100", lambda tr: sc.call_local(tr, cap=100)), ("search_reloc", sc.call_reloc), ("search_by_sim3 again", sc.call_sim3), ("run at the end", sc.call_run)]
+    got = {}
+    for name, call in steps:
+        got[name] = call(tr)
+        sc.same_as_a_fresh_handle(name, call, got[name])
+    print("matches: run %r, sim3 %r, local 40 %r, reloc %r" % tuple(got[k][1].tolist() for k in ("run", "search_by_sim3", "search_local 40", "search_reloc")))
+    # the calls did real work, and a repeated call is the same call
+    assert got["run"][1].min() > 5 and got["search_by_sim3"][1].min() > 5 and got["search_local 40"][1].sum() > 0 and got["search_reloc"][1].min() > 5
+    for again, first in (("run after the grids grew", "run"), ("run at the end", "run"), ("search_by_sim3 again", "search_by_sim3"),
+                         ("search_local 100", "search_local 40")):                # both capacities hold every point of the scene
+        assert all(g.tobytes() == e.tobytes() for g, e in zip(got[again], got[first])), again
+
+
+def test_a_refused_growth_leaves_the_handle_with_what_it_had(iv):
+    """ONE call of search_local with max_points_per_frame = 2**30 - 1 on a handle of nfeatures 64, max_pairs 2: its candidate lists alone
+    are 2 x 2**30 x 256 B = 512 GiB, which no device holds, and they are requested first, so nothing else is allocated: an ordinary error
+    return of the allocator, made once.  The call raises the library's allocation error; the next run and search_reloc on the handle
+    succeed on the scratch it kept and equal a fresh handle's, and no stale runtime error reaches them."""
+    from iv_slam_amd._lib import IVF_E_NO_DEVICE, IvfError
+    sc = _GrowthScene(iv)
+    tr = sc.fresh()
+    with pytest.raises(IvfError) as refused:
+        sc.call_local(tr, cap=2 ** 30 - 1)
+    assert refused.value.code == IVF_E_NO_DEVICE and "device allocation failed" in str(refused.value)
+    for name, call in (("run", sc.call_run), ("search_reloc", sc.call_reloc)):
+        got = call(tr)                                                  # raises unless the call returns IVF_OK
+        sc.same_as_a_fresh_handle(name + " after the refused growth", call, got)
+        assert got[1].min() > 5
