@@ -861,6 +861,69 @@ int  ivf_tracker_reloc_candidates(ivf_tracker* t, const ivf_vocabulary* voc, con
                                   const double* d_bow_value, const int32_t* d_bow_n, const int32_t* d_frame_record, int n_frames,
                                   int max_candidates, int32_t* d_cand, int32_t* d_ncand, int32_t* d_pairs, int32_t* d_select,
                                   float* d_scores, int32_t* d_common, void* hip_stream);
+/* LoopClosing::DetectLoop (ORB/src/LoopClosing.cc:108-234) for n_queries new keyframes, on the device: with the two calls below a batch
+ * goes from gather records (ivf_tracker_bow_vectors) to mvpEnoughConsistentCandidates as the pair table
+ * ivf_tracker_search_by_bow_keyframes takes, without the host reading anything.  The database is ivf_tracker_reloc_candidates' (the
+ * current keyframes are rows of it already); new are the connected sets of every keyframe as a CSR -- d_conn_start [n_keyframes + 1],
+ * d_conn [n_conn] database indices = GetVectorCovisibleKeyFrames / GetConnectedKeyFrames, in any order -- and the queries:
+ * d_query_kf [n_queries], the database index of each current keyframe, and d_query_visible [n_queries]: keyframe k is in the inverted
+ * file of query q iff k < d_query_visible[q], it is live and k != d_query_kf[q].  That is mpKeyFrameDB->add(mpCurrentKF) after each
+ * DetectLoop (:121, :151, :220): consecutive keyframes appended in order, each with visible = its own index, give the reference's
+ * sequential result from one snapshot.  An entry of d_conn outside [0, n_keyframes) is skipped; a row whose offsets are negative,
+ * decreasing or past n_conn is empty.
+ *
+ * ivf_tracker_loop_candidates: minScore (:129-143) and KeyFrameDatabase::DetectLoopCandidates (ORB/src/KeyFrameDatabase.cc:76-197).
+ * d_query_select [n_queries] (nullable): 0 = the early return of :119 (mnId < mLastLoopKFid + 10): d_ncand = -2 and nothing else of
+ * the query is written; a d_query_kf outside the database gives d_ncand = -1 likewise.  Per query:
+ *   minScore = 1.0f, lowered with `<` by the score of every connected keyframe that is live (isBad, :135), whether or not it is visible;
+ *   the score is L1Scoring::score as in ivf_tracker_reloc_candidates (f64 terms in ascending word order, -score / 2.0, narrowed to
+ *   float), so a connected keyframe that shares no word gives -0.0f and d_min_score keeps the bits of the row's first minimum;
+ *   mnLoopWords of keyframe k = the words both vectors hold for a k in the inverted file and not in the connected row (:93-102), else 0:
+ *   a connected keyframe never enters lKFsSharingWords, never raises maxCommonWords and is never accumulated as a neighbour;
+ *   minCommonWords = (int)(maxCommonWords * 0.8f) (:120); keyframes with mnLoopWords > minCommonWords are scored (:129-135) and enter
+ *   lScoreAndMatch iff si >= minScore (:136);
+ *   per entry accScore = its score, then for its d_kf_neigh in order accScore += mLoopScore of every neighbour that was scored in THIS
+ *   query, whether or not its own score reached minScore (:159); a neighbour that was not (0 < mnLoopWords <= minCommonWords included)
+ *   adds nothing -- there is no stale score as in relocalization; pBestKF moves on a strictly greater score (:162);
+ *   bestAccScore starts at minScore (:145); entries with accScore > 0.75f * bestAccScore, strictly, are retained (:176-184) and their
+ *   distinct pBestKF come out in list order = (smallest shared word, keyframe index) of the entry (:182-193).
+ * Outputs: d_min_score [n_queries]; d_cand [n_queries][max_candidates], -1 beyond the count; d_ncand [n_queries] the true count, even
+ * above max_candidates; d_scores / d_common [n_queries][n_keyframes] (nullable) as ivf_tracker_reloc_candidates writes them.
+ * IVF_E_INVALID: a null required pointer, a negative count, max_candidates < 1.  No read outside the arrays whatever they hold; two runs
+ * are bit-identical; asynchronous on hip_stream; the scratch is ivf_tracker_reloc_candidates' (40 bytes per query and keyframe, grown
+ * on demand, a refused growth leaves the handle usable); obeys the one-call-at-a-time rule. */
+int  ivf_tracker_loop_candidates(ivf_tracker* t, const int32_t* d_kf_bow_word, const double* d_kf_bow_value, const int32_t* d_kf_bow_n,
+                                 const uint8_t* d_kf_live, const int32_t* d_kf_neigh, int n_keyframes, const int32_t* d_conn_start,
+                                 const int32_t* d_conn, int n_conn, const int32_t* d_query_kf, const int32_t* d_query_visible,
+                                 const int32_t* d_query_select, int n_queries, int max_candidates, float* d_min_score, int32_t* d_cand,
+                                 int32_t* d_ncand, float* d_scores, int32_t* d_common, void* hip_stream);
+/* ivf_tracker_loop_consistency: the covisibility-consistency groups (ORB/src/LoopClosing.cc:148-230) for the queries of the call IN
+ * ORDER, from d_cand / d_ncand of ivf_tracker_loop_candidates.  mvConsistentGroups is device memory of the caller, read and written:
+ * d_group_member [group_cap][member_cap] keyframe indices ascending, -1 padded; d_group_size and d_group_count [group_cap] (the
+ * consistency counter); d_n_groups [1]; rows at and beyond n_groups are cleared (-1, 0, 0) whenever the state is rewritten.  Per query:
+ *   d_ncand < 0 (not selected, or no such keyframe): skipped, the state is untouched;
+ *   d_ncand == 0: n_groups = 0 (:152);
+ *   else the group of candidate i is its connected row plus itself (:169-170); it is consistent with previous group iG iff they share a
+ *   keyframe (:176-187).  The new state, in candidate order: for each i the previous groups iG, ascending, for which i is the FIRST
+ *   consistent candidate (vbConsistentGroup, :193-198), each as (group of i, count[iG] + 1); then, if i is consistent with no previous
+ *   group, (group of i, 0) (:208-212).  Candidate i is enough-consistent iff count[iG] + 1 >= th for some iG it is consistent with
+ *   (:199; th = mnCovisibilityConsistencyTh, 3 in the reference), whether or not iG was flagged before.
+ * Outputs: d_enough [n_queries][max_candidates] = mvpEnoughConsistentCandidates as keyframe indices in candidate order, -1 padded;
+ * d_nenough [n_queries]; d_pairs [n_queries][max_candidates][2] = (d_kf_record[query keyframe], d_kf_record[candidate]), the
+ * (KF1, KF2) order of ivf_tracker_search_by_bow_keyframes, and d_select = 1 where both records are >= 0, else (-1, -1) and 0;
+ * d_status [n_queries].  Overflow -- a group of more than member_cap keyframes, more than group_cap new entries, or d_ncand >
+ * max_candidates (a truncated list) -- is a condition: the state stays as it was before that query, and d_status of it and of every
+ * later query of the call is 1 with d_nenough = 0 and every select 0; 0 = exact.  A query with d_nenough > 0 is where the reference
+ * goes on to ComputeSim3; the later queries of the call are computed as if that loop was rejected, which is what the reference does when
+ * ComputeSim3 returns false.  IVF_E_INVALID: a null required pointer, a negative count, max_candidates / group_cap / member_cap < 1.
+ * One workgroup walks the queries; every loop is bounded by a connected row, n_keyframes / 32, max_candidates, group_cap or member_cap.
+ * The scratch (max_candidates * ((n_keyframes + 31) / 32 + 4 + group_cap) + 1 + 3 * group_cap words of 4 bytes) sits on the handle and grows
+ * on demand. */
+int  ivf_tracker_loop_consistency(ivf_tracker* t, const int32_t* d_kf_record, int n_keyframes, const int32_t* d_conn_start,
+                                  const int32_t* d_conn, int n_conn, const int32_t* d_query_kf, int n_queries, const int32_t* d_cand,
+                                  const int32_t* d_ncand, int max_candidates, int th, int32_t* d_group_member, int32_t* d_group_size,
+                                  int32_t* d_group_count, int32_t* d_n_groups, int group_cap, int member_cap, int32_t* d_enough,
+                                  int32_t* d_nenough, int32_t* d_pairs, int32_t* d_select, int32_t* d_status, void* hip_stream);
 
 /* ---- Tracking::UpdateLocalMap and the tail of TrackLocalMap from a device-resident map ---------------------------------------------
  * The map as flat device arrays the caller keeps between calls, in the style of the keyframe database above: keyframe index = position

@@ -182,6 +182,9 @@ _SIGS = {
     "ivf_tracker_search_by_sim3": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
     "ivf_tracker_bow_vectors": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
     "ivf_tracker_reloc_candidates": (C.c_int, [vp, vp] + [vp] * 7 + [C.c_int] + [vp] * 4 + [C.c_int, C.c_int] + [vp] * 6 + [vp]),
+    "ivf_tracker_loop_candidates": (C.c_int, [vp] + [vp] * 5 + [C.c_int, vp, vp, C.c_int] + [vp] * 3 + [C.c_int, C.c_int] + [vp] * 5 + [vp]),
+    "ivf_tracker_loop_consistency": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int] + [vp] * 4 + [C.c_int, C.c_int]
+                                     + [vp] * 5 + [vp]),
     "ivf_tracker_update_local_map": (C.c_int, [vp, C.POINTER(MapViewC), vp, C.c_int, C.c_int, C.c_int] + [vp] * 8 + [vp]),
     "ivf_tracker_create_map_points": (C.c_int, [vp, vp, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, C.c_int] + [vp] * 13 + [vp]),
     "ivf_tracker_local_map_lds_keyframes": (C.c_int, []),

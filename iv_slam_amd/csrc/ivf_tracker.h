@@ -1,8 +1,10 @@
-// ivf_tracker.h -- the batched tracker handle and what its twelve translation units share (not part of the public C-ABI):
+// ivf_tracker.h -- the batched tracker handle and what its thirteen translation units share (not part of the public C-ABI):
 // ivf_track.hip (the handle's life cycle and the TrackWithMotionModel search), ivf_track_local.hip (SearchLocalPoints),
 // ivf_track_bow.hip (TrackReferenceKeyFrame and loop closing's SearchByBoW(KF, KF)), ivf_track_sim3.hip (loop closing's SearchBySim3),
 // ivf_track_reloc.hip (Relocalization's SearchByProjection and the set bookkeeping around
 // it), ivf_track_db.hip (Relocalization's first two lines: mBowVec and KeyFrameDatabase::DetectRelocalizationCandidates),
+// ivf_track_loop.hip (LoopClosing::DetectLoop: minScore, KeyFrameDatabase::DetectLoopCandidates and the consistency groups; what the two
+// database queries repeat is ivf_db.h's),
 // ivf_track_map.hip (UpdateLocalMap: the local keyframes and points of a frame from a device-resident map),
 // ivf_track_points.hip (the points a search hands to a solver and the tail of TrackLocalMap), ivf_track_create.hip
 // (LocalMapping::CreateNewMapPoints: new map points for a batch of keyframes), ivf_pose.hip
@@ -41,6 +43,12 @@ struct DbScratch {
     int *common, *minWord; float* score; float* acc; int* best; unsigned long long* place; int* list; unsigned long long* listKey; int* maxCommon;
     size_t cap; int frameCap;
 };
+
+// The handle's scratch of ivf_tracker_loop_consistency (ivf_track_loop.hip), one buffer of cap 4-byte words grown on demand and carved by
+// the call: per candidate of ONE query the bitmap of its covisibility group over the keyframes, its size, flags and first new entry; per
+// (candidate, previous group) whether they share a keyframe; per previous group its first consistent candidate; per new entry its
+// candidate and counter
+struct LoopScratch { unsigned* buf; size_t cap; };
 
 // The handle's scratch of ivf_tracker_update_local_map (ivf_track_map.hip), grown on demand: the vote rows [n_frames][n_keyframes] of the
 // calls whose n_keyframes exceeds the LDS row (voteCap ints), and per frame the hash set of the de-duplication, `slots` point ids
@@ -173,6 +181,7 @@ struct ivf_tracker {
     ivf::Sim3SearchScratch sim3s{nullptr, nullptr, nullptr};
     ivf::DbScratch db{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
     ivf::MapScratch map{nullptr, nullptr, 0, 0};
+    ivf::LoopScratch loop{nullptr, 0};
     size_t ldsBytes = 0;
     hipEvent_t evDone = nullptr;          // end of the previous call: the scratch above belongs to ONE call at a time
     bool ran = false;
