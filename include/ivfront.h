@@ -691,8 +691,8 @@ int  ivf_tracker_filter_assign(ivf_tracker* t, int32_t* d_assign, int n_frames, 
  * mvbBestInliers, accepted with MORE than mRansacMinInliers inliers) succeeds returns mRefinedTcw and mvbRefinedInliers; with none, the
  * best hypothesis and its inliers when it has at least mRansacMinInliers; else no pose.  CheckInliers (:312-343) keeps the reference's
  * float / double mix.  cvSVD, cvInvert and cvSolve(CV_SVD) are a cyclic Jacobi SVD with a fixed pair order and sweep cap: a 4-point
- * hypothesis leaves a four-dimensional null space whose basis rounding chooses, so single hypotheses are not comparable between
- * implementations; Refine's pose is.
+ * hypothesis leaves a four-dimensional null space whose basis rounding chooses, so the poses of single hypotheses are not comparable
+ * between implementations (what they compute around that basis is: ivf_test_pnp_hypotheses below); Refine's pose is.
  * d_draws [n_frames][max_iterations][4]: the draws contract above with K = 4, the sampling of :192-205.
  * Outputs: d_poses [n_frames][12] (row-major 3x4, the f64 mRi / mti narrowed to float, :221-227 / :298-304) is written only where a
  * pose is returned; d_inlier [n_frames][nfeatures] = vbInliers by keypoint; d_ninliers [n_frames] = nInliers, 0 = cv::Mat() (also for
@@ -707,6 +707,21 @@ int  ivf_tracker_solve_pnp(ivf_tracker* t, const uint8_t* d_records, size_t reco
                            const float* d_xw, const uint8_t* d_has_point, const uint32_t* d_draws, int max_iterations, double probability,
                            int min_inliers, float epsilon, float th2, float* d_poses, uint8_t* d_inlier, int32_t* d_ninliers,
                            int32_t* d_iterations, float* d_hyp_poses, int32_t* d_hyp_ninliers, void* hip_stream);
+/* Testing hook: the hypotheses of ivf_tracker_solve_pnp with their intermediate values.  The inputs are those of that call; its first
+ * two launches run (the correspondences with mRansacMaxIts, then one wave per hypothesis), the bookkeeping of :213-259 and Refine do
+ * not.  d_hyp_poses and d_hyp_ninliers (both required here) receive what that call writes into them, to the bit.  d_taps
+ * [n_frames][max_iterations][IVF_PNP_TAP_DOUBLES] receives one record of doubles per iteration below mRansacMaxIts, the others and the
+ * frames with a bad record index are untouched: [0, 4) the sample, as indices into the frame's correspondences in the order drawn
+ * (PnPsolver.cc:192-205); [4, 16) cws[4][3] (choose_control_points); [16, 64) the four vectors ut + 12 * (11 - i), i = 0 .. 3, of MtM
+ * (:501-503); [64, 76) the singular values of MtM, descending; then per candidate c = 0, 1, 2 (find_betas_approx_1, _2, _3) at
+ * 76 + 21 c: the betas before gauss_newton (4) and after it (4), R (9, row-major), t (3) and the reprojection error; [139] the
+ * candidate chosen (:522-524).  IVF_E_INVALID as for ivf_tracker_solve_pnp, and for a null d_taps, d_hyp_poses or d_hyp_ninliers.
+ * Asynchronous on hip_stream; the handle's one-call-at-a-time rule holds. */
+#define IVF_PNP_TAP_DOUBLES 140
+int  ivf_test_pnp_hypotheses(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_frames, int n_frames,
+                             const float* d_xw, const uint8_t* d_has_point, const uint32_t* d_draws, int max_iterations, double probability,
+                             int min_inliers, float epsilon, float th2, double* d_taps, float* d_hyp_poses, int32_t* d_hyp_ninliers,
+                             void* hip_stream);
 /* Batched Sim3Solver (ORB/src/Sim3Solver.cc), the step of LoopClosing::ComputeSim3 (ORB/src/LoopClosing.cc:279-306) between
  * SearchByBoW(mpCurrentKF, pKF, vvpMapPointMatches[i]) and SearchBySim3: Horn's closed form on three 3D-3D correspondences inside a
  * RANSAC loop, for pair p = (KF1 = current keyframe record d_pairs[p][0], KF2 = candidate record d_pairs[p][1]).  d_select as in

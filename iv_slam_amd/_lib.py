@@ -176,6 +176,8 @@ _SIGS = {
     "ivf_tracker_filter_assign": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, vp]),
     "ivf_tracker_solve_pnp": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_float, C.c_float,
                                         vp, vp, vp, vp, vp, vp, vp]),
+    "ivf_test_pnp_hypotheses": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_float, C.c_float,
+                                          vp, vp, vp, vp]),
     "ivf_tracker_solve_sim3": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_int,
                                          vp, vp, vp, vp, vp, vp, vp, vp]),
     "ivf_tracker_search_by_bow_keyframes": (C.c_int, [vp, vp, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_int, vp, vp, C.c_float, C.c_int, vp, vp, vp]),

@@ -14,6 +14,8 @@
 //                   it can only change its answer at an iteration that raises mnBestInliers: it runs there (compute_pose over up to
 //                   nfeatures points as a workgroup reduction) and nowhere else.  The first success returns mRefinedTcw; without one the
 //                   best hypothesis is returned when it has mRansacMinInliers inliers.
+// ivf_test_pnp_hypotheses (testing hook) runs the first two with k_pnp_hyp<true>, which also leaves the intermediate values of every
+// hypothesis (sample, control points, the four vectors, the betas, every candidate's pose and error) in a buffer of doubles.
 // compute_pose is one text for both sizes (template on the thread count).  The sums over points go through xor-butterflies in the wave and
 // through LDS in wave order: the tree is fixed, two runs are bit-identical.  The 12x12 MtM, its vectors and every small matrix live in
 // LDS; a Jacobi rotation is spread over lanes (one matrix row each).  Every loop has a compile-time bound: NaN cannot spin a kernel.
@@ -217,9 +219,14 @@ DEVINL bool is_inlier(const double* R, const double* t, double fu, double fv, do
     return error2 < c.maxErr;
 }
 
+// The record of doubles ivf_test_pnp_hypotheses receives per hypothesis (include/ivfront.h)
+constexpr int kTapSample = 0, kTapCws = 4, kTapVv = 16, kTapW = 64, kTapCand = 76, kTapCandStride = 21, kTapBest = 139, kTapDoubles = IVF_PNP_TAP_DOUBLES;
+static_assert(kTapCand + 3 * kTapCandStride == kTapBest && kTapBest + 1 == kTapDoubles, "the record of include/ivfront.h");
+
 // compute_pose (:481-529) over the n correspondences corr[list[0 .. n)] -> S.R, S.t.  Called by all NT threads of the workgroup.
-template <int NT>
-DEVINL void compute_pose(Ws& S, const PnpParams& P, const Corr* __restrict__ corr, const unsigned short* list, int n, int tid)
+// TAP: the testing hook's instantiation also leaves its intermediate values in tap[0 .. kTapDoubles); the product's has no such code.
+template <int NT, bool TAP = false>
+DEVINL void compute_pose(Ws& S, const PnpParams& P, const Corr* __restrict__ corr, const unsigned short* list, int n, int tid, double* tap = nullptr)
 {
     const double fu = P.fu, fv = P.fv, uc = P.uc, vc = P.vc, dn = (double)n;
     // ---- choose_control_points (:379-413)
@@ -313,6 +320,10 @@ DEVINL void compute_pose(Ws& S, const PnpParams& P, const Corr* __restrict__ cor
     // ---- the four vectors of the smallest singular values (ut + 12 * (11 - i)), compute_L_6x10 (:764-804), compute_rho (:806-814)
     if (tid < 48) { const int i = tid / 12, e = tid % 12; S.vv[i][e] = S.V[e * 12 + S.ord[11 - i]]; }
     __syncthreads();
+    if constexpr (TAP) {
+        if (tid < 12) { tap[kTapCws + tid] = S.cws[tid / 3][tid % 3]; tap[kTapW + tid] = S.w[S.ord[tid]]; }
+        if (tid < 48) tap[kTapVv + tid] = S.vv[tid / 12][tid % 12];
+    }
     if (tid == 0) {
         for (int i = 0; i < 6; i++) {
             // pair i of (a, b): (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
@@ -356,7 +367,11 @@ DEVINL void compute_pose(Ws& S, const PnpParams& P, const Corr* __restrict__ cor
                 bt[2] = cand == 1 ? 0.0 : b[3] / bt[0];
                 bt[3] = 0.0;
             }
+            if constexpr (TAP)
+                for (int k = 0; k < 4; k++) tap[kTapCand + kTapCandStride * cand + k] = bt[k];
             gauss_newton(S);
+            if constexpr (TAP)
+                for (int k = 0; k < 4; k++) tap[kTapCand + kTapCandStride * cand + 4 + k] = bt[k];
             // compute_ccs (:457-468), and solve_for_sign (:640-653) on the first point's pcs[2]
             for (int j = 0; j < 4; j++)
                 for (int k = 0; k < 3; k++) S.ccs[j][k] = 0.0;
@@ -458,6 +473,15 @@ DEVINL void compute_pose(Ws& S, const PnpParams& P, const Corr* __restrict__ cor
         if (S.err[2] < S.err[best]) best = 2;
         for (int k = 0; k < 9; k++) S.R[k] = S.Rs[best][k];
         for (int k = 0; k < 3; k++) S.t[k] = S.ts[best][k];
+        if constexpr (TAP) {
+            for (int c = 0; c < 3; c++) {
+                double* o = tap + kTapCand + kTapCandStride * c + 8;
+                for (int k = 0; k < 9; k++) o[k] = S.Rs[c][k];
+                for (int k = 0; k < 3; k++) o[9 + k] = S.ts[c][k];
+                o[12] = S.err[c];
+            }
+            tap[kTapBest] = (double)best;
+        }
     }
     __syncthreads();
 }
@@ -521,9 +545,11 @@ __global__ __launch_bounds__(256) void k_pnp_prepare(PnpParams P, const uint8_t*
 }
 
 // ---- one hypothesis ------------------------------------------------------------------------------------------------------------------
+// TAP (ivf_test_pnp_hypotheses): also one record of taps per hypothesis it runs; the product launches k_pnp_hyp<false>, taps == nullptr
+template <bool TAP>
 __global__ __launch_bounds__(64) void k_pnp_hyp(PnpParams P, const Corr* __restrict__ corrAll, const int4* __restrict__ head,
                                                 const uint32_t* __restrict__ draws, double* __restrict__ hypPose, int* __restrict__ hypN,
-                                                float* __restrict__ outPoses, int* __restrict__ outN)
+                                                float* __restrict__ outPoses, int* __restrict__ outN, double* __restrict__ taps)
 {
     __shared__ Ws S;
     __shared__ unsigned short s_list[4];
@@ -541,7 +567,10 @@ __global__ __launch_bounds__(64) void k_pnp_hyp(PnpParams P, const Corr* __restr
         for (int k = 0; k < 4; k++) s_list[k] = (unsigned short)smp[k];
     }
     __syncthreads();
-    compute_pose<64>(S, P, corr, s_list, 4, tid);
+    double* tap = TAP ? taps + slot * kTapDoubles : nullptr;
+    if constexpr (TAP)
+        if (tid < 4) tap[kTapSample + tid] = (double)s_list[tid];
+    compute_pose<64, TAP>(S, P, corr, s_list, 4, tid, tap);
     double R[9], t[3];
     load_solution(S, R, t);
     const int ni = count_inliers<64>(P, R, t, corr, N, tid, s_wcnt, nullptr);
@@ -602,20 +631,16 @@ __global__ __launch_bounds__(kRefThreads) void k_pnp_replay(PnpParams P, const C
 
 }  // namespace
 
-extern "C" {
-
-int ivf_tracker_solve_pnp(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_frames, int n_frames,
-                          const float* d_xw, const uint8_t* d_has_point, const uint32_t* d_draws, int max_iterations, double probability,
-                          int min_inliers, float epsilon, float th2, float* d_poses, uint8_t* d_inlier, int32_t* d_ninliers, int32_t* d_iterations,
-                          float* d_hyp_poses, int32_t* d_hyp_ninliers, void* hip_stream)
+// What the two entry points below share: the argument checks, the handle's scratch at its first use, the uniform arguments, and the first
+// launch.  inlier / nInliers / iterations are k_pnp_prepare's outputs.
+static int pnp_begin(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, int n_frames, int max_iterations, double probability,
+                     int min_inliers, float epsilon, float th2, hipStream_t st, PnpParams& P)
 {
-    if (!t || !d_records || !d_frames || !d_xw || !d_has_point || !d_draws || !d_poses || !d_inlier || !d_ninliers) return fail(IVF_E_INVALID, "null argument");
     const int ra = ransac_args_ok(d_records, max_iterations, probability, min_inliers);
     if (ra != IVF_OK) return ra;
     if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(IVF_E_INVALID, "epsilon %g outside [0,1]", (double)epsilon);
     if (!(th2 > 0.0f)) return fail(IVF_E_INVALID, "min_inliers must be >= 0 and th2 positive");
     if (n_frames == 0) return IVF_OK;
-    hipStream_t st = (hipStream_t)hip_stream;
     const int rc = tracker_begin(t, true, record_bytes, n_records, n_frames, st);
     if (rc != IVF_OK) return rc;
     if (!t->pnp.corr) {                                                // first use: the scratch of ONE call, sized by max_pairs
@@ -624,19 +649,55 @@ int ivf_tracker_solve_pnp(ivf_tracker* t, const uint8_t* d_records, size_t recor
                          {t->pnp.hypPose, np * kRansacMaxIterations * 12 * sizeof(double)}, {t->pnp.hypN, np * kRansacMaxIterations * sizeof(int)}}))
             return fail(IVF_E_NO_DEVICE, "device allocation failed for the PnP scratch of %d frames x %d features", t->cfg.max_pairs, t->P.nf);
     }
-    PnpParams P;
     P.nf = t->P.nf; P.nRecords = n_records; P.recBytes = t->P.recBytes;
     P.fu = (double)t->P.fx; P.fv = (double)t->P.fy; P.uc = (double)t->P.cx; P.vc = (double)t->P.cy;
     level_sigma2(t->P, P.sigma2);
     P.maxIterations = max_iterations; P.minInliers = min_inliers; P.probability = probability; P.epsilon = epsilon; P.th2 = th2;
+    return IVF_OK;
+}
+
+extern "C" {
+
+int ivf_tracker_solve_pnp(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_frames, int n_frames,
+                          const float* d_xw, const uint8_t* d_has_point, const uint32_t* d_draws, int max_iterations, double probability,
+                          int min_inliers, float epsilon, float th2, float* d_poses, uint8_t* d_inlier, int32_t* d_ninliers, int32_t* d_iterations,
+                          float* d_hyp_poses, int32_t* d_hyp_ninliers, void* hip_stream)
+{
+    if (!t || !d_records || !d_frames || !d_xw || !d_has_point || !d_draws || !d_poses || !d_inlier || !d_ninliers) return fail(IVF_E_INVALID, "null argument");
+    hipStream_t st = (hipStream_t)hip_stream;
+    PnpParams P;
+    const int rc = pnp_begin(t, d_records, record_bytes, n_records, n_frames, max_iterations, probability, min_inliers, epsilon, th2, st, P);
+    if (rc != IVF_OK || n_frames == 0) return rc;
     Corr* corr = (Corr*)t->pnp.corr;
     int4* head = (int4*)t->pnp.head;
     hipLaunchKernelGGL(k_pnp_prepare, dim3(n_frames), dim3(256), 0, st, P, d_records, d_frames, d_xw, d_has_point, corr, head, d_inlier, d_ninliers,
                        d_iterations);
-    hipLaunchKernelGGL(k_pnp_hyp, dim3(max_iterations, n_frames), dim3(64), 0, st, P, (const Corr*)corr, (const int4*)head, d_draws, t->pnp.hypPose,
-                       t->pnp.hypN, d_hyp_poses, d_hyp_ninliers);
+    hipLaunchKernelGGL(k_pnp_hyp<false>, dim3(max_iterations, n_frames), dim3(64), 0, st, P, (const Corr*)corr, (const int4*)head, d_draws, t->pnp.hypPose,
+                       t->pnp.hypN, d_hyp_poses, d_hyp_ninliers, (double*)nullptr);
     hipLaunchKernelGGL(k_pnp_replay, dim3(n_frames), dim3(kRefThreads), (size_t)P.nf * sizeof(unsigned short), st, P, (const Corr*)corr,
                        (const int4*)head, (const double*)t->pnp.hypPose, (const int*)t->pnp.hypN, d_poses, d_inlier, d_ninliers, d_iterations);
+    return tracker_end(t, st);
+}
+
+// testing hook (see include/ivfront.h).  k_pnp_prepare's vbInliers reset and nInliers have no caller here: they go to the scratch that
+// k_pnp_hyp, the next launch on the stream, fills afterwards (hypPose holds 300 * 96 bytes per frame, hypN 300 ints).
+int ivf_test_pnp_hypotheses(ivf_tracker* t, const uint8_t* d_records, size_t record_bytes, int n_records, const int32_t* d_frames, int n_frames,
+                            const float* d_xw, const uint8_t* d_has_point, const uint32_t* d_draws, int max_iterations, double probability,
+                            int min_inliers, float epsilon, float th2, double* d_taps, float* d_hyp_poses, int32_t* d_hyp_ninliers, void* hip_stream)
+{
+    static_assert((size_t)kMaxTrackFeatures <= (size_t)kRansacMaxIterations * 12 * sizeof(double), "nfeatures flags fit a frame's hypPose rows");
+    if (!t || !d_records || !d_frames || !d_xw || !d_has_point || !d_draws || !d_taps || !d_hyp_poses || !d_hyp_ninliers)
+        return fail(IVF_E_INVALID, "null argument");
+    hipStream_t st = (hipStream_t)hip_stream;
+    PnpParams P;
+    const int rc = pnp_begin(t, d_records, record_bytes, n_records, n_frames, max_iterations, probability, min_inliers, epsilon, th2, st, P);
+    if (rc != IVF_OK || n_frames == 0) return rc;
+    Corr* corr = (Corr*)t->pnp.corr;
+    int4* head = (int4*)t->pnp.head;
+    hipLaunchKernelGGL(k_pnp_prepare, dim3(n_frames), dim3(256), 0, st, P, d_records, d_frames, d_xw, d_has_point, corr, head, (uint8_t*)t->pnp.hypPose,
+                       t->pnp.hypN, (int*)nullptr);
+    hipLaunchKernelGGL(k_pnp_hyp<true>, dim3(max_iterations, n_frames), dim3(64), 0, st, P, (const Corr*)corr, (const int4*)head, d_draws, t->pnp.hypPose,
+                       t->pnp.hypN, d_hyp_poses, d_hyp_ninliers, d_taps);
     return tracker_end(t, st);
 }
 

@@ -14,6 +14,7 @@ from ._lib import Bounds, TrackConfig, check
 LOCAL_POINT_BYTES = _lib.LOCAL_POINT_DTYPE.itemsize                      # sizeof(ivf_local_point); _lib asserts the dtype's size
 KF_NEIGH = 10                                                            # the neighbours a kf_neigh row holds: GetBestCovisibilityKeyFrames(10)
 KF_NEIGH_IS = "kf_neigh is [n_keyframes, %d]" % KF_NEIGH
+PNP_TAP_DOUBLES = 140                                                    # IVF_PNP_TAP_DOUBLES: the record of pnp_hypotheses() per hypothesis
 
 # The kinds of tensor a pointer argument can be: (name, element size, floating point; None = either).
 I32, F32, F64, U8 = ("int32", 4, False), ("float32", 4, True), ("float64", 8, True), ("uint8", 1, False)
@@ -387,6 +388,21 @@ class BatchTracker:
             p("ninliers", ninliers, I32, n_frames), p("iterations", iterations, I32, n_frames, optional=True),
             p("hyp_poses", hyp_poses, F32, n_frames * mi * 12, optional=True), p("hyp_ninliers", hyp_ninliers, I32, n_frames * mi, optional=True),
             stream_ptr))
+
+    def pnp_hypotheses(self, records, frames, xw, has_point, draws, taps, hyp_poses, hyp_ninliers, max_iterations=300, probability=0.99,
+                       min_inliers=10, epsilon=0.5, th2=5.991, stream_ptr=None):
+        """Testing hook (ivf_test_pnp_hypotheses): the hypotheses of solve_pnp() on the same inputs, without the bookkeeping and Refine
+        after them.  hyp_poses: torch.float32 [n_frames, max_iterations, 12] and hyp_ninliers: torch.int32 [n_frames, max_iterations]
+        as solve_pnp() writes them; taps: torch.float64 [n_frames, max_iterations, PNP_TAP_DOUBLES], one record per iteration below
+        mRansacMaxIts (the layout: include/ivfront.h).  Asynchronous on the given stream."""
+        p, nf, mi = partial(_ptr, self.device), self.nfeatures, int(max_iterations)
+        (records_p, n_rec), n_frames = self._records(records), _tensor("frames", frames).numel()
+        check(self._lib.ivf_test_pnp_hypotheses(
+            self._h, records_p, self.record_bytes, n_rec, p("frames", frames, I32, n_frames), n_frames, p("xw", xw, F32, n_frames * nf * 3),
+            p("has_point", has_point, U8, n_frames * nf), p("draws", draws, ANY4, n_frames * mi * 4, what="draws are [n_frames, max_iterations, 4]"),
+            mi, float(probability), int(min_inliers), float(epsilon), float(th2),
+            p("taps", taps, F64, n_frames * mi * PNP_TAP_DOUBLES, what="taps are [n_frames, max_iterations, %d]" % PNP_TAP_DOUBLES),
+            p("hyp_poses", hyp_poses, F32, n_frames * mi * 12), p("hyp_ninliers", hyp_ninliers, I32, n_frames * mi), stream_ptr))
 
     def solve_sim3(self, records, pairs, poses, kf_xw, point_flags, match12, draws, sim3, inlier, ninliers, max_iterations=300, probability=0.99,
                    min_inliers=20, fix_scale=True, select=None, state=None, iterations=None, hyp_sim3=None, hyp_ninliers=None, stream_ptr=None):

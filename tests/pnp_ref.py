@@ -5,7 +5,11 @@ It is the yardstick of ivf_tracker_solve_pnp (iv_slam_amd/csrc/ivf_pnp.hip); Ope
 
 cvSVD / cvInvert / cvSolve(CV_SVD) have two interchangeable back ends: "numpy" (numpy.linalg.svd) and "jacobi" (a plain cyclic one-sided
 Jacobi written below).  A 4-point hypothesis has an 8x12 M, so MtM has a four-dimensional null space whose basis rounding chooses: two
-correct back ends may return different poses for the same sample.  Only compute_pose on >= 11 non-planar points (Refine) is comparable."""
+correct back ends may return different poses for the same sample.  compute_pose on >= 11 non-planar points (Refine) is comparable as a
+whole.  Of a hypothesis, everything but that basis is: pose_tail() is compute_pose after the SVD of MtM as a function of a GIVEN basis
+(well conditioned: tests/test_pnp_hyp_cpu.py measures its spread), null_basis() what comes before.  tests/test_gpu_pnp_hyp.py takes the
+device's basis from the taps of ivf_test_pnp_hypotheses, checks that it is a null-space basis of the M numpy builds, and replays the tail
+on it; which basis of that space the device's SVD chose is the one thing still taken as given."""
 import itertools
 import math
 
@@ -164,11 +168,11 @@ def qr_solve(A, b, x):
     return x
 
 
-def gauss_newton(L, rho, betas):
+def gauss_newton(L, rho, betas, steps=5):
     bt = np.array(betas, D)
     x = np.zeros(4)
     with np.errstate(all="ignore"):
-        for _ in range(5):
+        for _ in range(steps):
             A = np.zeros((6, 4)); b = np.zeros(6)
             for i in range(6):
                 r = L[i]
@@ -199,44 +203,88 @@ def canonical_signs(V):
 PAIRS = [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]
 
 
-def compute_pose(X, uv, cam, backend="numpy", perm=None):
-    """compute_pose (:481-529) on the correspondences X [n,3] float, uv [n,2] float -> (R [3,3], t [3], reprojection error).
-    perm: an order of the points for the sums over them (the first point, whose pcs[2] decides the sign, stays the first)."""
+# Wrong readings of PnPsolver.cc that pose_tail(mis={...}) injects; tests/test_pnp_hyp_cpu.py shows that each one moves a tapped quantity of
+# some named scene by more than the bound of tests/test_gpu_pnp_hyp.py.
+MISREADINGS = ("approx1_cols",        # find_betas_approx_1 on columns 0, 1, 2, 3 of L_6x10 instead of 0, 1, 3, 6 (:677-683)
+               "b0_branch_cand0",     # find_betas_approx_1 without its b[0] < 0 branch (:688-693): the signs of betas 1..3 not turned
+               "b0_branch_cand12",    # find_betas_approx_2 / _3 without theirs (:721-727, :751-757): betas[1] from b[2] > 0 only
+               "no_b1_flip",          # if (b[1] < 0) betas[0] = -betas[0] dropped (:729, :759)
+               "b3_undivided",        # betas[2] = b[3] instead of b[3] / betas[0] (:761)
+               "gn_4_steps",          # four Gauss-Newton steps instead of five (:849)
+               "sign_last_point",     # solve_for_sign on the last point's pcs[2] instead of the first's (:642)
+               "det_row0",            # the determinant fix applied to row 0 of R instead of row 2 (:616-620)
+               "best_le",             # the best candidate chosen with <= (:522-524)
+               "best_02")             # the best candidate chosen from rep_errors[0] and [2] only
+
+
+def choose_best(err, mis=()):
+    """:522-524: N = 1, if (rep_errors[2] < rep_errors[1]) N = 2, ... as the three-way strict comparison it amounts to"""
+    lt = (lambda a, b: a <= b) if "best_le" in mis else (lambda a, b: a < b)
+    best = 0
+    if "best_02" not in mis and lt(err[1], err[0]):
+        best = 1
+    if lt(err[2], err[best]):
+        best = 2
+    return best
+
+
+def control_points(svd, pw):
+    """choose_control_points (:379-413) -> cws [4,3]"""
+    n = len(pw)
+    cws = np.zeros((4, 3))
+    cws[0] = pw.sum(0) / n
+    pw0 = pw - cws[0]
+    _, dc, uc_t = svd(pw0.T @ pw0)
+    uc_t = canonical_signs(uc_t)
+    for i in range(1, 4):
+        cws[i] = cws[0] + math.sqrt(dc[i - 1] / n) * uc_t[:, i - 1] if dc[i - 1] >= 0 else np.nan
+    return cws
+
+
+def barycentric(svd, cws):
+    """compute_barycentric_coordinates (:415-437) -> the function p [k,3] -> alphas [k,4]"""
+    cc = (cws[1:] - cws[0]).T
+    ci = pinv_solve(svd, cc, np.eye(3))
+
+    def alphas_of(p):
+        a = np.zeros((len(p), 4))
+        d = p - cws[0]
+        for j in range(3):
+            a[:, 1 + j] = (ci[j, 0] * d[:, 0] + ci[j, 1] * d[:, 1]) + ci[j, 2] * d[:, 2]
+        a[:, 0] = ((1.0 - a[:, 1]) - a[:, 2]) - a[:, 3]
+        return a
+    return alphas_of
+
+
+def fill_M(al, us, cam):
+    """fill_M (:440-455) -> M [2n,12]"""
+    fu, fv, uc, vc = (D(F(cam[k])) for k in ("fx", "fy", "cx", "cy"))
+    M = np.zeros((2 * len(al), 12))
+    for i in range(4):
+        M[0::2, 3 * i] = al[:, i] * fu; M[0::2, 3 * i + 2] = al[:, i] * (uc - us[:, 0])
+        M[1::2, 3 * i + 1] = al[:, i] * fv; M[1::2, 3 * i + 2] = al[:, i] * (vc - us[:, 1])
+    return M
+
+
+def pose_tail(X, uv, cam, cws, vv, backend="numpy", perm=None, mis=()):
+    """Everything of compute_pose after the SVD of MtM (:505-524), as a function of a GIVEN basis: the correspondences X [n,3] float,
+    uv [n,2] float, the control points cws [4,3] and the four vectors vv [4,12] (vv[i] = ut + 12 * (11 - i)).  compute_L_6x10, compute_rho,
+    the three find_betas_approx, gauss_newton, compute_R_and_t, reprojection_error, the choice.  -> dict(betas0 [3,4] (before
+    gauss_newton), betas1 [3,4] (after it), R [3,3,3], t [3,3], err [3], best).  perm as in compute_pose; mis: MISREADINGS."""
     svd = BACKENDS[backend]
+    mis = frozenset(mis)
+    assert mis <= set(MISREADINGS), mis
     pw = np.asarray(X, F).astype(D); us = np.asarray(uv, F).astype(D)
     n = len(pw)
-    first = pw[0].copy()
+    first = pw[-1].copy() if "sign_last_point" in mis else pw[0].copy()
     if perm is not None:
         pw = pw[perm]; us = us[perm]
+    cws = np.asarray(cws, D); v = [np.asarray(vv[i], D) for i in range(4)]
     fu, fv, uc, vc = (D(F(cam[k])) for k in ("fx", "fy", "cx", "cy"))
+    out = dict(betas0=np.zeros((3, 4)), betas1=np.zeros((3, 4)), R=np.zeros((3, 3, 3)), t=np.zeros((3, 3)), err=np.zeros(3))
     with np.errstate(all="ignore"):
-        # choose_control_points
-        cws = np.zeros((4, 3))
-        cws[0] = pw.sum(0) / n
-        pw0 = pw - cws[0]
-        _, dc, uc_t = svd(pw0.T @ pw0)
-        uc_t = canonical_signs(uc_t)
-        for i in range(1, 4):
-            cws[i] = cws[0] + math.sqrt(dc[i - 1] / n) * uc_t[:, i - 1] if dc[i - 1] >= 0 else np.nan
-        # compute_barycentric_coordinates
-        cc = (cws[1:] - cws[0]).T
-        ci = pinv_solve(svd, cc, np.eye(3))
-
-        def alphas_of(p):
-            a = np.zeros((len(p), 4))
-            d = p - cws[0]
-            for j in range(3):
-                a[:, 1 + j] = (ci[j, 0] * d[:, 0] + ci[j, 1] * d[:, 1]) + ci[j, 2] * d[:, 2]
-            a[:, 0] = ((1.0 - a[:, 1]) - a[:, 2]) - a[:, 3]
-            return a
+        alphas_of = barycentric(svd, cws)
         al = alphas_of(pw)
-        # fill_M, MtM
-        M = np.zeros((2 * n, 12))
-        for i in range(4):
-            M[0::2, 3 * i] = al[:, i] * fu; M[0::2, 3 * i + 2] = al[:, i] * (uc - us[:, 0])
-            M[1::2, 3 * i + 1] = al[:, i] * fv; M[1::2, 3 * i + 2] = al[:, i] * (vc - us[:, 1])
-        _, _, V = svd(M.T @ M)
-        v = [V[:, 11 - i] for i in range(4)]
         # compute_L_6x10, compute_rho
         L = np.zeros((6, 10)); rho = np.zeros(6)
         for i, (a, b) in enumerate(PAIRS):
@@ -245,24 +293,26 @@ def compute_pose(X, uv, cam, backend="numpy", perm=None):
                     2.0 * (dv[0] @ dv[3]), 2.0 * (dv[1] @ dv[3]), 2.0 * (dv[2] @ dv[3]), dv[3] @ dv[3]]
             rho[i] = ((cws[a] - cws[b]) ** 2).sum()
         a_first = alphas_of(first[None])[0]
-        results = []
-        for cand, cols in enumerate(([0, 1, 3, 6], [0, 1, 2], [0, 1, 2, 3, 4])):
+        for cand, cols in enumerate(([0, 1, 2, 3] if "approx1_cols" in mis else [0, 1, 3, 6], [0, 1, 2], [0, 1, 2, 3, 4])):
             b = pinv_solve(svd, L[:, cols], rho)
             bt = np.zeros(4)
+            neg = b[0] < 0 and ("b0_branch_cand0" if cand == 0 else "b0_branch_cand12") not in mis
             if cand == 0:
-                if b[0] < 0:
+                if neg:
                     bt[0] = math.sqrt(-b[0]); bt[1:] = -b[1:] / bt[0]
                 else:
                     bt[0] = math.sqrt(b[0]) if b[0] >= 0 else np.nan; bt[1:] = b[1:] / bt[0]
             else:
-                if b[0] < 0:
+                if neg:
                     bt[0] = math.sqrt(-b[0]); bt[1] = math.sqrt(-b[2]) if b[2] < 0 else 0.0
                 else:
                     bt[0] = math.sqrt(b[0]) if b[0] >= 0 else np.nan; bt[1] = math.sqrt(b[2]) if b[2] > 0 else 0.0
-                if b[1] < 0:
+                if b[1] < 0 and "no_b1_flip" not in mis:
                     bt[0] = -bt[0]
-                bt[2] = 0.0 if cand == 1 else b[3] / bt[0]
-            bt = gauss_newton(L, rho, bt)
+                bt[2] = 0.0 if cand == 1 else (b[3] if "b3_undivided" in mis else b[3] / bt[0])
+            out["betas0"][cand] = bt
+            bt = gauss_newton(L, rho, bt, 4 if "gn_4_steps" in mis else 5)
+            out["betas1"][cand] = bt
             # compute_ccs, compute_pcs, solve_for_sign
             ccs = np.zeros((4, 3))
             for i in range(4):
@@ -276,20 +326,38 @@ def compute_pose(X, uv, cam, backend="numpy", perm=None):
             U, _, Vv = svd(abt)
             R = U @ Vv.T
             if np.linalg.det(R) < 0 if np.isfinite(R).all() else False:
-                R[2] = -R[2]
+                k = 0 if "det_row0" in mis else 2
+                R[k] = -R[k]
             t = pc0 - R @ pwc
             # reprojection_error
             Pc = pw @ R.T + t
             inv = 1.0 / Pc[:, 2]
             ue = uc + fu * Pc[:, 0] * inv; ve = vc + fv * Pc[:, 1] * inv
-            err = np.sqrt((us[:, 0] - ue) ** 2 + (us[:, 1] - ve) ** 2).sum() / n
-            results.append((R, t, err))
-        best = 0
-        if results[1][2] < results[0][2]:
-            best = 1
-        if results[2][2] < results[best][2]:
-            best = 2
-    return results[best]
+            out["R"][cand] = R; out["t"][cand] = t
+            out["err"][cand] = np.sqrt((us[:, 0] - ue) ** 2 + (us[:, 1] - ve) ** 2).sum() / n
+        out["best"] = choose_best(out["err"], mis)
+    return out
+
+
+def null_basis(X, uv, cam, backend="numpy", perm=None):
+    """compute_pose up to the SVD of MtM (:485-503) -> (cws [4,3], vv [4,12], the 12 singular values of MtM descending, M [2n,12])"""
+    svd = BACKENDS[backend]
+    pw = np.asarray(X, F).astype(D); us = np.asarray(uv, F).astype(D)
+    if perm is not None:
+        pw = pw[perm]; us = us[perm]
+    with np.errstate(all="ignore"):
+        cws = control_points(svd, pw)
+        M = fill_M(barycentric(svd, cws)(pw), us, cam)
+        _, w, V = svd(M.T @ M)
+    return cws, np.stack([V[:, 11 - i] for i in range(4)]), w, M
+
+
+def compute_pose(X, uv, cam, backend="numpy", perm=None):
+    """compute_pose (:481-529) on the correspondences X [n,3] float, uv [n,2] float -> (R [3,3], t [3], reprojection error).
+    perm: an order of the points for the sums over them (the first point, whose pcs[2] decides the sign, stays the first)."""
+    cws, vv, _, _ = null_basis(X, uv, cam, backend, perm)
+    o = pose_tail(X, uv, cam, cws, vv, backend, perm)
+    return o["R"][o["best"]], o["t"][o["best"]], o["err"][o["best"]]
 
 
 def pose12(R, t):

@@ -136,3 +136,16 @@ def test_header_is_plain_c(tmp_path):
         r = subprocess.run(["gcc", "-o", str(exe), str(obj), lib, "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath,/opt/rocm/lib"],
                            capture_output=True, text=True)
         assert r.returncode == 0, r.stderr
+
+
+def test_testing_hooks_are_declared_as_such():
+    """an ivf_test_* entry point exists for the suite alone: the comment above its declaration says so, and the binding carries it like any
+    other symbol (a hook that is exported but unbound, or bound but undeclared, fails test_library_exports_every_declared_symbol)"""
+    import re
+    from iv_slam_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "ivfront.h")).read()
+    hooks = [s for s in header_symbols() if s.startswith("ivf_test_")]
+    assert hooks == ["ivf_test_pnp_hypotheses", "ivf_test_retain_best"] == sorted(s for s in _lib.EXPORTED_SYMBOLS if s.startswith("ivf_test_"))
+    for name in hooks:
+        m = re.search(r"/\*((?:(?!\*/).)*)\*/\s*(?:#define \w+ \d+\s*)?int\s+%s\s*\(" % name, hdr, flags=re.S)
+        assert m and "testing hook" in m.group(1).lower(), name

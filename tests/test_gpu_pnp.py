@@ -1,7 +1,10 @@
 """ivf_tracker_solve_pnp (iv_slam_amd/csrc/ivf_pnp.hip) -- PnPsolver (ORB/src/PnPsolver.cc) as Tracking::Relocalization runs it, batched on
 the device -- against tests/pnp_ref.py, the f64 restatement, on the scenes of tests/pnp_scenes.py.
 
-A 4-point hypothesis is not comparable between implementations (its MtM has a four-dimensional null space, see tests/pnp_ref.py), so the
+The POSE of a 4-point hypothesis is not comparable between implementations (its MtM has a four-dimensional null space whose basis
+rounding chooses, see tests/pnp_ref.py); what a hypothesis computes before and after that basis is, and tests/test_gpu_pnp_hyp.py compares
+it through the taps of ivf_test_pnp_hypotheses (sample, control points, the basis as a basis, the three candidates, the choice, the
+inlier count), taking only the basis as given.  Here the
 device's own hypotheses (hyp_poses, hyp_ninliers) are taken as given and everything after them is replayed: CheckInliers of every
 hypothesis pose in numpy, the bookkeeping of PnPsolver.cc:213-259 over those masks with the restatement's Refine, and the result compared.
 Tolerance of the Refine pose: 4 x the floor committed in tests/golden/pnp_noise.json (the restatement's spread over its two SVD back ends
@@ -14,7 +17,8 @@ between the count without and with those points and equal the count where there 
 that raises mnBestInliers the replay follows every inlier set consistent with the device's count.
 
 The sampler (draws -> indices) is not exposed by the call: the restatement's is checked on the CPU (tests/test_pnp_cpu.py, against a
-transcription of :192-205), the device's on a scene whose NaN-tagged world points name the sample of every iteration (sampler_scene)."""
+transcription of :192-205), the device's on a scene whose NaN-tagged world points name the sample of every iteration (sampler_scene),
+and directly, index by index, in tests/test_gpu_pnp_hyp.py."""
 import json
 import os
 import sys

@@ -100,11 +100,15 @@ TABLE = {
     "solve_pnp": lambda: dict(records=records(), frames=T(i32(N)), xw=T(f32(N, NF, 3)), has_point=T(u8(N, NF)), draws=T(i32(N, MI, 4), any4=True),
                               poses=T(f32(N, 12), exact=True), inlier=T(u8(N, NF)), ninliers=T(i32(N)), max_iterations=MI, probability=0.99, min_inliers=10,
                               epsilon=0.5, th2=5.991, iterations=T(i32(N)), hyp_poses=T(f32(N, MI, 12)), hyp_ninliers=T(i32(N, MI))),
+    "pnp_hypotheses": lambda: dict(records=records(), frames=T(i32(N), defines=True), xw=T(f32(N, NF, 3)), has_point=T(u8(N, NF)), draws=T(i32(N, MI, 4), any4=True),
+                                   taps=T(f64(N, MI, track.PNP_TAP_DOUBLES)), hyp_poses=T(f32(N, MI, 12)), hyp_ninliers=T(i32(N, MI)), max_iterations=MI,
+                                   probability=0.99, min_inliers=10, epsilon=0.5, th2=5.991),
     "solve_sim3": lambda: dict(records=T(u8(N * REC)), pairs=T(i32(N, 2), exact=True), poses=T(f32(N, 12), exact=True), kf_xw=T(f32(N, NF, 3), exact=True),
                                point_flags=T(u8(N, NF)), match12=T(i32(N, NF)), draws=T(i32(N, MI, 3), any4=True), sim3=T(f32(N, 16), exact=True),
                                inlier=T(u8(N, NF)), ninliers=T(i32(N)), max_iterations=MI, probability=0.99, min_inliers=20, fix_scale=True, select=T(i32(N)),
                                state=T(i32(N, 2), exact=True), iterations=T(i32(N)), hyp_sim3=T(f32(N, MI, 16)), hyp_ninliers=T(i32(N, MI))),
 }
+ENTRY = {"pnp_hypotheses": "ivf_test_pnp_hypotheses"}                      # the testing hook; every other method m calls ivf_tracker_<m>
 METHODS = sorted(n for n, f in vars(BatchTracker).items() if inspect.isfunction(f) and not n.startswith("_"))
 
 
@@ -136,7 +140,7 @@ def test_valid_calls_reach_the_library_once_with_every_pointer(method):
     t, args = tracker(), TABLE[method]()
     call(t, method, args)
     (name, full), = t._lib.calls
-    assert name == "ivf_tracker_" + method and len(full) == len(_lib._SIGS[name][1])
+    assert name == ENTRY.get(method, "ivf_tracker_" + method) and len(full) == len(_lib._SIGS[name][1])
     where = {}
     for n, a in args.items():
         if isinstance(a, T):
